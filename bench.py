@@ -7,7 +7,9 @@ on the Dubins-relative 3-D problem, fp64 (BASELINE.json).
 
 One "step" = one odeCFL3 time step = 3 RK substeps over the whole grid; inputs are resident in HBM
 before the timed region; a window of exactly K steps is timed between synchronisations, R times (--repeats,
-default 51), and `value` is the MEDIAN window (inter-quartile range and min/max in "repeats").
+default 51), and `value` is the MEDIAN window (inter-quartile range and min/max in "repeats").  After the untimed
+clock spin-up the state is reset to the initial data, so the W warm-up and R x K timed steps compute the same
+thing in every run with the same arguments (--dump-outputs DIR writes what the last of them returned).
 
 N = 1 (default): BASELINE C2, the 201^3 grid.  The same run also times, each with its own spin-up and
 reported under "also" with its own roofline fraction: the intended WENO5 arithmetic at 201^3, the
@@ -43,13 +45,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# the slab stepper uses three streams (+ RCCL's): give each its own hardware queue, otherwise streams
-# that share a queue serialise (must be set before HIP initialises)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 SPINUP_STEPS = int(os.environ.get("HJ_BENCH_SPINUP", "300"))   # untimed clock ramp before the W warm-up steps
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8 TB/s spec
 BYTES_PER_SUBSTEP = {"float64": 64.0 / 3.0, "float32": 32.0 / 3.0}   # 8 words / RK3 step
+DUMP_MAX_CELLS = 1 << 20        # --dump-outputs: at most 8 MB of fp64 state
 REF_IMPORT = "reference import (BASELINE.md s2, build container, 1 core): 6.6e5 at 51^3, 3.7e5 at 101^3, 1.57e5 at 201^3"
 
 
@@ -80,6 +80,9 @@ def parse():
                     "on the costate range, fused in two launches per stage against the split path)")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps of the single-GPU leg, write what its last step returned as DIR/<name>.npy: y (the "
+                         "state; a fixed seeded sample of %d cells when the grid is larger), t and dt" % DUMP_MAX_CELLS)
     ap.add_argument("--plan-only", action="store_true",
                     help="with --gpus N: print (one JSON line; a table on stderr) what every rank of the N-rank slab leg will do -- slab, "
                          "stepper and schedule, the launches of a substep, halo bytes per step, predicted ms/step -- WITHOUT touching a GPU")
@@ -279,6 +282,7 @@ class StepRunner(object):
 
     def __init__(self, torch, _ffi, DeviceGrid, wl, env=None, share=None):
         self.desc, g, self.ham, par, self.scheme, self.dtype, d0 = wl
+        self.d0 = d0
         old = {}
         for k, v in (env or {}).items():
             old[k] = os.environ.get(k)
@@ -342,6 +346,24 @@ class StepRunner(object):
                 break
         return settle
 
+    def restart(self):
+        """Back to the initial data at t = 0 (untimed): the steps that follow then compute the same thing in every run with the
+        same arguments, however many steps settle() took."""
+        self.state["cur"].copy_(self.d0)
+        self.state["t"] = 0.0
+
+    def dump(self, torch, d):
+        """What the caller of the last step received, as d/<name>.npy: y (the state, in its dtype; DUMP_MAX_CELLS cells drawn
+        with a fixed seed when the grid is larger), t and dt."""
+        y = self.state["cur"].reshape(-1)
+        if y.numel() > DUMP_MAX_CELLS:
+            idx = np.sort(np.random.default_rng(0).choice(y.numel(), DUMP_MAX_CELLS, replace=False))
+            y = y[torch.from_numpy(idx).to(y.device)]
+        os.makedirs(d, exist_ok=True)
+        np.save(os.path.join(d, "y.npy"), y.cpu().numpy())
+        np.save(os.path.join(d, "t.npy"), np.array([self.state["t"]]))
+        np.save(os.path.join(d, "dt.npy"), np.array([self.dtout.value]))
+
     def result(self, torch, walls, devs, settle):
         assert bool(torch.isfinite(self.state["cur"]).all()), "non-finite state after the timed steps (%s)" % self.desc
         nl, fused = C.c_int(3), C.c_int(0)
@@ -353,11 +375,13 @@ class StepRunner(object):
                 "kernel": kern.decode() if kern else "?"}
 
 
-def time_single(torch, _ffi, DeviceGrid, wl, steps, warmup, repeats, spinup):
-    """R repeats of K odeCFL3 steps (hj_rk_step: 3 launches, three arrays) on one GPU.  Returns a dict with
-    the wall seconds and HIP-event milliseconds of every repeat."""
+def time_single(torch, _ffi, DeviceGrid, wl, steps, warmup, repeats, spinup, dump=None):
+    """R repeats of K odeCFL3 steps (hj_rk_step: 3 launches, three arrays) on one GPU, after W warm-up steps from the initial
+    data.  Returns a dict with the wall seconds and HIP-event milliseconds of every repeat; `dump`: directory the outputs of the
+    last step are written to (StepRunner.dump)."""
     rn = StepRunner(torch, _ffi, DeviceGrid, wl)
     settle = rn.settle(torch, steps, spinup)
+    rn.restart()
     for _ in range(warmup):
         rn.one()
     walls, devs = [], []
@@ -365,6 +389,8 @@ def time_single(torch, _ffi, DeviceGrid, wl, steps, warmup, repeats, spinup):
         w, d = rn.window(torch, steps)
         walls.append(w)
         devs.append(d)
+    if dump:
+        rn.dump(torch, dump)
     return rn.result(torch, walls, devs, settle)
 
 
@@ -1061,6 +1087,10 @@ def main():
             print(error_json(a, a.gpus, "--gpus %d but WORLD_SIZE=%d: the launcher started a different number of ranks" % (a.gpus, world)))
         sys.exit(2)
     slab_leg = world > 1 or bool(os.environ.get("HJ_BENCH_FORCE_SLAB")) or (a.global_n not in (None, 0)) or a.workload is not None
+    if a.dump_outputs and slab_leg:
+        if rank == 0:
+            print(error_json(a, world, "--dump-outputs writes the outputs of the single-GPU leg; this run is the slab leg"))
+        sys.exit(2)
     cpu = None
     if rank == 0 and world == 1 and not slab_leg and not a.no_cpu_baseline:
         cpu = CpuBaseline(a.scheme, a.n)     # before the GPU is touched; idle until the GPU legs are done
@@ -1291,7 +1321,7 @@ def run(a, rank, world, local, slab_leg, cpu):
 
     # ---------------------------------------------------------------- single GPU: BASELINE C2 (+ also)
     wl = workload(L, _ffi, torch, a.single, None, None, 0) if a.single else workload(L, _ffi, torch, "dubins", a.scheme, a.dtype, a.n)
-    r = time_single(torch, _ffi, DeviceGrid, wl, a.steps, a.warmup, a.repeats, SPINUP_STEPS)
+    r = time_single(torch, _ffi, DeviceGrid, wl, a.steps, a.warmup, a.repeats, SPINUP_STEPS, dump=a.dump_outputs)
     s = summarize(r, a.steps)
     cells = r["cells"]
     tr = getattr(a, "live", None)

@@ -109,7 +109,9 @@ class HaloExchanger(object):
             r.wait()
         if self.host_staged and reqs:
             import torch
-            if torch.cuda.is_available():
+            # a process that never initialised the GPU has no device work to drain; is_available() would open the GPU in
+            # every host-tensor rank
+            if torch.cuda.is_initialized():
                 torch.cuda.synchronize()
 
     def exchange(self, buf):

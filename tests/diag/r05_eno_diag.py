@@ -1,10 +1,11 @@
 import sys, os
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+TESTS = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(TESTS)); sys.path.insert(0, TESTS)
 import numpy as np, torch
 import levelsetpy_amd as L
 from oracle import hj_oracle as O
 from test_gpu_parity import dubins, sdata, DERIV, mk
-G = dict(np.load("/root/repo/tests/golden/ode.npz"))
+G = dict(np.load(os.path.join(TESTS, "golden", "ode.npz")))
 for scheme in ("ENO2", "ENO3"):
     g, og = dubins(G["dubn_data"].shape)
     sd = sdata(g, L.DubinsVehicleRel(g, 1, 1), DERIV[scheme])

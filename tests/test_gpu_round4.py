@@ -684,6 +684,34 @@ def test_bench_line_contract():
     assert d["parity"]["ok"] is True and d["parity"]["max_abs_diff"] <= d["parity"]["tol"] == 1e-11
 
 
+def test_bench_dump_outputs_repeat_and_follow_steps(tmp_path):
+    """`bench.py --dump-outputs DIR`: two runs with the same arguments write the same y / t / dt bits (the timed steps start from the
+    initial data however long the clock settling took); y is the 201^3 fp64 state sampled to 2^20 cells, t is that of exactly W + R*K
+    steps, so --steps moves it."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def run(tag, steps):
+        d = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--repeats", "3", "--no-also", "--no-live-traffic", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert sorted(os.listdir(d)) == ["dt.npy", "t.npy", "y.npy"]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 << 20
+        return {k: np.load(d / (k + ".npy")) for k in ("y", "t", "dt")}
+    a, b, c = run("a", 3), run("b", 3), run("c", 4)
+    assert a["y"].dtype == np.float64 and a["y"].shape == (1 << 20,) and np.isfinite(a["y"]).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    dt = float(a["dt"][0])
+    assert dt > 0 and float(c["dt"][0]) == dt
+    assert abs(float(a["t"][0]) - (2 + 3 * 3) * dt) <= 1e-12 * float(a["t"][0])
+    assert abs(float(c["t"][0]) - (2 + 3 * 4) * dt) <= 1e-12 * float(c["t"][0])
+    assert not np.array_equal(a["y"], c["y"])
+
+
 @pytest.mark.parametrize("scheme", SCHEMES)
 @pytest.mark.parametrize("n,pd,dtype", [((23, 18, 31), 2, "float64"), ((40, 77), None, "float64"), ((9, 8, 10, 11), (0, 3), "float32"),
                                         ((33, 20, 17), (0, 2), "float32")])

@@ -370,7 +370,10 @@ def test_rewrite_keeps_closures_and_refuses_what_it_cannot_fix():
         TH.trace_callbacks(g, branchy, alpha, None)
 
 
-def test_explain_plan_says_which_path_and_why():
+def test_explain_plan_says_which_path_and_why(monkeypatch):
+    # a registration is verified once per process and expression: with the GPU tests in the same process this expression has been
+    # verified already, so the test starts from an empty registry to see its first use
+    monkeypatch.setattr(TH, "_REG_BY_SOURCE", {})
     g = grid3()
     mk = lambda o: L.Bundle(dict(grid=g, hamFunc=o.hamiltonian, partialFunc=o.dissipation, dissFunc=L.artificialDissipationGLF, CoStateCalc=L.upwindFirstENO2))  # noqa: E731
     e = L.explain_plan(mk(DubinsAbs(g, 1.3, 0.7)))

@@ -2,7 +2,6 @@
 """One GPU, world_size 1, backend nccl (RCCL): periodic axis 0 closed through a self send/recv.
 Checks the RCCL halo path of levelsetpy_amd.dist against the in-kernel periodic wrap and times it."""
 import ctypes as C, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist

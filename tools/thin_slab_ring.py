@@ -6,7 +6,6 @@ RCCL calls -- only the link is missing (the 'exchange' is a device-local copy).
 usage: thin_slab_ring.py [n] [worlds, e.g. 8 or 2,4,8] [schedules: deep,sub,plain] [C4|C5]
 C5: the slabs of the 129^4 fp32 double-pendulum grid (all axes periodic) instead -- n = 129: 65-, 33- and 17-plane slabs of 129^3-cell planes."""
 import os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch, torch.distributed as dist
