@@ -84,7 +84,8 @@ typedef struct hj_ctx hj_ctx;
 
 /* ---- context = the reference's grid Bundle fields the path uses (Grids/process_grid.py:185-293) ----
  * N[ndim] grid.N, xmin[ndim] grid.min, dx[ndim] grid.dx, bc[ndim] HJ_BC_*, toward_zero[ndim]
- * (ghostData.towardZero, add_ghost_extrapolate.py:60-64; may be NULL = all 0). */
+ * (ghostData.towardZero, add_ghost_extrapolate.py:60-64; may be NULL = all 0).  ndim 2..4; ndim 1 only for the
+ * second-order derivatives and hj_term_curvature (every other entry point refuses a 1-D ctx). */
 int hj_ctx_create(hj_ctx** out, int ndim, const int64_t* N, const double* xmin, const double* dx,
                   const int* bc, const int* toward_zero, int dtype, int device);
 void hj_ctx_destroy(hj_ctx* ctx);
@@ -312,6 +313,28 @@ int hj_term_reinit(hj_ctx* ctx, int scheme, const void* y, const void* initial, 
                    double* step_bound);
 int hj_term_convection(hj_ctx* ctx, int scheme, const void* y, const void* const* velocity, const double* velocity_scalar,
                        void* ydot, double* step_bound);
+
+/* ---- the second-order half of the toolbox: centred second-order derivatives and motion by mean curvature, ONE launch each
+ * (hj_curv.h: the compact stencil -- face and (+-1, +-1) diagonal neighbours -- with the ghost cells of
+ * addGhostAllDims(grid, data, 1), corner ghosts included, made on the fly).  The shipped reference functions raise
+ * (DESIGN.md section 2): the formulas are their docstrings' and ToolboxLS's, O&F eq. 1.8 with the mixed partials j < i.
+ * Grids of dimension 1..4 with at least 2 nodes along every axis; not on slabs.  All arrays are device pointers of the ctx
+ * dtype; no output may alias y.
+ *   hj_term_curvature          termCurvature   ExplicitIntegration/Term/term_curvature.py:7 (:140-147)
+ *                              ydot = b kappa |grad phi|; b = array of the grid (or null: b_scalar).  *step_bound (host) =
+ *                              1 / (2 max b sum_i dx_i^-2) (:144), inf when max b == 0.  One host synchronisation when b is an
+ *                              array (its maximum), none for a scalar b.
+ *   hj_curvature_second        curvatureSecond SpatialDerivative/Other/curvature.py:4 (:39-55): kappa and |grad phi|
+ *   hj_hessian_second          hessianSecond   SpatialDerivative/Other/hessian.py:4 (:64-99): first[d], d < dim, and
+ *                              second[i * dim + j] for j <= i (entries with j > i are not read)
+ *   hj_laplacian_second        laplacianSecond SpatialDerivative/Other/laplacian.py:3 (:38-40): sum_i phi_ii
+ *   hj_centered_first_second   centeredFirstSecond SpatialDerivative/Other/centered.py:3 (:42-54): phi_dim, ghost cells of
+ *                              grid.bdry[dim] only */
+int hj_term_curvature(hj_ctx* ctx, const void* y, const void* b, double b_scalar, void* ydot, double* step_bound);
+int hj_curvature_second(hj_ctx* ctx, const void* y, void* curvature, void* grad_mag);
+int hj_hessian_second(hj_ctx* ctx, const void* y, void* const* second, void* const* first);
+int hj_laplacian_second(hj_ctx* ctx, const void* y, void* out);
+int hj_centered_first_second(hj_ctx* ctx, int dim, const void* y, void* out);
 
 /* ---- a user's hamFunc / partialFunc pair as a fused kernel (round 4).  The reference takes ARBITRARY Python callables
  * (ExplicitIntegration/Term/term_lax_friedrich.py:111 hamFunc(t, data, derivC, schemeData);

@@ -26,6 +26,8 @@ from .hji_solver import HJIPDE_solve                                            
 from .gradients import computeGradients                                         # noqa: F401
 from .convection import termConvection                                          # noqa: F401
 from .normal_reinit import termNormal, termReinit                               # noqa: F401
+from .curvature import (curvatureSecond, hessianSecond, laplacianSecond,      # noqa: F401
+                        centeredFirstSecond, termCurvature, termSum, termForcing)
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind                     # noqa: F401
 
 __version__ = "0.1.0"

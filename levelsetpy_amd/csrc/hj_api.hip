@@ -4,6 +4,7 @@
 
 #include "hj_host.h"
 #include "hj_terms.h"
+#include "hj_curv.h"
 
 namespace hjh {
 
@@ -406,6 +407,7 @@ double key_to_double(unsigned long long k) {
 
 // max(D1^2) per dim of `y` -> `out` (ndim values of the ctx dtype, device), stream-ordered
 int weno_eps_to(hj_ctx* c, const void* y, void* out) {
+    if (c->ndim < 2) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4 here, got %d", c->ndim);
     const int64_t S = c->total / c->N[0];
     const int bx = (int)((S + 255) / 256);
     // enough workgroups to fill the GPU a few times over, chunks of at least 8 planes
@@ -449,6 +451,7 @@ int weno_eps_pass(hj_ctx* c, const void* y) { return weno_eps_to(c, y, c->weno_v
 static inline bool weno_rows_fit(const hj_ctx* c) { return (c->total / c->N[0] + 1023) / 1024 <= 512; }
 
 int weno_eps_rows(hj_ctx* c, const void* y, int* nrows) {
+    if (c->ndim < 2) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4 here, got %d", c->ndim);
     *nrows = 0;
     const int64_t S = c->total / c->N[0];
     const int64_t bx = (S + 1023) / 1024;
@@ -723,6 +726,7 @@ static int upwind_all_launch(hj_ctx* c, int scheme, const void* y, void* const* 
 }
 template <typename T>
 static int upwind_all_dispatch(hj_ctx* c, int scheme, const void* y, void* const* dL, void* const* dR, unsigned long long* keys, const T* epsv) {
+    if (c->ndim < 2) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4 here, got %d", c->ndim);
     if (c->ndim == 2) return upwind_all_launch<T, 2>(c, scheme, y, dL, dR, keys, epsv);
     if (c->ndim == 3) return upwind_all_launch<T, 3>(c, scheme, y, dL, dR, keys, epsv);
     return upwind_all_launch<T, 4>(c, scheme, y, dL, dR, keys, epsv);
@@ -1113,7 +1117,9 @@ const char* hj_version(void) { return "hj_mi355x 0.1 (gfx950)"; }
 static int ctx_create_impl(hj_ctx** out, int ndim, const int64_t* N, const double* xmin, const double* dx,
                            const int* bc, const int* toward_zero, int dtype, int device, int dry_cus) {
     if (!out || !N || !xmin || !dx || !bc) return fail(HJ_EINVAL, "null argument");
-    if (ndim < 2 || ndim > HJ_MAX_DIM) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4, got %d", ndim);
+    // 1-D grids: the second-order derivatives and termCurvature (hj_curv.h) only.  Every other entry point's dispatch refuses a
+    // 1-D ctx (weno_eps_to / weno_eps_rows, upwind_all_dispatch, term_run; the substep paths through the Hamiltonian's dimension).
+    if (ndim < 1 || ndim > HJ_MAX_DIM) return fail(HJ_EUNSUPPORTED, "grid.dim must be 1..4, got %d", ndim);
     if (dtype != HJ_F64 && dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", dtype);
     int64_t total = 1;
     for (int d = 0; d < ndim; ++d) {
@@ -1545,6 +1551,7 @@ int term_launch_nd(hj_ctx* c, int kind, int scheme, const void* y, const void* c
 int term_run(hj_ctx* c, int kind, int scheme, const void* y, const void* const* arr, const double* scal, int order,
              void* out, double* k) {
     if (!c || !y || !out) return fail(HJ_EINVAL, "null argument");
+    if (c->ndim < 2) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4 here, got %d", c->ndim);
     scheme = base_scheme(scheme);          // (the fast ENO variants exist for the substep kernels only)
     if (scheme < 0 || scheme > 3) return fail(HJ_EINVAL, "unknown scheme %d", scheme);
     if (y == out) return fail(HJ_EINVAL, "out must not alias the stencil input y");
@@ -1626,6 +1633,116 @@ int hj_term_convection(hj_ctx* c, int scheme, const void* y, const void* const* 
     for (int d = 0; d < c->ndim; ++d) inv += (k[d] > 0.0 ? k[d] : 0.0) / c->dx[d];
     if (step_bound) *step_bound = inv > 0.0 ? 1.0 / inv : std::numeric_limits<double>::infinity();
     return HJ_OK;
+}
+
+// ---- hessianSecond / curvatureSecond / laplacianSecond / centeredFirstSecond / termCurvature: one launch each (hj_curv.h)
+extern "C++" {
+namespace {
+template <typename T, int ND>
+int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double b_scalar, int dim, void* const* out,
+                   unsigned long long* key) {
+    CurvArgs<T, ND> A;
+    memset(&A, 0, sizeof(A));
+    A.y = (const T*)y;
+    hjh::fill_grid<T, ND>(c, A.G);
+    for (int d = 0; d < ND; ++d) {
+        const double di = 1.0 / c->dx[d];
+        A.hdx_inv[d] = (T)(0.5 * di);
+        A.dx_inv2[d] = (T)(di * di);
+    }
+    A.b = (const T*)b;
+    A.b_scalar = (T)b_scalar;
+    A.dim = dim;
+    constexpr int NOUT = ND + ND * (ND + 1) / 2;
+    for (int k = 0; k < NOUT; ++k) A.out[k] = (T*)out[k];
+    A.key = key;
+    const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 16);
+#define HJ_CK(K) hipLaunchKernelGGL((curv_kernel<T, ND, K>), dim3(blocks), dim3(256), 0, c->stream, A)
+    switch (out_kind) {
+        case HJ_CURV_TERM: HJ_CK(HJ_CURV_TERM); break;
+        case HJ_CURV_CURV: HJ_CK(HJ_CURV_CURV); break;
+        case HJ_CURV_LAPL: HJ_CK(HJ_CURV_LAPL); break;
+        case HJ_CURV_HESS: HJ_CK(HJ_CURV_HESS); break;
+        default: HJ_CK(HJ_CURV_CENTERED); break;
+    }
+#undef HJ_CK
+    HIP_TRY(hipGetLastError());
+    c->last_kernel = "curv_kernel";
+    return HJ_OK;
+}
+
+// checks the call and launches; `nout` output arrays, none of which may alias y (the stencil input)
+int curv_run(hj_ctx* c, int out_kind, const void* y, const void* b, double b_scalar, int dim, void* const* out, int nout,
+             unsigned long long* key) {
+    if (!c || !y) return fail(HJ_EINVAL, "null argument");
+    if (c->halo_lo || c->halo_hi) return fail(HJ_EUNSUPPORTED, "the second-order derivatives run on whole grids, not slabs");
+    for (int d = 0; d < c->ndim; ++d)
+        if (c->N[d] < 2) return fail(HJ_EINVAL, "grid too small along dim %d (N=%lld): the ghost rules need 2 nodes", d, (long long)c->N[d]);
+    for (int k = 0; k < nout; ++k) {
+        if (!out[k]) return fail(HJ_EINVAL, "null output array %d", k);
+        if (out[k] == y) return fail(HJ_EINVAL, "output %d must not alias the stencil input y", k);
+    }
+    void* o[HJ_MAX_DIM + HJ_MAX_DIM * (HJ_MAX_DIM + 1) / 2] = {};
+    for (int k = 0; k < nout; ++k) o[k] = out[k];
+#define HJ_CN(T_, ND_) return curv_launch_nd<T_, ND_>(c, out_kind, y, b, b_scalar, dim, o, key)
+    if (c->dtype == HJ_F64) {
+        switch (c->ndim) { case 1: HJ_CN(double, 1); case 2: HJ_CN(double, 2); case 3: HJ_CN(double, 3); case 4: HJ_CN(double, 4); }
+    } else {
+        switch (c->ndim) { case 1: HJ_CN(float, 1); case 2: HJ_CN(float, 2); case 3: HJ_CN(float, 3); case 4: HJ_CN(float, 4); }
+    }
+#undef HJ_CN
+    return fail(HJ_EUNSUPPORTED, "grid.dim %d", c->ndim);
+}
+}  // namespace
+}  // extern "C++"
+
+int hj_term_curvature(hj_ctx* c, const void* y, const void* b, double b_scalar, void* ydot, double* step_bound) {
+    if (!c) return fail(HJ_EINVAL, "null ctx");
+    unsigned long long* key = c->keys + 8;         // the scratch keys term_run uses
+    if (b) HIP_TRY(hipMemsetAsync(key, 0, sizeof(unsigned long long), c->stream));
+    void* out[1] = {ydot};
+    int rc = curv_run(c, HJ_CURV_TERM, y, b, b_scalar, 0, out, 1, key);
+    if (rc) return rc;
+    double mb = b_scalar;
+    if (b) {
+        unsigned long long h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, key, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!h) return fail(HJ_ESTATE, "no reduction of max b");
+        mb = key_to_double(h);
+    }
+    // stepBound = 1 / (2 max b sum_i dx_i^-2)   (term_curvature.py:144, O&F eq. 4.7); inf when nothing moves
+    double s = 0.0;
+    for (int d = 0; d < c->ndim; ++d) s += std::pow(c->dx[d], -2.0);
+    if (step_bound) *step_bound = mb == 0.0 ? std::numeric_limits<double>::infinity() : 1.0 / ((2.0 * mb) * s);
+    return HJ_OK;
+}
+
+int hj_curvature_second(hj_ctx* c, const void* y, void* curvature, void* grad_mag) {
+    void* out[2] = {curvature, grad_mag};
+    return curv_run(c, HJ_CURV_CURV, y, nullptr, 0.0, 0, out, 2, nullptr);
+}
+
+int hj_hessian_second(hj_ctx* c, const void* y, void* const* second, void* const* first) {
+    if (!c || !second || !first) return fail(HJ_EINVAL, "null argument");
+    void* out[HJ_MAX_DIM + HJ_MAX_DIM * (HJ_MAX_DIM + 1) / 2];
+    int k = 0;
+    for (int d = 0; d < c->ndim; ++d) out[k++] = first[d];
+    for (int i = 0; i < c->ndim; ++i)
+        for (int j = 0; j <= i; ++j) out[k++] = second[i * c->ndim + j];
+    return curv_run(c, HJ_CURV_HESS, y, nullptr, 0.0, 0, out, k, nullptr);
+}
+
+int hj_laplacian_second(hj_ctx* c, const void* y, void* out) {
+    void* o[1] = {out};
+    return curv_run(c, HJ_CURV_LAPL, y, nullptr, 0.0, 0, o, 1, nullptr);
+}
+
+int hj_centered_first_second(hj_ctx* c, int dim, const void* y, void* out) {
+    if (!c) return fail(HJ_EINVAL, "null ctx");
+    if (dim < 0 || dim >= c->ndim) return fail(HJ_EINVAL, "Illegal dim parameter");
+    void* o[1] = {out};
+    return curv_run(c, HJ_CURV_CENTERED, y, nullptr, 0.0, dim, o, 1, nullptr);
 }
 
 int hj_rk_combine(hj_ctx* c, int mode, double dt, const void* x0, const void* y, const void* z, void* out, int64_t n) {

@@ -322,9 +322,12 @@ def integrate_span_device(schemeFunc, schemeData, y, t0, tf, options, stop_tol, 
 
 def _any_device_grid(schemeData, like):
     """The DeviceGrid of the grid a (possibly wrapped) schemeData carries, for the dtype of `like`; None if
-    there is none (the elementwise stage kernels only need a ctx of the right dtype and device)."""
+    there is none (the elementwise stage kernels only need a ctx of the right dtype and device).  A list innerData
+    (termSum's cell vector of inner schemeData) is searched in order for the first entry that carries a grid."""
     sd = schemeData[0] if iscell(schemeData) else schemeData
     for _ in range(4):
+        if iscell(sd):
+            sd = next((e for e in sd if 'grid' in getattr(e, '__dict__', ())), sd[0] if sd else None)
         if sd is None:
             return None
         if isfield(sd, 'grid'):
