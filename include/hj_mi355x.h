@@ -85,7 +85,7 @@ typedef struct hj_ctx hj_ctx;
 /* ---- context = the reference's grid Bundle fields the path uses (Grids/process_grid.py:185-293) ----
  * N[ndim] grid.N, xmin[ndim] grid.min, dx[ndim] grid.dx, bc[ndim] HJ_BC_*, toward_zero[ndim]
  * (ghostData.towardZero, add_ghost_extrapolate.py:60-64; may be NULL = all 0).  ndim 2..4; ndim 1 only for the
- * second-order derivatives and hj_term_curvature (every other entry point refuses a 1-D ctx). */
+ * second-order derivatives, hj_term_curvature and hj_term_trace_hessian (every other entry point refuses a 1-D ctx). */
 int hj_ctx_create(hj_ctx** out, int ndim, const int64_t* N, const double* xmin, const double* dx,
                   const int* bc, const int* toward_zero, int dtype, int device);
 void hj_ctx_destroy(hj_ctx* ctx);
@@ -335,6 +335,15 @@ int hj_curvature_second(hj_ctx* ctx, const void* y, void* curvature, void* grad_
 int hj_hessian_second(hj_ctx* ctx, const void* y, void* const* second, void* const* first);
 int hj_laplacian_second(hj_ctx* ctx, const void* y, void* out);
 int hj_centered_first_second(hj_ctx* ctx, int dim, const void* y, void* out);
+
+/* ---- termTraceHessian (ExplicitIntegration/Term/term_trace_hess.py:8): ydot = trace(L D^2phi R), unnegated, ONE launch of the
+ * Hessian stencil above (hj_curv.h).  The shipped term raises; the formula is its docstring's and ToolboxLS's.
+ * L and R are dim x dim, row-major: entry e is the device array L_arr[e] (ctx dtype, grid-shaped, contiguous) or, where L_arr is
+ * NULL or L_arr[e] is NULL, the scalar L_scalar[e] (likewise R).  ydot must alias neither y nor a matrix array.
+ * *step_bound = 1 / (2 max |trace((L D) R)|), D[m][k] = 1 / (dx_m dx_k) (:118-122), inf when that max is 0: computed on the host
+ * when every entry is a scalar; otherwise reduced by the launch (one host synchronisation). */
+int hj_term_trace_hessian(hj_ctx* ctx, const void* y, const void* const* L_arr, const double* L_scalar,
+                          const void* const* R_arr, const double* R_scalar, void* ydot, double* step_bound);
 
 /* ---- a user's hamFunc / partialFunc pair as a fused kernel (round 4).  The reference takes ARBITRARY Python callables
  * (ExplicitIntegration/Term/term_lax_friedrich.py:111 hamFunc(t, data, derivC, schemeData);

@@ -28,6 +28,8 @@ from .convection import termConvection                                          
 from .normal_reinit import termNormal, termReinit                               # noqa: F401
 from .curvature import (curvatureSecond, hessianSecond, laplacianSecond,      # noqa: F401
                         centeredFirstSecond, termCurvature, termSum, termForcing)
+from .trace_hessian import (termTraceHessian, termDiscount,                     # noqa: F401
+                            cellMatrixMultiply, cellMatrixTrace)
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind                     # noqa: F401
 
 __version__ = "0.1.0"

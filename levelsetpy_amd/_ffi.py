@@ -75,6 +75,7 @@ SIGNATURES = {
     "hj_hessian_second": (_i, [_vp, _vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "hj_laplacian_second": (_i, [_vp, _vp, _vp]),
     "hj_centered_first_second": (_i, [_vp, _i, _vp, _vp]),
+    "hj_term_trace_hessian": (_i, [_vp, _vp, C.POINTER(_vp), _pd, C.POINTER(_vp), _pd, _vp, _pd]),
     "hj_ham_register": (_i, [C.c_char_p, _i, _i, C.c_char_p, C.c_char_p, _i, C.c_char_p, C.c_char_p, _pi]),
     "hj_ham_register2": (_i, [C.c_char_p, _i, _i, C.c_char_p, C.c_char_p, _i, _i, C.c_char_p, C.c_char_p, _pi]),
     "hj_ham_flags": (_i, [_i, _pi]),

@@ -1638,9 +1638,18 @@ int hj_term_convection(hj_ctx* c, int scheme, const void* y, const void* const* 
 // ---- hessianSecond / curvatureSecond / laplacianSecond / centeredFirstSecond / termCurvature: one launch each (hj_curv.h)
 extern "C++" {
 namespace {
+// termTraceHessian's matrices as the host hands them over: ND x ND row-major, an array entry or (null) the scalar
+struct TraceIn {
+    const void* L[HJ_MAX_DIM * HJ_MAX_DIM];
+    const void* R[HJ_MAX_DIM * HJ_MAX_DIM];
+    double Ls[HJ_MAX_DIM * HJ_MAX_DIM];
+    double Rs[HJ_MAX_DIM * HJ_MAX_DIM];
+    bool reduce;
+};
+
 template <typename T, int ND>
 int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double b_scalar, int dim, void* const* out,
-                   unsigned long long* key) {
+                   unsigned long long* key, const TraceIn* tin) {
     CurvArgs<T, ND> A;
     memset(&A, 0, sizeof(A));
     A.y = (const T*)y;
@@ -1657,8 +1666,26 @@ int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double
     for (int k = 0; k < NOUT; ++k) A.out[k] = (T*)out[k];
     A.key = key;
     const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 16);
-#define HJ_CK(K) hipLaunchKernelGGL((curv_kernel<T, ND, K>), dim3(blocks), dim3(256), 0, c->stream, A)
+#define HJ_CK(K) hipLaunchKernelGGL((curv_kernel<T, ND, K>), dim3(blocks), dim3(256), 0, c->stream, A, CurvTraceArgs<T, ND, K>{})
     switch (out_kind) {
+        case HJ_CURV_TRACE: {
+            TraceArgs<T, ND> TR;
+            memset(&TR, 0, sizeof(TR));
+            for (int m = 0; m < ND; ++m)
+                for (int k = 0; k < ND; ++k) {
+                    const int e = m * ND + k;
+                    TR.L[e] = (const T*)tin->L[e];
+                    TR.R[e] = (const T*)tin->R[e];
+                    TR.Ls[e] = (T)tin->Ls[e];
+                    TR.Rs[e] = (T)tin->Rs[e];
+                    TR.dd[e] = 1.0 / (c->dx[m] * c->dx[k]);
+                }
+            TR.reduce = tin->reduce;
+            // all-scalar matrices: the instantiation without the entry loads and the reduction (fewer VGPRs)
+            if (tin->reduce) hipLaunchKernelGGL((curv_kernel<T, ND, HJ_CURV_TRACE>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
+            else hipLaunchKernelGGL((curv_kernel<T, ND, HJ_CURV_TRACE_SC>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
+            break;
+        }
         case HJ_CURV_TERM: HJ_CK(HJ_CURV_TERM); break;
         case HJ_CURV_CURV: HJ_CK(HJ_CURV_CURV); break;
         case HJ_CURV_LAPL: HJ_CK(HJ_CURV_LAPL); break;
@@ -1673,7 +1700,7 @@ int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double
 
 // checks the call and launches; `nout` output arrays, none of which may alias y (the stencil input)
 int curv_run(hj_ctx* c, int out_kind, const void* y, const void* b, double b_scalar, int dim, void* const* out, int nout,
-             unsigned long long* key) {
+             unsigned long long* key, const TraceIn* tin = nullptr) {
     if (!c || !y) return fail(HJ_EINVAL, "null argument");
     if (c->halo_lo || c->halo_hi) return fail(HJ_EUNSUPPORTED, "the second-order derivatives run on whole grids, not slabs");
     for (int d = 0; d < c->ndim; ++d)
@@ -1684,7 +1711,7 @@ int curv_run(hj_ctx* c, int out_kind, const void* y, const void* b, double b_sca
     }
     void* o[HJ_MAX_DIM + HJ_MAX_DIM * (HJ_MAX_DIM + 1) / 2] = {};
     for (int k = 0; k < nout; ++k) o[k] = out[k];
-#define HJ_CN(T_, ND_) return curv_launch_nd<T_, ND_>(c, out_kind, y, b, b_scalar, dim, o, key)
+#define HJ_CN(T_, ND_) return curv_launch_nd<T_, ND_>(c, out_kind, y, b, b_scalar, dim, o, key, tin)
     if (c->dtype == HJ_F64) {
         switch (c->ndim) { case 1: HJ_CN(double, 1); case 2: HJ_CN(double, 2); case 3: HJ_CN(double, 3); case 4: HJ_CN(double, 4); }
     } else {
@@ -1715,6 +1742,59 @@ int hj_term_curvature(hj_ctx* c, const void* y, const void* b, double b_scalar, 
     double s = 0.0;
     for (int d = 0; d < c->ndim; ++d) s += std::pow(c->dx[d], -2.0);
     if (step_bound) *step_bound = mb == 0.0 ? std::numeric_limits<double>::infinity() : 1.0 / ((2.0 * mb) * s);
+    return HJ_OK;
+}
+
+// trace((L D) R) with D[m][k] = 1 / (dx_m dx_k), in the order of the kernel's trace_triple (term_trace_hess.py:119-121)
+static double trace_ldr(const hj_ctx* c, const double* L, const double* R) {
+#pragma clang fp contract(off)
+    const int n = c->ndim;
+    double tr = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double a = 0.0;
+        for (int k = 0; k < n; ++k) {
+            double lp = L[i * n] * (1.0 / (c->dx[0] * c->dx[k]));
+            for (int m = 1; m < n; ++m) lp = lp + L[i * n + m] * (1.0 / (c->dx[m] * c->dx[k]));
+            a = k == 0 ? lp * R[i] : a + lp * R[k * n + i];
+        }
+        tr = i == 0 ? a : tr + a;
+    }
+    return tr;
+}
+
+int hj_term_trace_hessian(hj_ctx* c, const void* y, const void* const* L_arr, const double* L_scalar,
+                          const void* const* R_arr, const double* R_scalar, void* ydot, double* step_bound) {
+    if (!c || !y) return fail(HJ_EINVAL, "null argument");
+    const int nn = c->ndim * c->ndim;
+    TraceIn tin;
+    memset(&tin, 0, sizeof(tin));
+    for (int e = 0; e < nn; ++e) {
+        tin.L[e] = L_arr ? L_arr[e] : nullptr;
+        tin.R[e] = R_arr ? R_arr[e] : nullptr;
+        if ((!tin.L[e] && !L_scalar) || (!tin.R[e] && !R_scalar))
+            return fail(HJ_EINVAL, "matrix entry %d is neither an array nor a scalar", e);
+        tin.Ls[e] = tin.L[e] ? 0.0 : L_scalar[e];
+        tin.Rs[e] = tin.R[e] ? 0.0 : R_scalar[e];
+        if (ydot && (ydot == tin.L[e] || ydot == tin.R[e])) return fail(HJ_EINVAL, "ydot must not alias a matrix entry (%d)", e);
+        tin.reduce = tin.reduce || tin.L[e] || tin.R[e];
+    }
+    unsigned long long* key = c->keys + 8;         // the scratch keys term_run uses
+    if (tin.reduce) HIP_TRY(hipMemsetAsync(key, 0, sizeof(unsigned long long), c->stream));
+    void* out[1] = {ydot};
+    int rc = curv_run(c, HJ_CURV_TRACE, y, nullptr, 0.0, 0, out, 1, key, &tin);
+    if (rc) return rc;
+    // stepBound = 1 / (2 max |trace((L D) R)|) (term_trace_hess.py:118-122, "a guess"); inf when nothing diffuses
+    double mt;
+    if (tin.reduce) {
+        unsigned long long h = 0;
+        HIP_TRY(hipMemcpyAsync(&h, key, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (!h) return fail(HJ_ESTATE, "no reduction of max |trace(L D R)|");
+        mt = key_to_double(h);
+    } else {
+        mt = std::fabs(trace_ldr(c, tin.Ls, tin.Rs));
+    }
+    if (step_bound) *step_bound = mt == 0.0 ? std::numeric_limits<double>::infinity() : 1.0 / (2.0 * mt);
     return HJ_OK;
 }
 

@@ -5,6 +5,7 @@
 //   laplacianSecond      sum_i phi_ii                                        SpatialDerivative/Other/laplacian.py:3
 //   centeredFirstSecond  the centred first partial of one dimension          SpatialDerivative/Other/centered.py:3
 //   termCurvature        ydot = b kappa |grad phi|  (+ max b for the CFL)    ExplicitIntegration/Term/term_curvature.py:7
+//   termTraceHessian     ydot = trace(L D^2phi R)  (+ max |trace(L D R)|)    ExplicitIntegration/Term/term_trace_hess.py:8
 //
 // The shipped hessianSecond raises (hessian.py:61,71), so curvatureSecond / laplacianSecond / termCurvature do too; the
 // curvature loop over mixed partials runs j < i - 1 (curvature.py:48 and hessian.py:88, a mistranslation of MATLAB's j = 1:i-1) and drops
@@ -27,7 +28,8 @@
 
 namespace hj {
 
-enum { HJ_CURV_TERM = 0, HJ_CURV_CURV = 1, HJ_CURV_LAPL = 2, HJ_CURV_HESS = 3, HJ_CURV_CENTERED = 4 };
+enum { HJ_CURV_TERM = 0, HJ_CURV_CURV = 1, HJ_CURV_LAPL = 2, HJ_CURV_HESS = 3, HJ_CURV_CENTERED = 4, HJ_CURV_TRACE = 5,
+       HJ_CURV_TRACE_SC = 6 };   // TRACE_SC: HJ_CURV_TRACE with every matrix entry a scalar (no loads, no reduction)
 
 // number of (face + diagonal) neighbours of the compact second-order stencil
 template <int ND> struct CurvStencil {
@@ -45,8 +47,27 @@ template <typename T, int ND> struct CurvArgs {
     int dim;                      // HJ_CURV_CENTERED: the dimension
     T* out[ND + ND * (ND + 1) / 2];   // TERM: ydot; CURV: kappa, |grad phi|; LAPL: sum; CENTERED: deriv;
                                       // HESS: first[0..ND), then second(i, j), j <= i, row by row
-    unsigned long long* key;      // HJ_CURV_TERM with array b: atomicMax key of max b
+    unsigned long long* key;      // HJ_CURV_TERM with array b: atomicMax key of max b; HJ_CURV_TRACE with reduce: of max |T|
 };
+
+// HJ_CURV_TRACE / HJ_CURV_TRACE_SC only (no other mode reads it): the ND x ND matrices L and R, row-major, entry e a grid-shaped
+// array (L[e] non-null) or the scalar Ls[e] (likewise R); dd[m * ND + k] = 1 / (dx_m dx_k), the D of the step bound (:119)
+template <typename T, int ND> struct TraceArgs {
+    const T* L[ND * ND];
+    const T* R[ND * ND];
+    T Ls[ND * ND];
+    T Rs[ND * ND];
+    double dd[ND * ND];
+    int reduce;                   // some entry is an array: reduce max |trace((L D) R)| into key
+};
+// the kernel's second argument: TraceArgs for the trace modes, empty for the others.  Chosen by specialisation, not by an
+// expression over the (unnamed) mode enum: such an expression is part of the kernel's mangled name, and the host and device
+// compilations number unnamed types independently, so the host stub would register a name the code object lacks.
+struct NoTraceArgs {};
+template <typename T, int ND, int OUT> struct CurvTraceArgsOf { using type = NoTraceArgs; };
+template <typename T, int ND> struct CurvTraceArgsOf<T, ND, HJ_CURV_TRACE> { using type = TraceArgs<T, ND>; };
+template <typename T, int ND> struct CurvTraceArgsOf<T, ND, HJ_CURV_TRACE_SC> { using type = TraceArgs<T, ND>; };
+template <typename T, int ND, int OUT> using CurvTraceArgs = typename CurvTraceArgsOf<T, ND, OUT>::type;
 
 // phi on the ghost-padded array at idx + a e_p + c e_q (p < q; c = 0: a face neighbour, q unused).  addGhostAllDims pads
 // dimension 0 first, then dimension 1 of the already padded array, and so on: a corner ghost (outside in p AND in q) is
@@ -84,8 +105,30 @@ __device__ __forceinline__ long long nb_offset(const GridArgs<T, ND>& G, const i
     return (long long)(k - idx[d]) * G.stride[d];
 }
 
+// trace(M1 P M2) for ND x ND matrices as cellMatrixMultiply / cellMatrixTrace evaluate it (term_trace_hess.py:115-116): the
+// products over ascending k starting from the k = 0 product, then the diagonal summed over ascending i; only the diagonal of
+// (M1 P) M2 is formed.  U is the arithmetic type.
+template <typename U, int ND, typename F1, typename FP, typename F2>
+__device__ __forceinline__ U trace_triple(F1 m1, FP p, F2 m2) {
+#pragma clang fp contract(off)
+    U tr = U(0);
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+        U a = U(0);
+#pragma unroll
+        for (int k = 0; k < ND; ++k) {
+            U lp = m1(i, 0) * p(0, k);
+#pragma unroll
+            for (int m = 1; m < ND; ++m) lp = lp + m1(i, m) * p(m, k);
+            a = k == 0 ? lp * m2(0, i) : a + lp * m2(k, i);
+        }
+        tr = i == 0 ? a : tr + a;
+    }
+    return tr;
+}
+
 template <typename T, int ND, int OUT>
-__global__ __launch_bounds__(256) void curv_kernel(const CurvArgs<T, ND> A) {
+__global__ __launch_bounds__(256) void curv_kernel(const CurvArgs<T, ND> A, const CurvTraceArgs<T, ND, OUT> TR) {
 #pragma clang fp contract(off)
     constexpr int NP = CurvStencil<ND>::NPAIR;
     double mb = -1e300;
@@ -128,6 +171,22 @@ __global__ __launch_bounds__(256) void curv_kernel(const CurvArgs<T, ND> A) {
                 for (int q = p + 1; q < ND; ++q, ++k)
 #pragma unroll
                     for (int s = 0; s < 4; ++s) g[k][s] = pc0[of[p][s & 1] + of[q][s >> 1]];
+        }
+        // the trace modes: the entries of L and R at this node, loaded with the stencil (an array entry's pointer is uniform)
+        constexpr bool TRACE = OUT == HJ_CURV_TRACE || OUT == HJ_CURV_TRACE_SC;
+        constexpr int NM = TRACE ? ND * ND : 1;
+        T Lm[NM], Rm[NM];
+        if constexpr (TRACE) {
+#pragma unroll
+            for (int e = 0; e < ND * ND; ++e) {
+                if constexpr (OUT == HJ_CURV_TRACE_SC) {
+                    Lm[e] = TR.Ls[e];
+                    Rm[e] = TR.Rs[e];
+                } else {
+                    Lm[e] = TR.L[e] ? TR.L[e][t] : TR.Ls[e];
+                    Rm[e] = TR.R[e] ? TR.R[e][t] : TR.Rs[e];
+                }
+            }
         }
         if (__any(ghost ? 1 : 0)) {
             // the waves at an extrapolated edge: the ghost values of addGhostAllDims in its order (padded_value)
@@ -178,6 +237,24 @@ __global__ __launch_bounds__(256) void curv_kernel(const CurvArgs<T, ND> A) {
                     sij[k] = A.hdx_inv[p] * (fq_p - fq_m);
                 }
         }
+        if constexpr (TRACE) {
+            // term_trace_hess.py:103-127: P the full symmetric Hessian (:110-112), ydot = trace(L P R) unnegated (:115-116, :127)
+            auto P = [&](int m, int k) -> T {
+                if (m == k) return sii[m];
+                const int j = m < k ? m : k, i = m < k ? k : m;
+                return sij[j * ND - j * (j + 1) / 2 + (i - j - 1)];
+            };
+            A.out[0][t] = trace_triple<T, ND>([&](int i, int k) { return Lm[i * ND + k]; }, P,
+                                              [&](int k, int i) { return Rm[k * ND + i]; });
+            if (OUT == HJ_CURV_TRACE && TR.reduce) {
+                // the step bound's T(x) = trace((L D) R) (:119-122) in double, whatever T is
+                const double tx = trace_triple<double, ND>([&](int i, int k) { return (double)Lm[i * ND + k]; },
+                                                           [&](int m, int k) { return TR.dd[m * ND + k]; },
+                                                           [&](int k, int i) { return (double)Rm[k * ND + i]; });
+                mb = fmax(mb, fabs(tx));
+            }
+            continue;
+        }
         if constexpr (OUT == HJ_CURV_HESS) {
 #pragma unroll
             for (int d = 0; d < ND; ++d) A.out[d][t] = fi[d];
@@ -215,8 +292,10 @@ __global__ __launch_bounds__(256) void curv_kernel(const CurvArgs<T, ND> A) {
             if (A.b) mb = fmax(mb, (double)bb);
         }
     }
-    if constexpr (OUT == HJ_CURV_TERM) {
-        if (!A.b) return;         // uniform across the launch: no thread reaches the barrier
+    if constexpr (OUT == HJ_CURV_TERM || OUT == HJ_CURV_TRACE) {
+        // uniform across the launch: no thread reaches the barrier
+        if constexpr (OUT == HJ_CURV_TERM) { if (!A.b) return; }
+        else { if (!TR.reduce) return; }
         __shared__ double red[4];
         const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
         const double w = wave_max(mb);
