@@ -166,11 +166,11 @@ def _integrate(order, schemeFunc, tspan, y0, options, schemeData):
     dev = _device_plan(schemeFunc, schemeData, y0)
     if dev is not None:
         _check_shape(schemeFunc, y0)
-        return _integrate_device(order, dev, tspan, y0, options, schemeData)
+        return _integrate_device(order, dev, tspan, y0, options, schemeData, schemeFunc)
     return _integrate_generic(order, schemeFunc, tspan, y0, options, schemeData, small, safetyFactorCFL)
 
 
-def _integrate_device(order, dev, tspan, y0, options, schemeData):
+def _integrate_device(order, dev, tspan, y0, options, schemeData, schemeFunc):
     plan, rs = dev
     grid, sid, ham, par = plan
     small = 100 * eps
@@ -260,6 +260,27 @@ def _integrate_device(order, dev, tspan, y0, options, schemeData):
             if steps > 1 and np.any(np.sign(eventValue) != np.sign(eventValueOld)):
                 break
             eventValueOld = eventValue
+        if not (post or terminal) or tf - t < small * abs(tf):
+            continue
+        # a hook may have changed the system in place or handed back another schemeData: the next step runs what the reference's next
+        # schemeFunc call would (ode_cfl_3.py:246-247, :38) -- the plan is looked up again (a cached lookup when nothing changed)
+        dev = _device_plan(schemeFunc, schemeData, dg.like(cur.reshape(shape0), y0, lazy=True))
+        if dev is None or dev[1] != rs or dev[0][0] is not grid:
+            # no longer fusable here: the rest of the span on the generic loop, from this t and y
+            if dynamic and order > 1:
+                _warn_late_bounds(lib, ctx, order, safetyFactorCFL, warn, wait=True, dt_last=dtout.value)
+            return _integrate_generic(order, schemeFunc, [t, tf], dg.like(cur.reshape(shape0), y0), options, schemeData, small, safetyFactorCFL,
+                                      steps, eventValueOld)
+        new = dev[0]
+        if new is not plan and (new[1], new[2], tuple(new[3]), new.diss) != (sid, ham, tuple(par), plan.diss):
+            if dynamic and order > 1:
+                _warn_late_bounds(lib, ctx, order, safetyFactorCFL, warn, wait=True, dt_last=dtout.value)
+            plan = new
+            grid, sid, ham, par = plan
+            plan.bind(dg)
+            parv = plan.parv
+            dynamic = getattr(plan, 'dynamic', False)
+            sb_static = plan.static_step_bound(dg)
     if dynamic and order > 1 and steps > 0 and not single:
         _warn_late_bounds(lib, ctx, order, safetyFactorCFL, warn, wait=True, dt_last=dtout.value)   # the last step's (a singleStep call leaves them to the next call)
     if strcmp(options.stats, 'on'):
@@ -339,14 +360,13 @@ def _any_device_grid(schemeData, like):
     return None
 
 
-def _integrate_generic(order, schemeFunc, tspan, y0, options, schemeData, small, safetyFactorCFL):
+def _integrate_generic(order, schemeFunc, tspan, y0, options, schemeData, small, safetyFactorCFL, steps=0, eventValueOld=None):
+    # (steps, eventValueOld: where a device span left off -- _integrate_device hands the rest of a span here when a hook made it unfusable)
     t = tspan[0]
     tf = tspan[1]
-    steps = 0
     startTime = cputime()
     y = copy.copy(y0)
     post = _post_hook(options)
-    eventValueOld = None
 
     def combine(mode, deltaT, x0, ycur, ydot):
         """One odeCFLn stage expression (ode_cfl_3.py:151,184-193,226-241; ode_cfl_2.py:184-201): a single

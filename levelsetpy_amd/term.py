@@ -94,18 +94,25 @@ _PLAN_CACHE = weakref.WeakKeyDictionary()
 
 def native_plan(schemeData, y=None):
     """(grid, scheme_id, ham_id, params) if this LF schemeData can run fused, else None.  y: the data the caller is about to step --
-    a plan TRACED from Python callbacks (trace_ham.py) is checked against them on the first data it meets, and is not used before."""
+    a plan TRACED from Python callbacks (trace_ham.py) is checked against them on the first data of each floating type it meets, and is not
+    used before."""
     sd = schemeData[0] if iscell(schemeData) else schemeData
     plan = _plan_of(sd)
-    if plan is not None and plan.traced and not getattr(plan.system.reg, "verified", False):
-        plan = _verify_traced(plan, sd, y)
+    if plan is not None and plan.traced:
+        done = getattr(plan.system.reg, "verified_dtypes", ())
+        if (array_dtype_name(y) if y is not None else None) not in done:
+            if y is None and done:
+                return plan
+            plan = _verify_traced(plan, sd, y)
     return plan
 
 
 def explain_plan(schemeData):
     """Which path a Lax-Friedrichs schemeData takes and why -- for the question "why is this slow?".  Returns a dict: path = 'built-in' |
     'registered' (user_ham.attach) | 'traced' | 'split', reason (split: what stopped the classification or the tracer), source (traced: the
-    generated device expression), verified (traced: has the kernel been checked against the callbacks yet -- it is on first use)."""
+    generated device expression), verified (traced: has the kernel been checked against the callbacks yet -- it is on first use), verified_dtypes
+    (the floating types it has been checked in: each is checked on its own first use), unchecked (state the callbacks can see where the
+    fingerprint's bounds stop: a change there is not seen)."""
     sd = schemeData[0] if iscell(schemeData) else schemeData
     for f in ('grid', 'dissFunc', 'hamFunc', 'partialFunc'):
         if not isfield(sd, f):
@@ -127,8 +134,9 @@ def explain_plan(schemeData):
     if plan is None:
         return dict(path='split', reason='the traced kernel disagreed with the callbacks on first use, the expression keeps changing, or the library '
                                          'refused the registration (HJ_TRACE_VERBOSE=1 says which)', source=tr.source)
+    done = sorted(getattr(plan.system.reg, "verified_dtypes", ()))
     return dict(path='traced', ham_id=plan[2], params=list(plan[3]), source=tr.source, column_source=tr.column_source,
-                uses_range=tr.uses_range, verified=bool(getattr(plan.system.reg, "verified", False)))
+                uses_range=tr.uses_range, verified=bool(done), verified_dtypes=done, unchecked=list(tr.unchecked))
 
 
 def _plan_of(sd):
@@ -192,54 +200,87 @@ def _classify(sd, fn):
     return _Plan((sd.grid, sid, nat[1], nat[2]), kind, nat[0], dynamic, traced)
 
 
+def _isolated(mask):
+    """No two True entries of this grid-shaped boolean array are face neighbours."""
+    for d in range(mask.ndim):
+        n = mask.shape[d]
+        a = mask.narrow(d, 0, n - 1) if is_tensor(mask) else np.take(mask, np.arange(n - 1), axis=d)
+        b = mask.narrow(d, 1, n - 1) if is_tensor(mask) else np.take(mask, np.arange(1, n), axis=d)
+        if bool((a & b).any()):
+            return False
+    return True
+
+
 def _verify_traced(plan, sd, y):
-    """First use of a kernel generated from Python callbacks: the term by BOTH paths on the caller's data.  Agreement to rounding marks the
-    registration verified (once per process and expression); anything else drops the trace with a warning and the split path stays."""
+    """First use of a kernel generated from Python callbacks, per floating type: the term by BOTH paths on the caller's data.  Agreement marks
+    the registration verified for that type (once per process, expression and type); anything else drops the trace with a warning and the
+    split path stays.  Agreement: with a WENO scheme every node within rounding of the callbacks' result; with an ENO scheme a stencil choice
+    may flip where the two arithmetics differ in the last bit, so a few nodes may differ more -- but only ISOLATED ones (no two face
+    neighbours): a wrong plane, row or region is an expression error however few nodes it holds."""
     if y is None:
         return None
     reg = plan.system.reg
+    import os
     import warnings
+    name = getattr(sd.hamFunc, "__qualname__", sd.hamFunc)
+    y0 = y.reshape(-1, 1)
     try:
-        y0 = y.reshape(-1, 1)
         fused, sb_f, dg = _fused_term(plan, 0.0, y0, 0)
-        split, sb_s, _ = _split_term(0.0, y0, sd, sd)
-        f = dg.like(fused, split, (dg.numel, 1))
-        if is_tensor(split):
-            diff = (f - split.reshape(-1, 1)).abs()
-            scale = float(split.abs().max()) + 1e-300
-            finite = bool(diff.isfinite().all())
-            tol = (1e-9 if str(split.dtype).endswith("64") else 2e-4) * scale
-            frac = float((diff > tol).double().mean())
-            worst = float(diff.max())
-        else:
-            f, s_ = np.asarray(f).reshape(-1, 1), np.asarray(split).reshape(-1, 1)
-            diff = np.abs(f - s_)
-            scale = float(np.abs(s_).max()) + 1e-300
-            finite = bool(np.isfinite(diff).all())
-            tol = (1e-9 if s_.dtype == np.float64 else 2e-4) * scale
-            frac = float((diff > tol).mean())
-            worst = float(diff.max())
-        # (an ENO stencil choice may flip where the two arithmetics differ in the last bit: a few isolated nodes, not an expression error)
-        single = not str(getattr(split, "dtype", "float64")).endswith("64")
-        ok = finite and frac <= 2e-3 and worst <= 5e-2 * scale and abs(sb_f - sb_s) <= (1e-4 if single else 1e-7) * abs(sb_s)
     except (_ffi.Unsupported, _trace.TraceError) as e:
         # (no kernel for this grid -- no tiling, too few nodes -- or a callback that met something symbolic it had kept: the split path)
-        import os
         if os.environ.get("HJ_TRACE_VERBOSE"):
-            warnings.warn("levelsetpy_amd: the traced kernel of %r was not used: %s: %s" % (getattr(sd.hamFunc, "__qualname__", sd.hamFunc), type(e).__name__, e))
+            warnings.warn("levelsetpy_amd: the traced kernel of %r was not used: %s: %s" % (name, type(e).__name__, e))
         return None
+    except Exception as e:
+        # (a hipRTC compile error, a HIP error raised by _ffi.check: the split path would have worked -- it is taken, and the expression is not
+        #  tried again)
+        _drop_traced(reg, sd)
+        warnings.warn("levelsetpy_amd: the kernel traced from %r failed on first use (%s: %s): the split path is used" % (name, type(e).__name__, e))
+        return None
+    split, sb_s, _ = _split_term(0.0, y0, sd, sd)
+    f = dg.like(fused, split, (dg.numel, 1))
+    single = not str(getattr(split, "dtype", "float64")).endswith("64")
+    eno = plan[1] not in (_ffi.SCHEME_IDS["WENO5"], _ffi.SCHEME_IDS["WENO5_ASSHIPPED"])
+    if is_tensor(split):
+        diff = (f - split.reshape(-1, 1)).abs()
+        scale = float(split.abs().max()) + 1e-300
+        finite = bool(diff.isfinite().all())
+        tol = (2e-4 if single else 1e-9) * scale
+        off = (diff > tol).reshape(tuple(int(n) for n in dg.shape))
+        frac = float(off.double().mean())
+        worst = float(diff.max())
+    else:
+        f, s_ = np.asarray(f).reshape(-1, 1), np.asarray(split).reshape(-1, 1)
+        diff = np.abs(f - s_)
+        scale = float(np.abs(s_).max()) + 1e-300
+        finite = bool(np.isfinite(diff).all())
+        tol = (2e-4 if single else 1e-9) * scale
+        off = (diff > tol).reshape(tuple(int(n) for n in dg.shape))
+        frac = float(off.mean())
+        worst = float(diff.max())
+    ok = finite and abs(sb_f - sb_s) <= (1e-4 if single else 1e-7) * abs(sb_s)
+    if eno:
+        ok = ok and frac <= 2e-3 and worst <= 5e-2 * scale and (frac == 0 or _isolated(off))
+    else:
+        ok = ok and frac == 0
     if not ok:
-        _trace.mark_bad(reg)
-        try:
-            del _PLAN_CACHE[sd]
-        except (KeyError, TypeError):
-            pass
+        _drop_traced(reg, sd)
         warnings.warn("levelsetpy_amd: the kernel traced from %r disagrees with the callbacks on this data (max |diff| %.3g of %.3g, %.2g %% of the "
-                      "nodes, stepBound %.17g / %.17g): the split path is used" % (getattr(sd.hamFunc, "__qualname__", sd.hamFunc), worst, scale,
-                                                                                 100 * frac, sb_f, sb_s))
+                      "nodes, stepBound %.17g / %.17g): the split path is used" % (name, worst, scale, 100 * frac, sb_f, sb_s))
         return None
-    reg.verified = True
+    done = getattr(reg, "verified_dtypes", None)
+    if done is None:
+        done = reg.verified_dtypes = set()
+    done.add(array_dtype_name(y))
     return plan
+
+
+def _drop_traced(reg, sd):
+    _trace.mark_bad(reg)
+    try:
+        del _PLAN_CACHE[sd]
+    except (KeyError, TypeError):
+        pass
 
 
 def _fused_term(plan, t, y, restrict_sign):

@@ -22,8 +22,9 @@ The traced kernel is not trusted blindly: the first time a plan built from it me
 evaluated by BOTH paths on that data and the fused result must agree with the callbacks' to rounding, else the trace is dropped
 with a warning.  A cached plan re-traces (0.2 ms of Python) when it is looked up again: parameters changed in place are
 picked up like system.native() does for the built-in systems, a changed expression is a new registration.  (Every lookup first
-compares a fingerprint of the scalar state the callbacks can see -- attributes of the objects they are bound to, of the schemeData,
-closure cells, module globals they name -- and re-traces only when it has changed; HJ_TRACE_RECHECK=1 re-traces always.)
+compares a fingerprint of the state the callbacks can see -- attributes, __slots__, dicts and lists of the objects they are bound to, of the
+schemeData, closure cells, partial arguments, module globals they name -- and re-checks the arrays and tensors the trace consumed
+(_Consumed); it re-traces only when one has changed; HJ_TRACE_RECHECK=1 re-traces always.)
 
     HJ_TRACE=0 switches the tracer off; HJ_TRACE_VERBOSE=1 says why a schemeData was not traced.
 """
@@ -598,6 +599,8 @@ class _Tracer(object):
         self.coord_hits = {}
         self.tables = []          # (axis, values): real arrays among the operands that vary along one axis
         self.table_index = {}
+        self.consumed = {}        # id -> the real arrays / tensors combined with the symbolic arguments (_Consumed)
+        self.derived = False      # a NumPy scalar was among the operands: a value computed from an array, maybe a stored one (_Consumed.hold)
 
     def _leaf(self, cls, op, d):
         s = cls(op, (), "num", len(self.order), d)
@@ -645,15 +648,19 @@ class _Tracer(object):
     def lift(self, v):
         if isinstance(v, Sym):
             return v
+        if isinstance(v, np.generic):
+            self.derived = True
         if isinstance(v, (bool, np.bool_, int, np.integer)):
             return self.const(int(v))
         if isinstance(v, (float, np.floating)):
             return self.param(v)
         if isinstance(v, np.ndarray):
+            self._consume(v)
             if v.size == 1:
                 return self.param(float(v.reshape(-1)[0])) if v.dtype.kind == "f" else self.const(int(v.reshape(-1)[0]))
             return self._coordinate(v, np.asarray(v))
         if _is_tensor(v):
+            self._consume(v)
             if v.numel() == 1:
                 return self.param(float(v.reshape(-1)[0].item())) if v.dtype.is_floating_point else self.const(int(v.reshape(-1)[0].item()))
             return self._coordinate(v, None)
@@ -668,32 +675,40 @@ class _Tracer(object):
         except Exception:
             raise TraceError("an operand of type %s cannot be traced" % type(v).__name__)
 
+    def _consume(self, v):
+        """A real array or tensor the callbacks combined with the symbolic arguments: its values are now part of the expression (a parameter, a
+        table, a coordinate), so a cached plan must see it change (_Consumed)."""
+        if id(v) not in self.consumed:
+            self.consumed[id(v)] = v
+
     def _coordinate(self, v, host):
         """A real array among the operands: fine if it IS a grid coordinate (grid.xs[d] read before the trace, a cached device copy)."""
         hit = self.coord_hits.get(id(v))
         if hit is not None and hit[0] is v:
             return hit[1][1] if isinstance(hit[1], tuple) else self.x[hit[1]]
         shape = tuple(int(s) for s in v.shape)
-        full = shape == self.shape
-        cand = []
-        for d in range(self.dim):
-            one = tuple(self.shape[k] if k == d else 1 for k in range(self.dim))
-            if full or shape == one or (len(shape) == 1 and shape[0] == self.shape[d]) or (shape == (self.shape[d], 1)):
-                cand.append(d)
+        # the axes NumPy / torch broadcasting gives the operand: its shape aligned to the RIGHT of the grid's ((n,) is the last axis, (n, 1) the
+        # second to last); a shape that does not broadcast against the grid's is refused, never matched to an axis by its length
+        lead = len(shape) - self.dim
+        if lead > 0 and any(s != 1 for s in shape[:lead]):
+            raise TraceError("an array of shape %s has more axes than the %d-D grid" % (shape, self.dim))
+        bshape = (1,) * max(0, -lead) + shape[max(0, lead):]
+        if any(b not in (1, n) for b, n in zip(bshape, self.shape)):
+            raise TraceError("an array of shape %s does not broadcast against the grid's shape %s" % (shape, self.shape))
+        cand = [d for d in range(self.dim) if bshape[d] != 1]
+        a = host.reshape(bshape) if host is not None else v.reshape(bshape)
         for d in cand:
             ref = self.real_vs[d]
-            bshape = tuple(self.shape[k] if k == d else 1 for k in range(self.dim))
+            one = tuple(self.shape[k] if k == d else 1 for k in range(self.dim))
             if host is not None:
-                a = host.reshape(bshape) if host.size == ref.size else host
                 # (compared in the ARRAY's floating type -- fp32 copies of the coordinates match -- but never in an integer or boolean one)
                 ct = a.dtype if a.dtype.kind == "f" else np.float64
-                ok = a.shape[d] == ref.size and bool(np.all(a.astype(ct, copy=False) == ref.reshape(bshape).astype(ct, copy=False)))
+                ok = bool(np.all(a.astype(ct, copy=False) == ref.reshape(one).astype(ct, copy=False)))
             else:
                 import torch
                 ct = v.dtype if v.dtype.is_floating_point else torch.float64
-                r = torch.as_tensor(ref, device=v.device, dtype=ct).reshape(bshape)
-                a = (v.reshape(bshape) if v.numel() == ref.size else v).to(ct)
-                ok = a.shape[d] == ref.size and bool((a == r).all().item())
+                r = torch.as_tensor(ref, device=v.device, dtype=ct).reshape(one)
+                ok = bool((a.to(ct) == r).all().item())
             if ok:
                 self.coord_hits[id(v)] = (v, d)
                 return self.x[d]
@@ -707,18 +722,14 @@ class _Tracer(object):
         # an array that varies along ONE grid axis (a cos(xs[2]) stored before the call, a per-heading gain): a table over that axis, looked
         # up by the node's coordinate
         for d in cand:
-            bshape = tuple(self.shape[k] if k == d else 1 for k in range(self.dim))
             first = tuple(slice(None) if k == d else slice(0, 1) for k in range(self.dim))
+            line = a[first]
             if host is not None:
-                a = host.reshape(bshape) if host.size == self.shape[d] else host
-                line = a[first]
                 ok = bool(np.all((a == line) | ((a != a) & (line != line))))
-                vals = np.asarray(line, dtype=np.float64).ravel()
+                vals = np.array(line, dtype=np.float64).ravel()          # (a copy: a view would keep the operand alive)
             else:
-                a = v.reshape(bshape) if v.numel() == self.shape[d] else v
-                line = a[first]
                 ok = bool(((a == line) | ((a != a) & (line != line))).all().item())
-                vals = line.detach().double().cpu().numpy().ravel()
+                vals = line.detach().double().cpu().numpy().copy().ravel()
             if ok and vals.size == self.shape[d] and vals.size <= self.MAX_TAB_LEN and bool(np.all(np.isfinite(vals))):
                 key = (d, vals.tobytes())
                 k = self.table_index.get(key)
@@ -734,6 +745,78 @@ class _Tracer(object):
         raise TraceError("an array of shape %s that is neither a grid coordinate, nor constant, nor a function of ONE grid axis was combined with the "
                          "symbolic arguments (values computed from several coordinates BEFORE the call cannot be traced: compute them inside "
                          "the callback)" % (shape,))
+
+
+class _Consumed(object):
+    """The real arrays and tensors a trace consumed (_Tracer._consume) that outlive it -- stored tables, filled arrays, tensors a system keeps --
+    and how to tell that one has changed since: a tensor by (data_ptr, _version) (views share the version counter of their base), a NumPy array
+    by an exact compare with a copy.  Temporaries the callbacks made and dropped (np.ones(shape) * c, np.abs(self.table)) are not kept; such a
+    temporary (or a NumPy scalar among the operands) may have been computed from a stored NumPy array, which the fingerprint sees by identity
+    only when it is large: .derived is then set, and the trace hands every such array of the state the callbacks can see to hold().  The grid's
+    own xs / vs are exempt.  NumPy arrays too large to compare on every lookup are refused."""
+    MAX_CHECKED = 1 << 16
+
+    def __init__(self, objs, exempt, derived=False):
+        import weakref
+        pending = []
+        for v in objs:
+            root = v
+            if isinstance(v, np.ndarray):
+                while isinstance(root.base, np.ndarray):
+                    root = root.base
+            else:
+                while getattr(root, "_base", None) is not None:
+                    root = root._base
+            if id(v) in exempt or id(root) in exempt:
+                continue
+            try:
+                pending.append((weakref.ref(v), weakref.ref(root), isinstance(v, np.ndarray)))
+            except TypeError:           # (no weak reference: keep it, compared like a live one)
+                pending.append(((lambda o: (lambda: o))(v), (lambda o: (lambda: o))(root), isinstance(v, np.ndarray)))
+        del objs[:]
+        v = root = None
+        self.items = []
+        self.derived = derived
+        for ref, rref, host in pending:
+            obj = ref()
+            if obj is None:
+                obj, ref = rref(), rref          # a temporary view of a stored array: the stored array is what can change
+            if obj is None:
+                self.derived = True              # a temporary made from something: maybe a stored array
+                continue
+            if host:
+                if obj.size > self.MAX_CHECKED:
+                    raise TraceError("the callbacks read a stored NumPy array of %d elements: too large to re-check on every call (keep it as a torch "
+                                     "tensor -- in-place changes are seen by its version counter -- or compute it inside the callbacks)" % obj.size)
+                self.items.append((ref, True, obj.copy()))
+            else:
+                self.items.append((ref, False, (obj.data_ptr(), obj._version)))
+
+    def hold(self, arrays):
+        """(path, array) pairs of large stored NumPy arrays the callbacks may have computed a temporary from: compared exactly at every lookup,
+        or refused when there is too much of them to compare."""
+        import weakref
+        have = set(id(r()) for r, host, _ in self.items if host)
+        new = [(k, a) for k, a in arrays if id(a) not in have]
+        if sum(a.size for _, a in new) > self.MAX_CHECKED:
+            raise TraceError("the callbacks computed with a value made from an array (a NumPy temporary or scalar), and the state they can see holds "
+                             "NumPy arrays (%s) of %d elements in all that such a value may come from: too large to re-check on every call (keep them "
+                             "as torch tensors -- in-place changes are seen by their version counters -- or compute the values inside the callbacks)"
+                             % (", ".join(_path(k) for k, _ in new[:4]), sum(a.size for _, a in new)))
+        for _, a in new:
+            self.items.append((weakref.ref(a), True, a.copy()))
+
+    def fresh(self):
+        for ref, host, was in self.items:
+            obj = ref()
+            if obj is None:
+                return False
+            if host:
+                if obj.shape != was.shape or obj.dtype != was.dtype or not np.array_equal(obj, was, equal_nan=obj.dtype.kind in "fc"):
+                    return False
+            elif (obj.data_ptr(), obj._version) != was:
+                return False
+        return True
 
 
 # ---------------------------------------------------------------------------------------------- the result of a trace
@@ -1189,7 +1272,22 @@ def _trace_once(grid, hamFunc, partialFunc, schemeData=None, owners=None):
             for k in [k for k, v in grid.__dict__.items() if isinstance(v, Sym) or (isinstance(v, (list, tuple)) and any(isinstance(e, Sym) for e in v))]:
                 del grid.__dict__[k]          # (anything symbolic a callback parked on the grid)
             grid.__dict__.update(hidden)
-        return Traced(tr, H, alpha)
+        traced = Traced(tr, H, alpha)
+        # (the callbacks have returned: of what they consumed, only what something else still holds can change before the next call)
+        exempt = set(id(a) for v in saved.values() for a in v)
+        tr.coord_hits.clear()
+        objs = list(tr.consumed.values())
+        tr.consumed.clear()
+        res = H = alpha = a = None
+        traced.state = _Consumed(objs, exempt, tr.derived)
+        # the state the callbacks can see, walked once now: where the fingerprint's bounds stop it (reported), and the large NumPy arrays it
+        # sees by identity only -- re-checked by value if a temporary may have been made from one of them
+        w = _Walk(collect=True)
+        _walk_state((owners or (hamFunc, partialFunc))[0], (owners or (hamFunc, partialFunc))[1], schemeData, w)
+        traced.unchecked = w.unseen
+        if traced.state.derived:
+            traced.state.hold([(k, v) for k, v in w.big if id(v) not in exempt])
+        return traced
     except TraceError:
         raise
     except RecursionError:
@@ -1205,6 +1303,7 @@ def _trace_once(grid, hamFunc, partialFunc, schemeData=None, owners=None):
 _REG_BY_SOURCE = {}          # (dim, source, column source, uses_range, nparams) -> NativeRegistration
 _BAD_SOURCES = set()         # failed the check against the callbacks (term.verify_traced)
 _WHY_NOT = {}                # id(hamFunc.__func__ or hamFunc) -> reason, reported once (HJ_TRACE_VERBOSE)
+_UNCHECKED = {}              # id(hamFunc.__func__ or hamFunc) -> state beyond the fingerprint's bounds, reported once (HJ_TRACE_VERBOSE)
 
 
 def enabled():
@@ -1217,90 +1316,179 @@ def _scalarish(v):
     return False
 
 
-def _fingerprint_of(obj, depth, seen, out):
-    d = getattr(obj, "__dict__", None)
-    if d is None or id(obj) in seen or len(seen) > 64:
-        return
-    seen.add(id(obj))
-    for k, v in d.items():
-        if _scalarish(v):
-            out.append((k, v))
-        elif isinstance(v, (list, tuple)) and len(v) <= 16 and all(_scalarish(e) for e in v):
+_FP_SEQ = 1024           # a list / tuple of up to this many numbers is part of the fingerprint by value
+_FP_ITEMS = 256          # dicts, and lists of other things, of up to this many entries are walked
+_FP_ARRAY = 8192         # NumPy arrays up to this size by value, larger ones by identity (what a trace consumed is re-checked by _Consumed)
+_SLOTS = {}              # type -> the names of its __slots__, base classes included
+
+
+def _slots_of(cls):
+    names = _SLOTS.get(cls)
+    if names is None:
+        names = []
+        for c in cls.__mro__:
+            sl = c.__dict__.get("__slots__", ())
+            for n in ((sl,) if isinstance(sl, str) else sl):
+                if n not in ("__dict__", "__weakref__") and n not in names:
+                    names.append(n)
+        names = _SLOTS[cls] = tuple(names)
+    return names
+
+
+class _Walk(object):
+    """One walk over the state the callbacks can see: .out the fingerprint; with collect=True (at trace time, not per lookup) also .big, the
+    NumPy arrays the fingerprint holds by identity only, and .unseen, where a bound stopped the walk."""
+    __slots__ = ("out", "seen", "big", "unseen")
+
+    def __init__(self, collect=False):
+        self.out, self.seen = [], set()
+        self.big = [] if collect else None
+        self.unseen = [] if collect else None
+
+    def skip(self, k, why):
+        if self.unseen is not None:
+            self.unseen.append("%s (%s)" % (_path(k), why))
+
+
+def _path(k):
+    if isinstance(k, tuple):
+        return "".join(_path(e) if i == 0 else "[%r]" % (e,) for i, e in enumerate(k))
+    return str(k)
+
+
+def _fp_value(k, v, depth, w):
+    """One holder of state: numbers by value, arrays by value (small) or identity, tensors by (data_ptr, _version); dicts, lists and objects
+    (attributes and __slots__) are walked `depth` levels down, each within a bound."""
+    out, seen = w.out, w.seen
+    if _scalarish(v):
+        out.append((k, v))
+    elif isinstance(v, np.ndarray):
+        if v.size <= _FP_ARRAY:
+            out.append((k, hash(v.tobytes())))
+        else:
+            out.append((k, ("id", id(v), v.shape)))
+            if w.big is not None:
+                w.big.append((k, v))
+    elif _is_tensor(v):
+        out.append((k, (v.data_ptr(), getattr(v, "_version", 0), tuple(v.shape))))
+    elif isinstance(v, (list, tuple)):
+        if len(v) <= _FP_SEQ and all(_scalarish(e) for e in v):
             out.append((k, tuple(v)))
-        elif isinstance(v, np.ndarray) and v.size <= 8192:
-            out.append((k, hash(v.tobytes())))          # (stored per-axis tables: their values are part of the traced expression)
-        elif _is_tensor(v) and v.numel() <= 8192:
-            out.append((k, (v.data_ptr(), getattr(v, "_version", 0))))
-        elif depth > 0 and hasattr(v, "__dict__") and not callable(v) and k not in ("grid",) and not isinstance(v, (type, _ModuleType)):
-            _fingerprint_of(v, depth - 1, seen, out)          # (not into modules or classes an object keeps a reference to: `self.torch = torch`)
+        elif id(v) in seen:
+            pass
+        elif depth > 0 and len(v) <= _FP_ITEMS and len(seen) <= 64:
+            seen.add(id(v))
+            out.append((k, len(v)))
+            for i, e in enumerate(v):
+                _fp_value((k, i), e, depth - 1, w)
+        else:
+            w.skip(k, "a %s of %d entries" % (type(v).__name__, len(v)) if depth > 0 else "too deep")
+    elif isinstance(v, dict):
+        # (a nested dict of settings does not cost a level: the walk is bounded by the number of containers, 64)
+        if id(v) in seen:
+            pass
+        elif depth > 0 and len(v) <= _FP_ITEMS and len(seen) <= 64:
+            seen.add(id(v))
+            out.append((k, len(v)))
+            for kk, e in v.items():
+                _fp_value((k, kk), e, depth if isinstance(e, dict) else depth - 1, w)
+        else:
+            w.skip(k, "a dict of %d entries" % len(v) if depth > 0 else "too deep")
+    elif not callable(v) and not isinstance(v, (type, _ModuleType)):
+        if depth > 0:
+            _fingerprint_of(v, depth - 1, w, k)          # (not into modules or classes an object keeps a reference to: `self.torch = torch`)
+        else:
+            w.skip(k, "too deep")
 
 
-def fingerprint(sd):
-    """The scalar state the callbacks can be expected to read: attributes of the objects they are bound to (two levels), of the schemeData,
-    closure cells and module globals they name.  A cached traced plan is re-traced when this changes (or always: HJ_TRACE_RECHECK=1)."""
-    out, seen = [], set()
-    for f in (sd.hamFunc, sd.partialFunc):
+def _fingerprint_of(obj, depth, w, at=None):
+    if id(obj) in w.seen:
+        return
+    if len(w.seen) > 64:
+        w.skip(at if at is not None else type(obj).__name__, "more than 64 containers")
+        return
+    w.seen.add(id(obj))
+    d = getattr(obj, "__dict__", None)
+    if isinstance(d, dict):
+        for k, v in d.items():
+            if k != "grid":
+                _fp_value(k if at is None else (at, k), v, depth, w)
+    for k in _slots_of(type(obj)):
+        try:
+            v = getattr(obj, k)
+        except AttributeError:
+            continue
+        if k != "grid":
+            _fp_value(k if at is None else (at, k), v, depth, w)
+
+
+def _walk_state(hamFunc, partialFunc, sd, w):
+    for f in (hamFunc, partialFunc):
         while hasattr(f, "func") and hasattr(f, "args") and hasattr(f, "keywords"):          # functools.partial
-            out.append(("<partial>", tuple(a for a in f.args if _scalarish(a)), tuple(sorted((k, v) for k, v in (f.keywords or {}).items() if _scalarish(v)))))
-            for a in tuple(f.args) + tuple((f.keywords or {}).values()):
-                if not _scalarish(a):
-                    _fingerprint_of(a, 1, seen, out)
+            for i, a in enumerate(f.args):
+                _fp_value(("<partial>", i), a, 2, w)
+            for k, a in sorted((f.keywords or {}).items()):
+                _fp_value(("<partial>", k), a, 2, w)
             f = f.func
         owner = getattr(f, "__self__", None)
         if owner is not None:
-            _fingerprint_of(owner, 2, seen, out)
+            _fingerprint_of(owner, 2, w, "self")
         fn = getattr(f, "__func__", f)
-        for cell in getattr(fn, "__closure__", None) or ():
+        for cell, name in zip(getattr(fn, "__closure__", None) or (), getattr(getattr(fn, "__code__", None), "co_freevars", ())):
             try:
                 v = cell.cell_contents
             except ValueError:
                 continue
-            if _scalarish(v):
-                out.append(("<cell>", v))
-            elif isinstance(v, np.ndarray) and v.size <= 8192:
-                out.append(("<cell>", hash(v.tobytes())))             # (a per-axis table the closure captured)
-            elif _is_tensor(v) and v.numel() <= 8192:
-                out.append(("<cell>", (v.data_ptr(), getattr(v, "_version", 0))))
-            else:
-                _fingerprint_of(v, 1, seen, out)
+            _fp_value(("<cell>", name), v, 2, w)
         code, glb = getattr(fn, "__code__", None), getattr(fn, "__globals__", None)
         if code is not None and glb is not None:
             for name in code.co_names:
                 v = glb.get(name)
-                if v is not None and _scalarish(v):
-                    out.append((name, v))
-                elif isinstance(v, np.ndarray) and v.size <= 8192:
-                    out.append((name, hash(v.tobytes())))
-    _fingerprint_of(sd, 1, seen, out)
-    return tuple(out)
+                if v is not None and not callable(v) and not isinstance(v, _ModuleType):
+                    _fp_value(name, v, 1, w)
+    if sd is not None:
+        _fingerprint_of(sd, 1, w, "schemeData")
+
+
+def fingerprint(sd):
+    """The state the callbacks can be expected to read: attributes and __slots__ of the objects they are bound to (two levels), of the
+    schemeData, closure cells, functools.partial arguments and the module globals they name -- numbers, small arrays, tensors, and dicts / lists /
+    objects of those, each within a bound.  A cached traced plan is re-traced when this changes (or always: HJ_TRACE_RECHECK=1)."""
+    w = _Walk()
+    _walk_state(sd.hamFunc, sd.partialFunc, sd, w)
+    return tuple(w.out)
 
 
 class _TracedSystem(object):
-    """What a plan carries for a traced pair: .grid, and ._hj_native with the registration and the parameters as of NOW."""
+    """What a plan carries for a traced pair: .grid, and ._hj_native with the registration and the parameters as of NOW; .traced: the trace
+    the registration and the parameters come from."""
 
     def __init__(self, sd, reg, traced):
         self.grid = sd.grid
         self._sd = sd
         self._hj_native = self
         self.reg = reg
+        self.traced = traced
         self._key = _key_of(traced)
         self._params = list(traced.params)
         self._print = fingerprint(sd)
 
     def params(self, _obj=None):
         # parameters changed in place come out as new par[] values; a different EXPRESSION is a different kernel -- the cached plan is then
-        # dropped by term.native_plan (the ham id it compares changes).  Re-traced when the scalar state the callbacks can see has changed
-        # (fingerprint) or on every lookup (HJ_TRACE_RECHECK=1: state the fingerprint does not reach)
+        # dropped by term.native_plan (the ham id it compares changes).  Re-traced when the state the callbacks can see has changed
+        # (fingerprint), when an array or tensor the trace consumed has (_Consumed), or on every lookup (HJ_TRACE_RECHECK=1: state neither reaches)
         if os.environ.get("HJ_TRACE_RECHECK", "0") in ("0", ""):
             fp = fingerprint(self._sd)
-            if fp == self._print:
+            if fp == self._print and self.traced.state.fresh():
                 return list(self._params)
             self._print = fp
         try:
             tr = trace_callbacks(self.grid, self._sd.hamFunc, self._sd.partialFunc, self._sd)
-        except TraceError:
+        except TraceError as e:
+            _why_not(getattr(self._sd.hamFunc, "__func__", self._sd.hamFunc), e)
             self.reg = _NoReg
             return []
+        self.traced = tr
         if _key_of(tr) != self._key:
             reg = _registration(tr, getattr(self._sd.hamFunc, "__func__", self._sd.hamFunc), getattr(self._sd.hamFunc, "__self__", None))
             self.reg = reg if reg is not None else _NoReg
@@ -1364,6 +1552,12 @@ def mark_bad(reg):
         _REG_BY_SOURCE.pop(key, None)
 
 
+def _why_not(ident, e):
+    if os.environ.get("HJ_TRACE_VERBOSE") and _WHY_NOT.get(id(ident)) != str(e):
+        _WHY_NOT[id(ident)] = str(e)
+        warnings.warn("levelsetpy_amd: hamFunc / partialFunc stay on the split path: %s" % e)
+
+
 def traced_native(sd):
     """(system, ham_id, params) like dynamics.native_of for a schemeData whose callbacks could be traced, else None."""
     if not enabled():
@@ -1375,13 +1569,15 @@ def traced_native(sd):
         if reg is None:
             return None
     except TraceError as e:
-        if os.environ.get("HJ_TRACE_VERBOSE") and _WHY_NOT.get(id(ident)) != str(e):
-            _WHY_NOT[id(ident)] = str(e)
-            warnings.warn("levelsetpy_amd: hamFunc / partialFunc stay on the split path: %s" % e)
+        _why_not(ident, e)
         return None
     except ValueError as e:          # the library refused the registration
         if os.environ.get("HJ_TRACE_VERBOSE"):
             warnings.warn("levelsetpy_amd: traced callbacks were not registered: %s" % e)
         return None
+    if tr.unchecked and os.environ.get("HJ_TRACE_VERBOSE") and _UNCHECKED.get(id(ident)) != tr.unchecked:
+        _UNCHECKED[id(ident)] = tr.unchecked
+        warnings.warn("levelsetpy_amd: traced callbacks run fused, but a change to this state would not be seen (the fingerprint's bounds stop "
+                      "there): %s" % "; ".join(tr.unchecked[:8]))
     system = _TracedSystem(sd, reg, tr)
     return system, reg.ham_id, list(tr.params)
