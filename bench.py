@@ -3,7 +3,7 @@
 (odeCFL3 -> termLaxFriedrichs -> upwindFirstWENO5 -> artificialDissipationGLF -> ghost cells)
 on the Dubins-relative 3-D problem, fp64 (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one odeCFL3 time step = 3 RK substeps over the whole grid; inputs are resident in HBM
 before the timed region; a window of exactly K steps is timed between synchronisations, R times (--repeats,
@@ -11,7 +11,12 @@ default 51), and `value` is the MEDIAN window (inter-quartile range and min/max 
 clock spin-up the state is reset to the initial data, so the W warm-up and R x K timed steps compute the same
 thing in every run with the same arguments (--dump-outputs DIR writes what the last of them returned).
 
-N = 1 (default): BASELINE C2, the 201^3 grid.  The same run also times, each with its own spin-up and
+A plain run does only what its headline figure needs: it sets up, settles the clocks, warms up, times the windows,
+writes --dump-outputs and prints the line.  Everything else the benchmark measures or checks runs with --full only:
+the extra workloads under "also", the CPU baseline and the parity check against the NumPy oracle, the rocprofv3 and
+streaming-rate child passes (N = 1), the companion scaling point and the per-rank exchange / launch timings (N > 1).
+
+N = 1 (default): BASELINE C2, the 201^3 grid.  With --full the same run also times, each with its own spin-up and
 reported under "also" with its own roofline fraction: the intended WENO5 arithmetic at 201^3, the
 single-GPU 513^3 grid (C4's N = 1 point), C3 (double integrator 4096^2, ENO3; "C3 fast": the opt-in lean ENO arithmetic) and C5 (double
 pendulum 129^4 fp32, all axes periodic) -- C3 / C5 / 513^3 / WENO5 with their own PMC traffic passes --, the headline with the CFL reduction kept
@@ -27,9 +32,10 @@ grid).  Before it is timed, a decomposition has to reproduce the single-domain r
 it runs on ("slab_check_max_abs_diff").
 
 Prints ONE JSON line (rank 0).  Extra objects: "roofline" (algorithmic bytes / measured kernel time vs
-the 8 TB/s HBM peak; "traffic" = fabric bytes per launch from two rocprofv3 --pmc child passes of this very
-run, taken before the timed legs) and "cpu_baseline" (the NumPy oracle timed on this host's cores on a bounded sample
-of the same workload; N = 1 only).
+the 8 TB/s HBM peak; "traffic" = fabric bytes per launch, with --full from two rocprofv3 --pmc child passes of this
+very run, taken before the timed legs, otherwise from profiles/traffic.json if it was taken on these kernel sources)
+and, with --full, "cpu_baseline" (the NumPy oracle timed on the host's cores on a bounded sample of the same workload)
+and "parity" (N = 1 only).
 """
 import argparse
 import ctypes as C
@@ -51,6 +57,7 @@ HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8 TB/s spec
 BYTES_PER_SUBSTEP = {"float64": 64.0 / 3.0, "float32": 32.0 / 3.0}   # 8 words / RK3 step
 DUMP_MAX_CELLS = 1 << 20        # --dump-outputs: at most 8 MB of fp64 state
 REF_IMPORT = "reference import (BASELINE.md s2, build container, 1 core): 6.6e5 at 51^3, 3.7e5 at 101^3, 1.57e5 at 201^3"
+ALSO_DEFAULT = "WENO5,513,C3,C3 fast,C5,CFL,API,RTC,RANGE"     # the extra workloads of a --full run
 
 
 def parse():
@@ -70,16 +77,20 @@ def parse():
                          "periodic, ring of slabs (BASELINE configs[4]; --global-n = points per axis, default 129)")
     ap.add_argument("--scheme", default="WENO5_ASSHIPPED", choices=["WENO5", "WENO5_ASSHIPPED", "ENO3", "ENO2"],
                     help="WENO5_ASSHIPPED = what the reference's upwindFirstWENO5 computes (parity-pinned; "
-                         "headline); WENO5 = the intended nonlinear scheme (reported in 'also')")
+                         "headline); WENO5 = the intended nonlinear scheme (reported in 'also' by --full)")
     ap.add_argument("--dtype", default="float64", choices=["float64", "float32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the extra workloads reported under 'also'")
-    ap.add_argument("--also", default="WENO5,513,C3,C3 fast,C5,CFL,API,RTC,RANGE", help="comma list of the extra workloads to time (API = the 201^3 / "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the extra workloads under 'also', the CPU baseline and the "
+                         "parity check against the NumPy oracle, the rocprofv3 and streaming-rate child passes (N = 1), the companion "
+                         "scaling point and the per-rank exchange / launch timings (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the extra workloads reported under 'also'")
+    ap.add_argument("--also", default=None, help="with --full: comma list of the extra workloads to time (default %s; API = the 201^3 / "
                     "51^3 workloads through odeCFL3 / HJIPDE_solve, the reference's own call protocol; RTC = the same system as a "
                     "Hamiltonian compiled at run time with hipRTC, and as Python callbacks on the split path; RANGE = a Hamiltonian whose alpha depends "
-                    "on the costate range, fused in two launches per stage against the split path)")
+                    "on the costate range, fused in two launches per stage against the split path)" % ALSO_DEFAULT)
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run")
+                    help="with --full: do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps of the single-GPU leg, write what its last step returned as DIR/<name>.npy: y (the "
                          "state; a fixed seeded sample of %d cells when the grid is larger), t and dt" % DUMP_MAX_CELLS)
@@ -88,7 +99,12 @@ def parse():
                          "stepper and schedule, the launches of a substep, halo bytes per step, predicted ms/step -- WITHOUT touching a GPU")
     ap.add_argument("--single", default=None, help=argparse.SUPPRESS)     # child passes of live_traffic: the main leg times this `also` workload (C3, C5)
     ap.add_argument("--cpu-worker", default=None, help=argparse.SUPPRESS)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.also is not None and not a.full:
+        ap.error("--also picks the extra workloads of a --full run; a plain run times the headline only")
+    if a.also is None:
+        a.also = ALSO_DEFAULT
+    return a
 
 
 # ------------------------------------------------------------------------------------------ CPU baseline
@@ -1091,16 +1107,18 @@ def main():
         if rank == 0:
             print(error_json(a, world, "--dump-outputs writes the outputs of the single-GPU leg; this run is the slab leg"))
         sys.exit(2)
+    # the child processes of the single-GPU leg (CPU baseline, streaming rates, rocprofv3 passes) belong to --full runs only
+    full_single = a.full and rank == 0 and world == 1 and not slab_leg
     cpu = None
-    if rank == 0 and world == 1 and not slab_leg and not a.no_cpu_baseline:
+    if full_single and not a.no_cpu_baseline:
         cpu = CpuBaseline(a.scheme, a.n)     # before the GPU is touched; idle until the GPU legs are done
     a.live, a.live_also = None, {}
     a.achievable = None
     # (quick runs -- --no-also -- and runs that are themselves being profiled skip the passes)
     profiled = any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if rank == 0 and world == 1 and not slab_leg and not a.no_also and not profiled:
+    if full_single and not a.no_also and not profiled:
         a.achievable = achievable_rates()    # a child process, before this one touches the GPU
-    if rank == 0 and world == 1 and not slab_leg and not a.no_live_traffic and not a.no_also and not profiled:
+    if full_single and not a.no_live_traffic and not a.no_also and not profiled:
         a.live = live_traffic(a)             # two rocprofv3 child passes, also before this process touches the GPU
         # the same for the digit entries of --also (513^3: the point where the arrays do not fit the Infinity Cache)
         a.live_also = {x: live_traffic(a, int(x)) for x in a.also.split(",") if x.isdigit()} if a.live else {}
@@ -1199,7 +1217,8 @@ def run(a, rank, world, local, slab_leg, cpu):
             dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", local))
         wname = a.workload or "C4"
         gn = (513 if wname == "C4" else 129) if a.global_n is None else a.global_n
-        res = hjdist.bench_slab(a, rank, world, global_n=gn, workload=wname)
+        # (the per-rank exchange-alone / launches-alone timings, also.time_of_a_step: --full runs only)
+        res = hjdist.bench_slab(a, rank, world, global_n=gn, workload=wname, diagnostics=a.full)
         if res.get("nranks") != world:
             raise RuntimeError("the slab transport spans %r ranks, --gpus says %d" % (res.get("nranks"), world))
         wl = res["workload"]
@@ -1251,8 +1270,8 @@ def run(a, rank, world, local, slab_leg, cpu):
         # The companion point of the scaling curve, same ranks, same communicator set-up: BASELINE's metric names 201^3 and
         # configs[3] names 513^3, so the strong-scaling line also carries the WEAK-scaling figure (a 201-plane slab of an
         # (N*201) x 201 x 201 grid per rank: per-GPU work fixed) and vice versa.  Any failure of this extra leg is reported in
-        # place of its number; it cannot take the main figure down (it runs after it) unless a rank hangs (watchdog).
-        if world > 1 and wname == "C4" and not a.no_also:
+        # place of its number; it cannot take the main figure down (it runs after it) unless a rank hangs (watchdog).  --full runs only.
+        if world > 1 and wname == "C4" and a.full and not a.no_also:
             a._partial = out          # from here on a stuck rank costs the companion figure only (watchdog in main())
             if hasattr(a, "_arm_companion"):
                 a._arm_companion()
@@ -1354,7 +1373,7 @@ def run(a, rank, world, local, slab_leg, cpu):
     if a.achievable:
         out["achievable_streaming_rates"] = a.achievable
     also = {}
-    if not a.no_also:
+    if a.full and not a.no_also:
         for name in [x for x in a.also.split(",") if x]:
             try:
                 if name == "CFL":

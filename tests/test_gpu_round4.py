@@ -658,16 +658,16 @@ def test_terms_through_the_tiled_kernel_equal_the_direct_kernel_bitwise(scheme, 
 
 
 def test_bench_line_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the keys the driver reads: metric / value / unit /
+    """`python bench.py --gpus 1 --steps K --warmup W --full` prints ONE JSON line with the keys the driver reads: metric / value / unit /
     n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config{workload} + roofline
     {bound, achieved, peak, unit, frac, traffic} + cpu_baseline{value, unit, cores, kind, sample} + parity (ok).  (The extra
-    workloads and the rocprofv3 child passes are switched off here: they are exercised by every default bench run.)"""
+    workloads and the rocprofv3 child passes are switched off here: they are exercised by every --full bench run.)"""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--repeats", "5",
-                        "--no-also", "--no-live-traffic"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--full", "--no-also", "--no-live-traffic"], capture_output=True, text=True, timeout=600, cwd=root)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -682,6 +682,30 @@ def test_bench_line_contract():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["unit"] == "cell-substeps/s" and c["value"] > 1e5 and c["sample"]
     assert d["parity"]["ok"] is True and d["parity"]["max_abs_diff"] <= d["parity"]["tol"] == 1e-11
+
+
+def test_bench_plain_run_times_the_headline_only():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` carries the headline keys with the same meaning as a --full run, and none of
+    what --full adds: no `also`, `cpu_baseline`, `parity` or streaming rates, and no roofline traffic from child passes of the run."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--repeats", "5"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("grid-cell RK-substep updates/sec, Dubins-3D HJI 201^3 fp64") and d["unit"] == "cell-substeps/s"
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["higher_is_better"], d["dtype"]) == (1, 5, 2, True, "f64")
+    assert d["value"] > 5e10 and abs(d["value"] - 8120601 * 3 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert d["repeats"]["n"] == 5 and 0.2 < d["roofline"]["frac"] < 1.0
+    for k in ("also", "cpu_baseline", "parity", "achievable_streaming_rates"):
+        assert k not in d, k
+    assert d["roofline"]["achievable"] is None
+    assert "child passes" not in (d["roofline"]["traffic_source"] or "")
+    assert d["summary"] == [d["summary"][0]] and d["summary"][0].startswith("headline 201^3")
 
 
 def test_bench_dump_outputs_repeat_and_follow_steps(tmp_path):

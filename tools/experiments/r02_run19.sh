@@ -9,7 +9,7 @@ for n in 201 251 301 401 513; do
 done
 for p in 0 1; do
 echo "== also HJ_PAIR=$p" >> $out/ab.txt
-HJ_PAIR=$p python bench.py --no-cpu-baseline --steps 20 --also WENO5,ENO3,ENO2,C3 >> $out/ab.txt 2>> $out/ab.err
+HJ_PAIR=$p python bench.py --full --no-cpu-baseline --steps 20 --also WENO5,ENO3,ENO2,C3 >> $out/ab.txt 2>> $out/ab.err
 done
 python - <<'PY'
 import json

@@ -3,7 +3,7 @@
 out=gpurun_out/r02ag; mkdir -p $out; rm -f $out/*
 for ring in 0 1 0 1; do
 echo "== ring=$ring" >> $out/ab.txt
-HJ_PAIR_RING=$ring python bench.py --no-cpu-baseline --no-live-traffic --steps 20 --also WENO5,ENO3,ENO2,C3,151,251 >> $out/ab.txt 2>> $out/ab.err
+HJ_PAIR_RING=$ring python bench.py --full --no-cpu-baseline --no-live-traffic --steps 20 --also WENO5,ENO3,ENO2,C3,151,251 >> $out/ab.txt 2>> $out/ab.err
 done
 python - <<'PY'
 import json

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 3, run 13: the driver's bench command + the profile round (kernel-trace stats, PMC passes at 201^3 / 513^3)
 out=gpurun_out/r03m; mkdir -p $out; rm -f $out/*
-timeout -k 10 900 python bench.py --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench.err; echo "bench rc=$?"
+timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 > $out/bench_default.json 2> $out/bench.err; echo "bench rc=$?"
 bash tools/profile_round.sh r03prof > $out/profile_round.txt 2>&1; tail -50 $out/profile_round.txt
 # VALU operations per cell of the intended WENO5 substep kernel (roofline_valu): SQ_INSTS_VALU x 64 / cells
 cd /tmp; export TMPDIR=/tmp

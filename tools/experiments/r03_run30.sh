@@ -3,7 +3,7 @@
 # (threads, pairs per thread, halo slots per thread), with and without the LDS halo ring; tune build libhj_vC5P.so
 out=gpurun_out/r03ad; mkdir -p $out; rm -rf $out/*
 export HJ_LIB=$PWD/levelsetpy_amd/csrc/libhj_vC5P.so
-run() { echo "== $*" >> $out/ab.txt; env "$@" HJ_DEBUG=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-live-traffic --n 101 --steps 8 --repeats 2 --also C5 >> $out/ab.txt 2> $out/last.err; grep -E "pair|tiling|E=\(" $out/last.err | sort | uniq -c | sort -rn | head -4 >> $out/ab.txt; tail -2 $out/last.err >> $out/ab.txt; }
+run() { echo "== $*" >> $out/ab.txt; env "$@" HJ_DEBUG=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-live-traffic --n 101 --steps 8 --repeats 2 --also C5 >> $out/ab.txt 2> $out/last.err; grep -E "pair|tiling|E=\(" $out/last.err | sort | uniq -c | sort -rn | head -4 >> $out/ab.txt; tail -2 $out/last.err >> $out/ab.txt; }
 run HJ_PAIR=1
 run HJ_PAIR_NT=512 HJ_PAIR_R=1 HJ_PAIR_KH=5
 run HJ_PAIR_NT=512 HJ_PAIR_R=1 HJ_PAIR_KH=5 HJ_PAIR_RING=1

@@ -2,7 +2,7 @@
 # round 3, run 31: C5 (129^4 fp32): more cells per thread / smaller workgroups, both tiled kernels (tune build libhj_vC5Q.so)
 out=gpurun_out/r03ae; mkdir -p $out; rm -rf $out/*
 export HJ_LIB=$PWD/levelsetpy_amd/csrc/libhj_vC5Q.so
-run() { echo "== $*" >> $out/ab.txt; env "$@" HJ_DEBUG=1 HJ_AUTOTUNE=0 timeout -k 10 300 python bench.py --no-cpu-baseline --no-live-traffic --n 101 --steps 8 --repeats 2 --also C5 >> $out/ab.txt 2> $out/last.err; grep -E "tiling" $out/last.err | sort | uniq -c | sort -rn | head -2 >> $out/ab.txt; tail -1 $out/last.err >> $out/ab.txt; }
+run() { echo "== $*" >> $out/ab.txt; env "$@" HJ_DEBUG=1 HJ_AUTOTUNE=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-live-traffic --n 101 --steps 8 --repeats 2 --also C5 >> $out/ab.txt 2> $out/last.err; grep -E "tiling" $out/last.err | sort | uniq -c | sort -rn | head -2 >> $out/ab.txt; tail -1 $out/last.err >> $out/ab.txt; }
 run HJ_PAIR=1
 run HJ_NT=512 HJ_R=2 HJ_KH=4 HJ_OCC=2 HJ_PD=2
 run HJ_NT=512 HJ_R=4 HJ_KH=7 HJ_OCC=2 HJ_PD=2

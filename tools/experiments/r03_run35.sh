@@ -3,7 +3,7 @@
 out=gpurun_out/r03ai; mkdir -p $out; rm -rf $out/*
 for add in 0 2 4 6 8 10 12 14 16 18 20 22 24 26 28 30 32; do
   echo "== HJ_LDS_PITCH_ADD=$add" >> $out/ab.txt
-  HJ_LDS_PITCH_ADD=$add HJ_DEBUG=1 HJ_AUTOTUNE=0 timeout -k 10 300 python bench.py --no-cpu-baseline --no-live-traffic --n 101 --steps 10 --repeats 3 --also C5 >> $out/ab.txt 2> $out/last.err || exit 1
+  HJ_LDS_PITCH_ADD=$add HJ_DEBUG=1 HJ_AUTOTUNE=0 timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-live-traffic --n 101 --steps 10 --repeats 3 --also C5 >> $out/ab.txt 2> $out/last.err || exit 1
   grep -E "pair tiling" $out/last.err | sort | uniq -c | sort -rn | head -1 >> $out/ab.txt
 done
 python - <<'PY'

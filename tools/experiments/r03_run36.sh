@@ -2,7 +2,7 @@
 # round 3, run 36: launches of hj_rk_step no longer reduce a CFL bound nobody reads (dt comes from the static bound): A/B against
 # HJ_KEEP_BOUNDS=1 (every launch ends in wave_max -> LDS -> 3 atomicMax per workgroup on one cache line), tiled and direct kernels
 out=gpurun_out/r03aj; mkdir -p $out; rm -rf $out/*
-run() { echo "== $* $EXTRA" >> $out/ab.txt; env "$@" timeout -k 10 400 python bench.py --no-cpu-baseline --no-live-traffic --steps 50 --repeats 5 $EXTRA >> $out/ab.txt 2> $out/last.err || { tail -3 $out/last.err; exit 1; }; }
+run() { echo "== $* $EXTRA" >> $out/ab.txt; env "$@" timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-live-traffic --steps 50 --repeats 5 $EXTRA >> $out/ab.txt 2> $out/last.err || { tail -3 $out/last.err; exit 1; }; }
 for n in 31 51 101 151 201; do
   for kb in 1 0; do
     EXTRA="--n $n --no-also" run HJ_KEEP_BOUNDS=$kb

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 3, run 55: pendulum drift with ONE division (product) against two (tune build -DHJ_PENDULUM_TWO_DIV): C5; the 4-D tests
 out=gpurun_out/r03bc; mkdir -p $out; rm -rf $out/*
-run() { echo "== $*" >> $out/ab.txt; env "$@" timeout -k 10 400 python bench.py --no-cpu-baseline --no-live-traffic --n 101 --steps 30 --repeats 5 --also C5 >> $out/ab.txt 2> $out/last.err || { tail -3 $out/last.err; exit 1; }; }
+run() { echo "== $*" >> $out/ab.txt; env "$@" timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-live-traffic --n 101 --steps 30 --repeats 5 --also C5 >> $out/ab.txt 2> $out/last.err || { tail -3 $out/last.err; exit 1; }; }
 run HJ_LIB=$PWD/levelsetpy_amd/csrc/libhj_vDIV2.so
 run HJ_X=0
 run HJ_LIB=$PWD/levelsetpy_amd/csrc/libhj_vDIV2.so

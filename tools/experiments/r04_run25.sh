@@ -5,7 +5,7 @@ out=gpurun_out/r04_run25; mkdir -p $out; : > $out/ab.txt
 D=$PWD/levelsetpy_amd/csrc
 for rep in 1 2 3; do for v in libhj_vOLDENO.so libhj_mi355x.so; do
   echo "== $v pass $rep" >> $out/ab.txt
-  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-live-traffic --also C3,ENO3,ENO2 --repeats 15 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err >> $out/ab.txt
+  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-live-traffic --also C3,ENO3,ENO2 --repeats 15 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err >> $out/ab.txt
   python3 - $out/b.json >> $out/ab.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

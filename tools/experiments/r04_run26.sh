@@ -8,7 +8,7 @@ for v in libhj_vS_max-ilp.so libhj_vS_max-memory-clause.so; do
 done
 for rep in 1 2; do for v in libhj_mi355x.so libhj_vS_max-ilp.so libhj_vS_max-memory-clause.so; do
   echo "== $v pass $rep" >> $out/ab.txt
-  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-live-traffic --also WENO5,513,C3,C5 --repeats 15 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err >> $out/ab.txt
+  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-live-traffic --also WENO5,513,C3,C5 --repeats 15 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err >> $out/ab.txt
   python3 - $out/b.json >> $out/ab.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

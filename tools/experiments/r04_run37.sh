@@ -4,7 +4,7 @@
 out=gpurun_out/r04_run37; mkdir -p $out; : > $out/ab.txt
 D=$PWD/levelsetpy_amd/csrc
 for rep in 1 2 3; do for v in libhj_vPREV.so libhj_mi355x.so; do
-  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-live-traffic --also C3 --repeats 11 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err
+  HJ_LIB=$D/$v timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-live-traffic --also C3 --repeats 11 --steps 20 > $out/b.json 2> $out/b.err || tail -3 $out/b.err
   python3 - $out/b.json $v $rep >> $out/ab.txt <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

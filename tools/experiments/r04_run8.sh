@@ -3,7 +3,7 @@
 # plain order of rounds 1-3), timing + FETCH_SIZE / WRITE_SIZE of the substep kernel
 out=gpurun_out/r04_run8; mkdir -p $out; rm -rf $out/*
 timeout -k 10 200 python -m pytest tests/test_gpu_configs.py -x -q -m gpu -k "c5 or 4d or pendulum" > $out/pytest_4d.log 2>&1; echo "pytest 4-D rc=$?"; tail -2 $out/pytest_4d.log
-run() { echo "== HJ_TB1=$1 HJ_TB2=$2" >> $out/ab.txt; HJ_DEBUG=1 HJ_TB1=$1 HJ_TB2=$2 timeout -k 10 200 python bench.py --no-cpu-baseline --no-live-traffic --also C5 --steps 8 --warmup 2 --repeats 3 >> $out/ab.txt 2> $out/last.err || tail -3 $out/last.err >> $out/ab.txt; grep -h "tiling" $out/last.err | tail -1 >> $out/ab.txt; }
+run() { echo "== HJ_TB1=$1 HJ_TB2=$2" >> $out/ab.txt; HJ_DEBUG=1 HJ_TB1=$1 HJ_TB2=$2 timeout -k 10 200 python bench.py --full --no-cpu-baseline --no-live-traffic --also C5 --steps 8 --warmup 2 --repeats 3 >> $out/ab.txt 2> $out/last.err || tail -3 $out/last.err >> $out/ab.txt; grep -h "tiling" $out/last.err | tail -1 >> $out/ab.txt; }
 for tb in "0 0" "4 4" "8 8" "4 8" "8 4" "2 8" "8 2" "3 6" "6 3" "2 2" "16 1" "1 16"; do run $tb; done
 python - <<'PY'
 import json
@@ -17,7 +17,7 @@ PY
 export TMPDIR=/tmp; root=$PWD; cd /tmp
 for tb in "0 0" "4 4"; do set -- $tb
 for ctr in FETCH_SIZE WRITE_SIZE; do
-  HJ_TB1=$1 HJ_TB2=$2 HJ_BENCH_SPINUP=3 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $root/$out/pmc_$1_$2_$ctr -- python3 $root/bench.py --no-cpu-baseline --no-live-traffic --also C5 --steps 2 --warmup 1 --repeats 1 > /dev/null 2> $root/$out/pmc.err
+  HJ_TB1=$1 HJ_TB2=$2 HJ_BENCH_SPINUP=3 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d $root/$out/pmc_$1_$2_$ctr -- python3 $root/bench.py --full --no-cpu-baseline --no-live-traffic --also C5 --steps 2 --warmup 1 --repeats 1 > /dev/null 2> $root/$out/pmc.err
 done; done
 cd $root
 python - <<'PY'

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage: tools/profile_round.sh <round-tag>      (on the GPU box; writes under gpurun_out/<tag>/)
-# 1. rocprofv3 --kernel-trace --stats of the default bench command (the driver's: --steps 20 --warmup 5)
+# 1. rocprofv3 --kernel-trace --stats of the --full bench command (--steps 20 --warmup 5: every leg)
 # 2. separate --pmc passes at 201^3 and 513^3: FETCH_SIZE, WRITE_SIZE (HBM traffic), SQ issue/wait and LDS counters
 # 1c/1d. a 513^3-only kernel-trace stats file; the static instruction mix of the built library (tools/isa_mix.py)
 # 3. profiles/traffic.json rows (with the hash of the kernel sources they were measured on) printed at the end
@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic > $out/stats_bench.json 2> $out/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -- python3 $root/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-live-traffic > $out/stats_bench.json 2> $out/stats.err
 # 1b. the headline workload alone (201^3, the default K/W): this stats file's average for the dominant kernel is the
-#     number bench.py's roofline.kernel_ms has to agree with (the default command above mixes 201^3 and 513^3 launches
+#     number bench.py's roofline.kernel_ms has to agree with (the --full command above mixes 201^3 and 513^3 launches
 #     of the same instantiation in one row)
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats201 -- python3 $root/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-also > $out/stats201_bench.json 2> $out/stats201.err
 find $out/stats201 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $out/kernel_stats_201.csv
