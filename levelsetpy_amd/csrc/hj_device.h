@@ -19,12 +19,6 @@
 
 namespace hj {
 
-// VERTICAL PAIRS (hj_fusedv.h): 1 = the two pair slots of a thread are vertically adjacent on 3-D grids (shared middle-axis rows); the tilings
-// (hj_api.hip, make_tiling) then give such launches an even row count.  Built and measured in round 6 (same bits, 12 -> 6 ds_read_b128 per
-// thread and plane on the middle axis) and left OFF: 3 % SLOWER at 201^3 and 513^3 in a same-run A/B (profiles/r06_stage1_bound.txt, appendix 3)
-#ifndef HJ_VPAIR
-#define HJ_VPAIR 0
-#endif
 template <typename T> struct Lim;
 template <> struct Lim<double> { static constexpr double tiny = 1e-99; static constexpr double lowest = -1.0e300; };
 template <> struct Lim<float>  { static constexpr float  tiny = 1e-30f; static constexpr float lowest = -3.0e38f; };
@@ -911,11 +905,7 @@ __device__ __forceinline__ unsigned long long max_key(double v) {
 // systems most workgroups carry the same maxima and now skip theirs (round 5: the kept CFL reduction cost 3-8 % of the 201^3 launch).
 __device__ __forceinline__ void key_max(unsigned long long* p, double v) {
     const unsigned long long k = max_key(v);
-#if defined(HJ_KEY_MAX_BLIND)        // A/B knob (tune builds): the round-4 form, an atomic whatever the key holds
-    atomicMax(p, k);
-#else
     if (k > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, k);
-#endif
 }
 
 // Wavefront max / min of a double, every lane receives the result.  DPP data moves (row_shr 1,2,4,8 inside the four

@@ -45,12 +45,7 @@
 // surplus) their LDS stores go out unpredicated -- a benign duplicate write instead of an exec save + branch per slot and
 // plane: C5 +3 % (tools/experiments/r03_run54.sh).  In 2-D / 3-D most slots of the last round are surplus (2-D: 506 of 512)
 // and whole waves would store to ONE LDS address, which the LDS serialises (C3 -9 %): there the predicate stays.
-// -DHJ_PRED_HALO (tuning builds): the predicate everywhere.
-#ifdef HJ_PRED_HALO
-#define HJ_SLOT_PRED(k) if (h_real[k])
-#else
 #define HJ_SLOT_PRED(k) if (ND < 4 ? h_real[k] : true)
-#endif
 namespace hj {
 
 // cache policies of the streams (tuning macros): y0 and the output are touched once
@@ -64,22 +59,9 @@ namespace hj {
 #define HJ_AUX_OWN 0
 #endif
 
-// LDS stencil read.  ds_read2_b64 moves 16 B/lane in 8 LDS cycles, two ds_read_b64 in 4
-// (MI355X_MICROARCH.md, LDS table), and the LDS pipe is the busiest unit of this kernel (PMC: 65 % at 513^3,
-// half of it counted as bank-conflict cycles).  The back end pairs any two LDS reads that share a base
-// register and differ by a constant offset, i.e. the six neighbours along the contiguous axis; passing each
-// address through an empty asm makes the bases opaque, so they stay single ds_read_b64 (one extra 32-bit
-// add per read).  Measured (round 2): the opaque offsets cost 12-18 VGPRs -- one wave per SIMD less at 201^3
-// (172 -> 184 VGPRs), scratch at 401^3+ -- and gain nothing; default 0 = let the compiler pair.
-#ifndef HJ_LDS_NO_READ2
-#define HJ_LDS_NO_READ2 0
-#endif
-template <typename T> __device__ __forceinline__ T lds_read(const T* buf, int o) {
-#if HJ_LDS_NO_READ2
-    if constexpr (sizeof(T) == 8) asm("" : "+v"(o));     // the 32-bit element offset, so that `buf` keeps its LDS address space
-#endif
-    return buf[o];
-}
+// LDS stencil read along the contiguous axis.  The back end pairs any two LDS reads that share a base register and differ by a
+// constant offset (ds_read2_b64) and is left to: keeping them single reads cost 12-18 VGPRs and gained nothing (round 2).
+template <typename T> __device__ __forceinline__ T lds_read(const T* buf, int o) { return buf[o]; }
 
 template <typename T, int ND> struct FusedArgs {
     const T* max_d1sq;            // ND values (HJ_WENO5 only)

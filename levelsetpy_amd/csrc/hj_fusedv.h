@@ -54,33 +54,17 @@ __device__ __forceinline__ Pair<float>::V buf_load2(__amdgpu_buffer_rsrc_t r, un
 // vmcnt accounting), followed by a nop statement that takes the data as an INPUT and clobbers memory: the clobber
 // keeps it after the store, the input keeps the data registers live (unwritable) up to the nop.
 // tools/check_store_hazard.py disassembles the built library and verifies the rule for every wide store
-// (tests/test_cabi.py runs it).  -DHJ_ST_ASM: store + wait states as ONE asm statement (2-3 % slower: the
-// compiler no longer counts the store in vmcnt; it also needs the leading s_nop 4, because the hazard recogniser
-// does not look inside asm and the SRD / soffset may just have been restored from a spill lane by v_readlane).
-// 1: the intended WENO5 shares the MIDDLE axis' smoothness values between lanes through LDS (WX below).  Built and measured in round 5 and
-// left OFF: the values are the same bits and 18 fp64 operations per cell go, but the instantiation was at 252 VGPRs -- what has to live
-// across the extra barrier spills (36-68 B of scratch) and the launch is 19 % SLOWER (201^3: 6.23 against 7.70e10; profiles/r05_weno5_eno_fast.txt)
-#ifndef HJ_WENO_LDS_SHARE
-#define HJ_WENO_LDS_SHARE 0
-#endif
-#ifndef HJ_ST_PRE
-#define HJ_ST_PRE 4
-#endif
+// (tests/test_cabi.py runs it).
 #ifndef HJ_ST_POST
 #define HJ_ST_POST 2
 #endif
 #define HJ_STR2(x) #x
 #define HJ_STR(x) HJ_STR2(x)
 __device__ __forceinline__ void buf_store2(Pair<double>::V v, __amdgpu_buffer_rsrc_t r, unsigned off, unsigned soff) {
-#if defined(HJ_ST_ASM)
-    asm volatile("s_nop " HJ_STR(HJ_ST_PRE) "\n\tbuffer_store_dwordx4 %0, %1, %2, %3 offen\n\ts_nop " HJ_STR(HJ_ST_POST)
-                 :: "v"(v), "v"(off), "s"(r), "s"(soff) : "memory");
-#else
     using W = decltype(__builtin_amdgcn_raw_buffer_load_b128(r, off, soff, 0));
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(W, v), r, off, soff, HJ_PAIR_AUX_OUT);
 #if !defined(HJ_ST_UNSAFE)      // HJ_ST_UNSAFE: tuning only (what the wait states cost); results can be wrong
     asm volatile("s_nop " HJ_STR(HJ_ST_POST) :: "v"(v) : "memory");
-#endif
 #endif
 }
 __device__ __forceinline__ void buf_store2(Pair<float>::V v, __amdgpu_buffer_rsrc_t r, unsigned off, unsigned soff) {
@@ -88,34 +72,15 @@ __device__ __forceinline__ void buf_store2(Pair<float>::V v, __amdgpu_buffer_rsr
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(W, v), r, off, soff, 0);
 }
 
-// round 4: every load of the setup is issued before the first wait (the rings of the first AH planes used to be requested and
-// waited for one after the other: two serialised memory round trips in front of the plane loop), and HJ_EARLY_ARGS batches
-// the kernel-argument loads (profiles/r04_headline_skeleton.txt)
-#ifndef HJ_EARLY_ARGS
-#define HJ_EARLY_ARGS 1
-#endif
-// TWO PLANES PER BARRIER (round 6 experiment): the two plane iterations of a loop pass stage their centre planes and halo rings first, meet at ONE
-// barrier, then compute both -- half the synchronisations of the per-plane chain barrier -> LDS reads -> arithmetic -> store (profiles/r06_stage1_bound.txt).
-// Needs 4 + halo_ahead LDS plane buffers instead of 2 + halo_ahead (the host side sizes them: hj_inst.hip).  Light stencils only (the intended
-// WENO5's epsilon producer reads the previous plane's outputs behind the plane's own barrier).
-#ifndef HJ_TWO_PLANES
+// What is left of two deleted experiments (two planes per barrier, round 6; the intended WENO5's middle-axis smoothness values shared through
+// LDS, round 5: DESIGN.md section 9): three unused declarations in fused_pair_kernel that read these constants.  They stay for now because
+// deleting them is NOT code-neutral: the six 2-D intended-WENO5 instantiations (256 threads, one pair per thread, fp32 and fp64) come out with
+// other register numbers -- same instruction counts and resource figures, same bits, fp64 within the noise and fp32 0.16 % FASTER in a
+// same-process A/B, which is outside the parent-against-parent spread a pure refactor may move by (profiles/refactor_pair_kernel.txt).
+// They go with the next change to this kernel that is measured anyway.
+#define HJ_WENO_LDS_SHARE 0
 #define HJ_TWO_PLANES 0
-#endif
-// VERTICAL PAIRS (round 6): on 3-D grids the TWO pair slots of a thread (R = 2) are the pairs of the same columns in two ADJACENT tile rows, not two
-// slots dealt half a tile apart.  The middle-axis stencils of the two then overlap in all but two rows, and each one's missing neighbour row is the
-// other's own pair (in registers): 6 ds_read_b128 per thread and plane for that axis instead of 12 -- the LDS stencil reads are what the stage-1
-// launch of the headline cannot hide (13.6 % at 513^3, 16 % at 201^3: profiles/r06_stage1_bound.txt).  Same cells, same arithmetic: same bits.
-// The host gives such launches an EVEN tile extent on axis 1 (make_tiling, hj_api.hip).
-// MEASURED SLOWER (-3 %, same-run A/B at 201^3 and 513^3) and compiled out: HJ_VPAIR defaults to 0 (hj_device.h).
-
 template <int K> struct IntTag { static constexpr int value = K; };
-constexpr bool defined_ablate2() {
-#if defined(HJ_ABLATE) && (HJ_ABLATE & 2)
-    return true;
-#else
-    return false;
-#endif
-}
 constexpr bool light_scheme_dev(int s) { return s == HJ_WENO5_ASSHIPPED || s == HJ_ENO2 || s == HJ_ENO2_FAST; }
 constexpr int HJ_VPAD = 4;      // left pad of an LDS row (cells): even, so that tile cell 0 of a row is 16-byte aligned
 
@@ -140,7 +105,6 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
     static_assert((NT / 64) * ND * 8 <= 512, "reduction scratch");
     const int xb = XP ? A.xbase : 0;            // index of tile axis 1 that byte offset 0 stands for
 
-#if HJ_EARLY_ARGS
     // Round 4: the setup below reads ~45 fields of the 700-byte kernel-argument block.  The compiler places each scalar load next to
     // its first use, so the prologue was a chain of 6-8 dependent s_load -> s_waitcnt round trips before the first
     // buffer_load went out (1.8 us after the workgroup started: profiles/r04_prologue.txt).  Naming the fields as inputs of
@@ -152,7 +116,6 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
                  "s"(A.nchunks_e));
     asm volatile("" ::"s"(y), "s"(y0), "s"(out), "s"(A.ham.coord[0]), "s"(A.ham.coord[1]), "s"(A.ham.coord[ND - 1]), "s"(A.ham.aux[0]),
                  "s"(A.ham.aux[1]), "s"(A.bc[1]), "s"(A.bc[ND - 1]), "s"(A.use_y0));
-#endif
     const int L = logical_block(A);
     if (L < 0) return;
     const T dt_launch = launch_dt<HAM>(A);
@@ -219,20 +182,11 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
     unsigned own_g[R];
     typename HAM::Cell hcell[R][2];
     typename HAM::Raw hraw[R][2];
-    constexpr bool VPAIR = HJ_VPAIR && ND == 3 && R == 2 && !HJ_WENO_LDS_SHARE && !defined_ablate2();
-    constexpr bool vp_on = VPAIR;                                         // (the host hands such launches an EVEN row count: make_tiling, hj_api.hip)
-    const int vp_hp = A.E[LA] >> 1, vp_half = (A.E[1] >> 1) * vp_hp;      // pairs of a tile row; threads that hold two real slots
-    const bool last_real = vp_on ? (tid < vp_half) : ((tid + (R - 1) * NT) < tile_slots);
+    const bool last_real = (tid + (R - 1) * NT) < tile_slots;
     unsigned nbv[R];              // bit d: the pair's forward neighbour on plane axis d lies inside the tile (eps_part pairs)
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         int c = 2 * min(tid + r * NT, tile_slots - 1);
-        if constexpr (vp_on) {    // slot r of thread t: row 2 * (t / hp) + r, pair t % hp  (surplus threads shadow the last thread that holds real slots)
-            const int tt = min(tid, vp_half - 1);
-            int rp, col;
-            fdivmod(tt, fdiv_make(vp_hp), rp, col);
-            c = 2 * ((2 * rp + r) * vp_hp + col);
-        }
         int lo = 0, g = 0;
         int idx[ND];
         idx[0] = 0;
@@ -500,12 +454,7 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
     // until the next iteration's barrier
     const bool eps_prod = SCHEME == HJ_WENO5 && A.eps_part != nullptr;
     T* const obuf = lds + A.lds_nbuf * lds_plane;
-    // ... and (HJ_WENO_LDS_SHARE=1 builds only: measured slower, see the macro) on 3-D grids the MIDDLE axis shares them too, between lanes: every cell writes its three left-biased values to
-    // an LDS plane each (behind the two planes of the epsilon producer), and after one more barrier takes the three of the cell ONE ROW UP as
-    // its own right-biased ones; the cells of a tile's last row form theirs as before.  18 fp64 operations per cell replaced by 3 + 3
-    // 16-byte LDS accesses per pair; the values are the same bits (weno5_cd_carry's identity, across lanes instead of across planes).
-    constexpr bool WX = WCARRY && ND == 3 && HJ_WENO_LDS_SHARE;
-    T* const qbuf = lds + (A.lds_nbuf + 2) * lds_plane;
+    constexpr bool WX = WCARRY && ND == 3 && HJ_WENO_LDS_SHARE;      // (unused: see HJ_WENO_LDS_SHARE)
     double dmax[ND];
     V oprev[R];
 #pragma unroll
@@ -683,19 +632,15 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
     unsigned long long st_acc[4] = {0, 0, 0, 0};
 #endif
     int ring_c = 0;                                            // LDS buffer of the plane the next iteration computes
-    constexpr bool TWOB = HJ_TWO_PLANES && light_scheme_dev(SCHEME) && !HJ_MAYDOWN && ND <= 3 && MODE != 3 && !ham_xp<HAM>::value;
-    int ring_of[2] = {0, 0};                                   // TWOB: the buffer each plane of the pass was staged in
-    // PH: 0 the whole plane iteration (staging, barrier, compute); 1 the staging only, 2 the compute only (TWOB: one barrier per PASS between them)
-    auto body = [&](auto off_tag, auto ph_tag, int m, V* own_c, V* own_n, T* hal_c, T* hin_c, V* halp_c, V* hinp_c, V* y0_c, typename HAM::Plane& pl_c) {
+    constexpr bool TWOB = HJ_TWO_PLANES && light_scheme_dev(SCHEME) && !HJ_MAYDOWN && ND <= 3 && MODE != 3 && !ham_xp<HAM>::value;      // (unused: see HJ_TWO_PLANES)
+    int ring_of[2] = {0, 0};                                   // (unused, likewise)
+    auto body = [&](auto off_tag, int m, V* own_c, V* own_n, T* hal_c, T* hin_c, V* halp_c, V* hinp_c, V* y0_c, typename HAM::Plane& pl_c) {
         constexpr int OFF = decltype(off_tag)::value;          // window [OFF, OFF + 7) of the queue is planes P(m - 3) .. P(m + 3)
-        constexpr int PH = decltype(ph_tag)::value;
         const int p = plane_at(m);                              // the plane this iteration computes
 #ifdef HJ_STAMP
         const unsigned long long st0 = __builtin_readcyclecounter();
 #endif
-        if constexpr (PH != 2) ring_of[OFF] = ring_c;
-        T* buf = lds + ring_of[OFF] * lds_plane;                // plane p
-      if constexpr (PH != 2) {
+        T* buf = lds + ring_c * lds_plane;                      // plane p
         int ring_h = ring_c + AH;
         if (ring_h >= NB) ring_h -= NB;
         T* bufh = lds + ring_h * lds_plane;                     // plane p + AH: where hal_c goes
@@ -704,20 +649,18 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
         // stage the centre plane: one 16-byte LDS store per pair
 #pragma unroll
         for (int r = 0; r < R; ++r)
-            if ((!vp_on && r < R - 1) || last_real) {
+            if (r < R - 1 || last_real) {
                 V c2;
                 c2.x = q[r][0][3 + OFF];
                 c2.y = q[r][1][3 + OFF];
                 *reinterpret_cast<V*>(buf + own_lds[r]) = c2;
             }
         park_halo(bufh, hal_c, hin_c, halp_c, hinp_c);
-      }
-      if constexpr (PH == 1) return;
 #ifdef HJ_STAMP
         const unsigned long long st1 = __builtin_readcyclecounter();
 #endif
 #ifndef HJ_ABLATE_NOSYNC        // timing experiment only (results are wrong without the barrier)
-        if constexpr (PH == 0) __syncthreads();
+        __syncthreads();
 #endif
 #ifdef HJ_STAMP
         const unsigned long long st2 = __builtin_readcyclecounter();
@@ -727,32 +670,10 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
         const unsigned so_out = (unsigned)(p - p_lo) * plane_bytes;
         const typename HAM::Plane pl_use = pl_c;
         pl_c = HAM::plane(A.ham, p2, A.sc);
-        // VPAIR: the middle-axis stencils of BOTH slots from six shared rows (the slots' rows are j1 and j1 + 1: rows j1 - 3 .. j1 - 1 and
-        // j1 + 2 .. j1 + 4 from LDS, each slot's missing neighbour row is the other's own pair) -- formed first, so that the rows do not stay live
-        T vpc[R][2], vhd[R][2];
-        if constexpr (vp_on) {
-            const T* base0 = buf + own_lds[0];
-            V vrow[6];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) vrow[k] = *reinterpret_cast<const V*>(base0 + (k < 3 ? k - 3 : k - 1) * ls[1]);
-            V own0, own1;
-            own0.x = q[0][0][3 + OFF]; own0.y = q[0][1][3 + OFF];
-            own1.x = q[1][0][3 + OFF]; own1.y = q[1][1][3 + OFF];
-            const V l0[7] = {vrow[0], vrow[1], vrow[2], own0, own1, vrow[3], vrow[4]};
-            const V l1[7] = {vrow[1], vrow[2], own0, own1, vrow[3], vrow[4], vrow[5]};
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                T va[7], vb[7];
-#pragma unroll
-                for (int j = 0; j < 7; ++j) { va[j] = r == 0 ? l0[j].x : l1[j].x; vb[j] = r == 0 ? l0[j].y : l1[j].y; }
-                sten(IntTag<1>(), va, vpc[r][0], vhd[r][0], last_real);
-                sten(IntTag<1>(), vb, vpc[r][1], vhd[r][1], last_real);
-            }
-        }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             T pc[2][ND], hd[2][ND];
-            const bool slot_real = (!vp_on && r < R - 1) || last_real;
+            const bool slot_real = r < R - 1 || last_real;
 #pragma unroll
             for (int c = 0; c < 2; ++c) {
                 if (down) {
@@ -771,10 +692,6 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
             // plane axes other than the contiguous one: the pair's neighbours are pairs (16-byte LDS reads)
 #pragma unroll
             for (int d = 1; d < LA; ++d) {
-                if constexpr (vp_on) {
-                    pc[0][1] = vpc[r][0]; hd[0][1] = vhd[r][0]; pc[1][1] = vpc[r][1]; hd[1][1] = vhd[r][1];
-                    continue;
-                }
                 T va[7], vb[7];
 #pragma unroll
                 for (int j = 0; j < 7; ++j) {
@@ -787,38 +704,7 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
                     vb[j] = n2.y;
 #endif
                 }
-                if constexpr (WX) {
-                    T lqa[3], lqb[3], rqa[3], rqb[3];
-                    WenoCand<T> ca, cb;
-                    {
-                        const WenoLine<T> la = weno5_line(va), lb = weno5_line(vb);
-                        weno5_left_q(la, wk[1], lqa);
-                        weno5_left_q(lb, wk[1], lqb);
-                        ca = weno5_candidates(la);
-                        cb = weno5_candidates(lb);
-                        if (!(nbv[r] & 2u)) {      // a tile's last row has no row above it in LDS: its own right-biased values, as ever
-                            weno5_right_q(la, wk[1], rqa);
-                            weno5_right_q(lb, wk[1], rqb);
-                        }
-                    }
-                    T* const qb = qbuf + own_lds[r];
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        V w2;
-                        w2.x = lqa[k]; w2.y = lqb[k];
-                        *reinterpret_cast<V*>(qb + k * lds_plane) = w2;
-                    }
-                    __syncthreads();
-                    if (nbv[r] & 2u) {           // the row above is a row of this tile: its left-biased values, reversed, are ours on the right
-#pragma unroll
-                        for (int k = 0; k < 3; ++k) {
-                            const V n2 = *reinterpret_cast<const V*>(qb + ls[1] + (2 - k) * lds_plane);
-                            rqa[k] = n2.x; rqb[k] = n2.y;
-                        }
-                    }
-                    weno5_combine_cand(ca, lqa, rqa, pc[0][1], hd[0][1]);
-                    weno5_combine_cand(cb, lqb, rqb, pc[1][1], hd[1][1]);
-                } else if (d == 1) { sten(IntTag<1>(), va, pc[0][1], hd[0][1], slot_real); sten(IntTag<1>(), vb, pc[1][1], hd[1][1], slot_real); }
+                if (d == 1) { sten(IntTag<1>(), va, pc[0][1], hd[0][1], slot_real); sten(IntTag<1>(), vb, pc[1][1], hd[1][1], slot_real); }
                 else { sten(IntTag<(ND > 3 ? 2 : 1)>(), va, pc[0][d], hd[0][d], slot_real); sten(IntTag<(ND > 3 ? 2 : 1)>(), vb, pc[1][d], hd[1][d], slot_real); }
             }
             {   // the contiguous axis: cells j-3 .. j+4 = [b64][b128][own pair][b128][b64]
@@ -880,7 +766,7 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
                 }
                 if (c == 0) o2.x = o; else o2.y = o;
             }
-            if ((!vp_on && r < R - 1) || last_real) buf_store2(o2, rout, own_g[r], so_out);
+            if (r < R - 1 || last_real) buf_store2(o2, rout, own_g[r], so_out);
             if constexpr (SCHEME == HJ_WENO5) {
                 if (eps_prod) {
                     T* ob = obuf + ((p - p_begin) & 1) * lds_plane;
@@ -908,10 +794,8 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if constexpr (OFF == 0) {            // the pass's first plane: the new plane joins behind the window, nothing moves
-                if constexpr (PH == 0) {         // (TWOB: appended when the pass begins, before its second staging reuses the register set)
-                    q[r][0][7] = own_c[r].x;
-                    q[r][1][7] = own_c[r].y;
-                }
+                q[r][0][7] = own_c[r].x;
+                q[r][1][7] = own_c[r].y;
             } else {                              // its second plane: two places down, ready for the next pass
 #pragma unroll
                 for (int j = 0; j < 6; ++j) { q[r][0][j] = q[r][0][j + 2]; q[r][1][j] = q[r][1][j + 2]; }
@@ -930,19 +814,8 @@ __global__ __launch_bounds__(NT, OCC) void fused_pair_kernel(const T* __restrict
     if (A.timing && tid == 0) A.timing[4 * (size_t)A.nblocks + 8 * (size_t)L + 5] = wall_clock64();   // loop start
     const int nplanes = p_end - p_begin;
     for (int m = 0; m < nplanes; m += PD) {
-        if constexpr (TWOB) {
-            const bool two = m + 1 < nplanes;
-#pragma unroll
-            for (int r = 0; r < R; ++r) { q[r][0][7] = own[0][r].x; q[r][1][7] = own[0][r].y; }      // plane P(m + 4), requested a pass ago
-            body(IntTag<0>(), IntTag<1>(), m, own[0], own[1], hal[0], hin[0], halp[0], hinp[0], y0s[0], pls[0]);
-            if (two) body(IntTag<1>(), IntTag<1>(), m + 1, own[1], own[0], hal[1], hin[1], halp[1], hinp[1], y0s[1], pls[1]);
-            __syncthreads();
-            body(IntTag<0>(), IntTag<2>(), m, own[0], own[1], hal[0], hin[0], halp[0], hinp[0], y0s[0], pls[0]);
-            if (two) body(IntTag<1>(), IntTag<2>(), m + 1, own[1], own[0], hal[1], hin[1], halp[1], hinp[1], y0s[1], pls[1]);
-        } else {
-            body(IntTag<0>(), IntTag<0>(), m, own[0], own[1], hal[0], hin[0], halp[0], hinp[0], y0s[0], pls[0]);
-            if (m + 1 < nplanes) body(IntTag<1>(), IntTag<0>(), m + 1, own[1], own[0], hal[1], hin[1], halp[1], hinp[1], y0s[1], pls[1]);
-        }
+        body(IntTag<0>(), m, own[0], own[1], hal[0], hin[0], halp[0], hinp[0], y0s[0], pls[0]);
+        if (m + 1 < nplanes) body(IntTag<1>(), m + 1, own[1], own[0], hal[1], hin[1], halp[1], hinp[1], y0s[1], pls[1]);
         if (A.timing && tid == 0 && m == 0) A.timing[4 * (size_t)A.nblocks + 8 * (size_t)L + 7] = wall_clock64();
     }
     if (A.timing && tid == 0) A.timing[4 * (size_t)A.nblocks + 8 * (size_t)L + 6] = wall_clock64();   // loop end

@@ -244,7 +244,6 @@ int launch_pair4_mode(hj_ctx* c, const SubstepCall& s) {
     A.halo_ahead = 0;
     A.npairs = 0;
     c->last_nbuf = 2;
-    c->last_nbase = 2;
     c->last_kernel = "fused_pair4_kernel";
     c->last_E[0] = t.chunk;
     for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
@@ -349,7 +348,6 @@ int launch_flat4_mode(hj_ctx* c, const SubstepCall& s) {
     A.halo_ahead = 0;
     A.npairs = 0;
     c->last_nbuf = 2;
-    c->last_nbase = 2;
     if (t.lds_bytes > 64 * 1024) {
         static std::mutex mu;
         static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
@@ -696,17 +694,12 @@ int launch_cfg(hj_ctx* c, const SubstepCall& s) {
                 // 11 % fewer fetched bytes); the 256-thread configurations (several workgroups per CU) lose 1-3 %
                 // (2-D / 3-D only: the 4-D instantiations are built without the parked ring -- hj_fusedv.h, AHM -- whatever HJ_PAIR_RING says)
                 const bool ring = HAM::ND <= 3 && (c->pair_ring == 1 || (c->pair_ring < 0 && kp.NT == 512 && kp.R == 2 && c->total >= 6500000));
-                // (HJ_TWO_PLANES builds: two planes per barrier need four buffers under the planes parked ahead -- hj_fusedv.h, TWOB)
-                c->last_nbase = (HJ_TWO_PLANES && light_scheme(SCHEME) && HAM::ND <= 3 && !hj::ham_xp<HAM>::value) ? 4 : 2;
-                c->last_nbuf = c->last_nbase + (ring ? c->pair_ah : 0);          // planes parked ahead + the double buffer
+                c->last_nbuf = 2 + (ring ? c->pair_ah : 0);          // the double buffer + planes parked ahead
                 const long long key = ((long long)SCHEME << 40) | ((long long)stage_class(s.stage) << 36) | (1ll << 35) |
                                       ((long long)kp.NT << 20) | ((long long)kp.R << 12) | ((long long)kp.KH << 4) | (long long)(ring ? 1 : 0) |
                                       (produce ? 2ll : 0ll);
                 TuneTrial tr;
-                // (HJ_WENO_LDS_SHARE builds: two planes for the epsilon producer -- kept whether it runs or not -- and three for the smoothness values
-                //  the middle axis shares between lanes: hj_fusedv.h, WX)
-                const int wx_planes = (HJ_WENO_LDS_SHARE && SCHEME == HJ_WENO5 && HAM::ND == 3) ? 5 : (produce ? 2 : 0);
-                const Tiling tp = tune_begin<HAM::ND>(c, s, kp, 2, c->last_nbuf + wx_planes, key, tr);
+                const Tiling tp = tune_begin<HAM::ND>(c, s, kp, 2, c->last_nbuf + (produce ? 2 : 0), key, tr);      // (+ the epsilon producer's two planes)
                 if (tp.ok) {
                     int rc_t = -12345;
 #define X(NT_, R_, KH_, OCC_) if constexpr (cfg_built(SCHEME, HAM::ND, NT_, R_, true, (int)sizeof(T))) { if (rc_t == -12345 && kp.NT == NT_ && kp.R == R_ && kp.KH == KH_ && occp == OCC_) rc_t = launch_tiled<T, HAM, SCHEME, NT_, R_, KH_, OCC_, 2, true>(c, s, tp); }
@@ -762,7 +755,7 @@ int launch_scheme(hj_ctx* c, const SubstepCall& s) {
                 if (it == c->xp_choice.end()) {
                     const auto keep_plan = c->last_plan;
                     const char* keep_kernel = c->last_kernel;
-                    int keep_E[HJ_MAX_DIM], keep_nbuf = c->last_nbuf, keep_nbase = c->last_nbase;
+                    int keep_E[HJ_MAX_DIM], keep_nbuf = c->last_nbuf;
                     for (int d = 0; d < HJ_MAX_DIM; ++d) keep_E[d] = c->last_E[d];
                     const int keep_dry = c->dry;
                     c->dry = 2;
@@ -779,7 +772,7 @@ int launch_scheme(hj_ctx* c, const SubstepCall& s) {
                     if (launch_scheme<T, HAM>(c, a) == HJ_OK && c->last_plan.ntiles > 0) c0 = cost();
                     if (launch_xp<T, HAM>(c, s) == HJ_OK) cx = cost();
                     c->dry = keep_dry;
-                    c->last_plan = keep_plan; c->last_kernel = keep_kernel; c->last_nbuf = keep_nbuf; c->last_nbase = keep_nbase;
+                    c->last_plan = keep_plan; c->last_kernel = keep_kernel; c->last_nbuf = keep_nbuf;
                     for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = keep_E[d];
                     hj_ctx::XpTrial t;
                     t.prior = cx > 0 && (c0 <= 0 || cx <= 0.975 * c0);
