@@ -15,6 +15,9 @@
  *  - every `const void* / void*` array argument is a DEVICE pointer (HIP) to a
  *    C-order (last axis contiguous) array of the ctx's dtype, owned by the
  *    caller.  `double*` outputs documented as "host" are host pointers.
+ *  - array pointers need only the alignment of one element of the ctx dtype.
+ *  - no entry point reads or writes outside the arrays it is given (the pad
+ *    planes of slab inputs excepted) or writes an argument documented as const.
  *  - calls are stream-ordered on the ctx stream (hj_ctx_set_stream) and return
  *    without synchronising unless they hand back a host scalar.
  *  - return 0 on success, a negative HJ_E* code otherwise; the message is in
