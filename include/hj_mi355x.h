@@ -440,6 +440,20 @@ unsigned long long hj_ctx_state_generation(hj_ctx* ctx);
 int hj_plan_substep(int ndim, const int64_t* N_host, const int* bc_host, int dtype, int scheme, int ham, int stage,
                     int64_t p0, int64_t p1, int halo_lo, int halo_hi, int num_cus,
                     int64_t* out_host /* 12 */, char* kernel_name_host, int name_cap);
+/* As hj_plan_substep, and symbols_host (symbols_cap bytes) receives the mangled names of the kernel instantiations the
+ * plan would launch, one per line (as hj_launch_record_read): tests check on a machine without a GPU which instantiation a
+ * (grid, scheme, stage, environment) selects.  No reference counterpart. */
+int hj_plan_substep_symbols(int ndim, const int64_t* N_host, const int* bc_host, int dtype, int scheme, int ham, int stage,
+                            int64_t p0, int64_t p1, int halo_lo, int halo_hi, int num_cus,
+                            int64_t* out_host /* 12 */, char* symbols_host, int symbols_cap);
+/* Test hook beside hj_last_kernel: while the record is on (on != 0; off by default, one branch per launch), every launch of a kernel of
+ * the library on this ctx adds that instantiation to a set.  Kernels compiled at run time (hj_ham_register) are no symbols of the library
+ * and are left out.  Switching the record on or off empties it. */
+int hj_launch_record(hj_ctx* ctx, int on);
+/* The record as text: the mangled names of the kernels, one per line, in buf_host (cap bytes).  (A kernel's name is its host stub's --
+ * what `nm -D` lists as ...__device_stub__<kernel>... -- without that prefix.)  Returns the bytes the text needs including its NUL; the record is emptied when it fitted (call with cap 0 to
+ * size the buffer).  Negative: an error code.  No reference counterpart. */
+int hj_launch_record_read(hj_ctx* ctx, char* buf_host, int cap);
 const char* hj_version(void);
 
 #ifdef __cplusplus

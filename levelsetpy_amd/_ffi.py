@@ -95,6 +95,9 @@ SIGNATURES = {
     "hj_last_tile": (_i, [_vp, _pi]),
     "hj_ctx_state_generation": (C.c_uint64, [_vp]),
     "hj_plan_substep": (_i, [_i, _pi64, _pi, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _pi64, C.c_char_p, _i]),
+    "hj_plan_substep_symbols": (_i, [_i, _pi64, _pi, _i, _i, _i, _i, _i64, _i64, _i, _i, _i, _pi64, C.c_char_p, _i]),
+    "hj_launch_record": (_i, [_vp, _i]),
+    "hj_launch_record_read": (_i, [_vp, C.c_char_p, _i]),
     "hj_version": (C.c_char_p, []),
 }
 

@@ -424,9 +424,9 @@ int weno_eps_to(hj_ctx* c, const void* y, void* out) {
     {                                                                                            \
         GridArgs<T, ND> G;                                                                       \
         fill_grid<T, ND>(c, G);                                                                  \
-        hipLaunchKernelGGL((max_d1sq_kernel<T, ND>), dim3(bx, by), dim3(256), 0, c->stream,      \
+        HJ_LAUNCH(c, (max_d1sq_kernel<T, ND>), dim3(bx, by), dim3(256), 0, c->stream,      \
                            (const T*)y, G, c->partials, chunk);                                  \
-        hipLaunchKernelGGL((partials_to_values_kernel<T>), dim3(1), dim3(256), 0, c->stream,     \
+        HJ_LAUNCH(c, (partials_to_values_kernel<T>), dim3(1), dim3(256), 0, c->stream,     \
                            c->partials, nblocks, (T*)out, c->ndim);                              \
     }
     if (c->dtype == HJ_F64) {
@@ -466,7 +466,7 @@ int weno_eps_rows(hj_ctx* c, const void* y, int* nrows) {
     {                                                                                                      \
         GridArgs<T, ND> G;                                                                                 \
         fill_grid<T, ND>(c, G);                                                                            \
-        hipLaunchKernelGGL((max_d1sq_kernel<T, ND, 1024>), dim3((unsigned)bx, by), dim3(1024), 0, c->stream, \
+        HJ_LAUNCH(c, (max_d1sq_kernel<T, ND, 1024>), dim3((unsigned)bx, by), dim3(1024), 0, c->stream, \
                            (const T*)y, G, c->partials, chunk);                                            \
     }
     if (c->dtype == HJ_F64) {
@@ -649,9 +649,9 @@ int read_ring(hj_ctx* c, int pos, double* sb, double* amax) {
 
 int hjh::eps_rows_to_vals(hj_ctx* c, const double* rows, int nrows, hipStream_t stream) {
     if (c->dtype == HJ_F64)
-        hipLaunchKernelGGL((partials_to_values_kernel<double>), dim3(1), dim3(256), 0, stream, rows, nrows, (double*)c->weno_vals, c->ndim);
+        HJ_LAUNCH(c, (partials_to_values_kernel<double>), dim3(1), dim3(256), 0, stream, rows, nrows, (double*)c->weno_vals, c->ndim);
     else
-        hipLaunchKernelGGL((partials_to_values_kernel<float>), dim3(1), dim3(256), 0, stream, rows, nrows, (float*)c->weno_vals, c->ndim);
+        HJ_LAUNCH(c, (partials_to_values_kernel<float>), dim3(1), dim3(256), 0, stream, rows, nrows, (float*)c->weno_vals, c->ndim);
     HIP_TRY(hipGetLastError());
     return HJ_OK;
 }
@@ -687,7 +687,7 @@ template <typename T> static int upwind_launch(hj_ctx* c, int scheme, int dim, c
         HIP_TRY(hipStreamSynchronize(c->stream));
         eps = T(1e-6) * m + Lim<T>::tiny;
     }
-#define HJ_UPW(S) hipLaunchKernelGGL((upwind_kernel<T, S>), dim3(blocks), dim3(256), 0, c->stream, (const T*)phi, (T*)dL, (T*)dR, V, eps, keys)
+#define HJ_UPW(S) HJ_LAUNCH(c, (upwind_kernel<T, S>), dim3(blocks), dim3(256), 0, c->stream, (const T*)phi, (T*)dL, (T*)dR, V, eps, keys)
     switch (scheme) {
         case HJ_ENO2: HJ_UPW(HJ_ENO2); break;
         case HJ_ENO3: HJ_UPW(HJ_ENO3); break;
@@ -709,7 +709,7 @@ static int upwind_all_launch(hj_ctx* c, int scheme, const void* y, void* const* 
     A.max_d1sq = epsv;
     A.keys = keys;
     const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 16);
-#define HJ_UPA(S) hipLaunchKernelGGL((upwind_all_kernel<T, ND, S>), dim3(blocks), dim3(256), 0, c->stream, (const T*)y, A)
+#define HJ_UPA(S) HJ_LAUNCH(c, (upwind_all_kernel<T, ND, S>), dim3(blocks), dim3(256), 0, c->stream, (const T*)y, A)
     switch (scheme) {
         case HJ_ENO2: HJ_UPA(HJ_ENO2); break;
         case HJ_ENO3: HJ_UPA(HJ_ENO3); break;
@@ -1085,7 +1085,7 @@ static int split_end_launch(hj_ctx* c, const void* const* dL, const void* const*
     A.n = c->total;
     A.nd = c->ndim;
     const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 8);
-    hipLaunchKernelGGL((lf_split_end_kernel<T>), dim3(blocks), dim3(256), 0, c->stream, A);
+    HJ_LAUNCH(c, (lf_split_end_kernel<T>), dim3(blocks), dim3(256), 0, c->stream, A);
     HIP_TRY(hipGetLastError());
     return HJ_OK;
 }
@@ -1282,12 +1282,40 @@ int hj_ctx_create(hj_ctx** out, int ndim, const int64_t* N, const double* xmin, 
     return ctx_create_impl(out, ndim, N, xmin, dx, bc, toward_zero, dtype, device, 0);
 }
 
+// record -> newline-separated mangled names of the kernels' host stubs in buf (cap bytes, NUL-terminated); returns the bytes the text needs
+// including its NUL (the record is cleared when it fitted), or a negative error code
+static int record_read(hj_ctx* c, char* buf, int cap) {
+    std::string text;
+    for (const void* k : c->rec) {
+        Dl_info info;
+        if (!dladdr(k, &info) || !info.dli_sname || info.dli_saddr != k) return fail(HJ_ESTATE, "a recorded kernel address is no symbol of the library");
+        if (!text.empty()) text += '\n';
+        text += info.dli_sname;
+    }
+    const int need = (int)text.size() + 1;
+    if (buf && cap >= need) { memcpy(buf, text.c_str(), (size_t)need); c->rec.clear(); }
+    else if (buf && cap > 0) buf[0] = 0;
+    return need;
+}
+
+int hj_launch_record(hj_ctx* c, int on) {
+    if (!c) return fail(HJ_EINVAL, "null ctx");
+    c->rec_on = on != 0;
+    c->rec.clear();
+    return HJ_OK;
+}
+
+int hj_launch_record_read(hj_ctx* c, char* buf, int cap) {
+    if (!c) return fail(HJ_EINVAL, "null ctx");
+    return record_read(c, buf, cap);
+}
+
 // The launch plan of one substep over planes [p0, p1) of an N-cell grid, made WITHOUT a device (bench.py --plan-only: what every rank of
 // an N-GPU run will launch, before the node is there).  Same code as the real launch up to the point where the kernel would be enqueued.
 // out[12] = {threads per workgroup, workgroups, tiles, chunks, chunk length (planes), tile extents E1..E3, LDS bytes, workgroups per CU,
 // slab pads honoured (1/0), 0}; kernel_name (cap bytes) receives the kernel's name.  Built-in Hamiltonians only.
-int hj_plan_substep(int ndim, const int64_t* N, const int* bc, int dtype, int scheme, int ham, int stage, int64_t p0, int64_t p1,
-                    int halo_lo, int halo_hi, int num_cus, int64_t* out, char* kernel_name, int cap) {
+static int plan_substep_impl(int ndim, const int64_t* N, const int* bc, int dtype, int scheme, int ham, int stage, int64_t p0, int64_t p1,
+                             int halo_lo, int halo_hi, int num_cus, int64_t* out, char* kernel_name, int cap, char* symbols, int symbols_cap) {
     if (!N || !bc || !out) return fail(HJ_EINVAL, "null argument");
     if (ham_ndim(ham) != ndim || user_ham_valid(ham)) return fail(HJ_EUNSUPPORTED, "hj_plan_substep plans the built-in Hamiltonians (id %d, dim %d)", ham, ndim);
     if (scheme < HJ_ENO2 || scheme > HJ_ENO3_FAST) return fail(HJ_EINVAL, "unknown scheme %d", scheme);
@@ -1296,6 +1324,7 @@ int hj_plan_substep(int ndim, const int64_t* N, const int* bc, int dtype, int sc
     int rc = ctx_create_impl(&c, ndim, N, xmin, dx, bc, nullptr, dtype, -1, num_cus > 0 ? num_cus : 256);
     if (rc) return rc;
     c->halo_lo = halo_lo != 0; c->halo_hi = halo_hi != 0;
+    c->rec_on = symbols != nullptr;
     const double par[8] = {1, 1, 1, 1, 1, 1, 1, 1};
     SubstepCall s{};
     s.scheme = scheme; s.ham = ham; s.stage = stage; s.restrict_sign = 0; s.par = par; s.dt = 0.0;
@@ -1307,9 +1336,25 @@ int hj_plan_substep(int ndim, const int64_t* N, const int* bc, int dtype, int sc
         out[4] = c->last_E[0]; out[5] = c->last_E[1]; out[6] = c->last_E[2]; out[7] = c->last_E[3];
         out[8] = (int64_t)c->last_plan.lds_bytes; out[9] = c->last_plan.wg_per_cu; out[10] = (c->halo_lo || c->halo_hi) ? 1 : 0; out[11] = 0;
         if (kernel_name && cap > 0) { strncpy(kernel_name, c->last_kernel, (size_t)cap - 1); kernel_name[cap - 1] = 0; }
+        if (symbols) {
+            const int need = record_read(c, symbols, symbols_cap);
+            if (need < 0) rc = need;
+            else if (need > symbols_cap) rc = fail(HJ_EINVAL, "symbols_cap %d is too small for the plan's %d bytes of kernel names", symbols_cap, need);
+        }
     }
     delete c;
     return rc;
+}
+
+int hj_plan_substep(int ndim, const int64_t* N, const int* bc, int dtype, int scheme, int ham, int stage, int64_t p0, int64_t p1,
+                    int halo_lo, int halo_hi, int num_cus, int64_t* out, char* kernel_name, int cap) {
+    return plan_substep_impl(ndim, N, bc, dtype, scheme, ham, stage, p0, p1, halo_lo, halo_hi, num_cus, out, kernel_name, cap, nullptr, 0);
+}
+
+int hj_plan_substep_symbols(int ndim, const int64_t* N, const int* bc, int dtype, int scheme, int ham, int stage, int64_t p0, int64_t p1,
+                            int halo_lo, int halo_hi, int num_cus, int64_t* out, char* symbols, int symbols_cap) {
+    if (!symbols || symbols_cap < 1) return fail(HJ_EINVAL, "null argument");
+    return plan_substep_impl(ndim, N, bc, dtype, scheme, ham, stage, p0, p1, halo_lo, halo_hi, num_cus, out, nullptr, 0, symbols, symbols_cap);
 }
 
 void hj_ctx_destroy(hj_ctx* c) {
@@ -1378,9 +1423,9 @@ int hj_ghost(hj_ctx* c, int dim, int width, const void* in, void* out) {
     const long long total = c->total / c->N[dim] * (c->N[dim] + 2 * width);
     const int blocks = (int)std::min<long long>((total + 255) / 256, 256 * 8);
     if (c->dtype == HJ_F64)
-        hipLaunchKernelGGL((ghost_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (const double*)in, (double*)out, make_view<double>(c, dim, false), width);
+        HJ_LAUNCH(c, (ghost_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (const double*)in, (double*)out, make_view<double>(c, dim, false), width);
     else
-        hipLaunchKernelGGL((ghost_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (const float*)in, (float*)out, make_view<float>(c, dim, false), width);
+        HJ_LAUNCH(c, (ghost_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (const float*)in, (float*)out, make_view<float>(c, dim, false), width);
     HIP_TRY(hipGetLastError());
     return HJ_OK;
 }
@@ -1527,7 +1572,7 @@ int term_launch_nd(hj_ctx* c, int kind, int scheme, const void* y, const void* c
     fill_term_par<T>(c, arr, scal, order, A.P);
     A.keys = keys;
     const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 16);
-#define HJ_TK(S, K) hipLaunchKernelGGL((term_kernel<T, ND, S, K>), dim3(blocks), dim3(256), 0, c->stream, A)
+#define HJ_TK(S, K) HJ_LAUNCH(c, (term_kernel<T, ND, S, K>), dim3(blocks), dim3(256), 0, c->stream, A)
 #define HJ_TS(K)                                                                       \
     switch (scheme) {                                                                  \
         case HJ_ENO2: HJ_TK(HJ_ENO2, K); break;                                        \
@@ -1663,7 +1708,7 @@ int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double
     for (int k = 0; k < NOUT; ++k) A.out[k] = (T*)out[k];
     A.key = key;
     const int blocks = (int)std::min<int64_t>((c->total + 255) / 256, 256 * 16);
-#define HJ_CK(K) hipLaunchKernelGGL((curv_kernel<T, ND, K>), dim3(blocks), dim3(256), 0, c->stream, A, CurvTraceArgs<T, ND, K>{})
+#define HJ_CK(K) HJ_LAUNCH(c, (curv_kernel<T, ND, K>), dim3(blocks), dim3(256), 0, c->stream, A, CurvTraceArgs<T, ND, K>{})
     switch (out_kind) {
         case HJ_CURV_TRACE: {
             TraceArgs<T, ND> TR;
@@ -1679,8 +1724,8 @@ int curv_launch_nd(hj_ctx* c, int out_kind, const void* y, const void* b, double
                 }
             TR.reduce = tin->reduce;
             // all-scalar matrices: the instantiation without the entry loads and the reduction (fewer VGPRs)
-            if (tin->reduce) hipLaunchKernelGGL((curv_kernel<T, ND, HJ_CURV_TRACE>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
-            else hipLaunchKernelGGL((curv_kernel<T, ND, HJ_CURV_TRACE_SC>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
+            if (tin->reduce) HJ_LAUNCH(c, (curv_kernel<T, ND, HJ_CURV_TRACE>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
+            else HJ_LAUNCH(c, (curv_kernel<T, ND, HJ_CURV_TRACE_SC>), dim3(blocks), dim3(256), 0, c->stream, A, TR);
             break;
         }
         case HJ_CURV_TERM: HJ_CK(HJ_CURV_TERM); break;
@@ -1829,10 +1874,10 @@ int hj_rk_combine(hj_ctx* c, int mode, double dt, const void* x0, const void* y,
     if (n <= 0) return HJ_OK;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
     if (c->dtype == HJ_F64)
-        hipLaunchKernelGGL((rk_combine_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, mode, dt, (const double*)x0,
+        HJ_LAUNCH(c, (rk_combine_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, mode, dt, (const double*)x0,
                            (const double*)y, (const double*)z, (double*)out, (long long)n);
     else
-        hipLaunchKernelGGL((rk_combine_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, mode, (float)dt, (const float*)x0,
+        HJ_LAUNCH(c, (rk_combine_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, mode, (float)dt, (const float*)x0,
                            (const float*)y, (const float*)z, (float*)out, (long long)n);
     HIP_TRY(hipGetLastError());
     return HJ_OK;
@@ -1897,7 +1942,7 @@ int hj_static_step_bound(hj_ctx* c, int ham, const double* par, double* sb, doub
         fill_ham<T>(c, par, P, ham);                                                             \
         DxArgs DX;                                                                               \
         for (int d = 0; d < HJ_MAX_DIM; ++d) DX.dx[d] = c->dx[d];                                \
-        hipLaunchKernelGGL((alpha_bound_kernel<T, HAM<T>>), dim3(blocks), dim3(256), 0,          \
+        HJ_LAUNCH(c, (alpha_bound_kernel<T, HAM<T>>), dim3(blocks), dim3(256), 0,          \
                            c->stream, G, P, c->keys, DX, c->alpha_part, c->keys + 6,             \
                            (unsigned long long*)nullptr, 0ull, DtArgs{0, 0, 0, nullptr});        \
     }
@@ -2031,7 +2076,7 @@ static int rk_step_dynamic(hj_ctx* c, int order, int scheme, int ham, const doub
             if ((rc = do_substep(c, b, slot1))) return rc;
             DxArgs DX;
             for (int d = 0; d < HJ_MAX_DIM; ++d) DX.dx[d] = c->dx[d];
-            hipLaunchKernelGGL((bound_to_dt_kernel<0>), dim3(1), dim3(64), 0, c->stream, c->ring + (size_t)c->slot_ring[slot1] * HJ_MAX_DIM, c->ndim, DX, dta,
+            HJ_LAUNCH(c, (bound_to_dt_kernel<0>), dim3(1), dim3(64), 0, c->stream, c->ring + (size_t)c->slot_ring[slot1] * HJ_MAX_DIM, c->ndim, DX, dta,
                                c->host_words, seq);
             HIP_TRY(hipGetLastError());
         }
@@ -2376,9 +2421,9 @@ int hj_minmax_with(hj_ctx* c, int op, void* y, const void* other, int64_t n) {
     c->eps_ready = false;
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
     if (c->dtype == HJ_F64)
-        hipLaunchKernelGGL((minmax_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (double*)y, (const double*)other, (long long)n, op);
+        HJ_LAUNCH(c, (minmax_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (double*)y, (const double*)other, (long long)n, op);
     else
-        hipLaunchKernelGGL((minmax_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (float*)y, (const float*)other, (long long)n, op);
+        HJ_LAUNCH(c, (minmax_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (float*)y, (const float*)other, (long long)n, op);
     HIP_TRY(hipGetLastError());
     return HJ_OK;
 }
@@ -2389,9 +2434,9 @@ int hj_any_nan(hj_ctx* c, const void* y, int64_t n, int* has) {
     const int blocks = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
     if (n > 0) {
         if (c->dtype == HJ_F64)
-            hipLaunchKernelGGL((any_nan_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (const double*)y, (long long)n, c->flag);
+            HJ_LAUNCH(c, (any_nan_kernel<double>), dim3(blocks), dim3(256), 0, c->stream, (const double*)y, (long long)n, c->flag);
         else
-            hipLaunchKernelGGL((any_nan_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (const float*)y, (long long)n, c->flag);
+            HJ_LAUNCH(c, (any_nan_kernel<float>), dim3(blocks), dim3(256), 0, c->stream, (const float*)y, (long long)n, c->flag);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipMemcpyAsync(has, c->flag, sizeof(int), hipMemcpyDeviceToHost, c->stream));

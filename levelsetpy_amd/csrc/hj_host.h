@@ -16,6 +16,7 @@
 #include <cstring>
 #include <limits>
 #include <map>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -34,6 +35,13 @@ int fail(int code, const char* fmt, ...);     // records the message for hj_last
         if (e_ != hipSuccess)                                                            \
             return hjh::fail(HJ_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
                         __FILE__, __LINE__);                                             \
+    } while (0)
+
+// a launch on the context's record (hj_ctx::note_kernel, hj_launch_record)
+#define HJ_LAUNCH(ctx, kern, ...)                 \
+    do {                                          \
+        (ctx)->note_kernel(kern);                 \
+        hipLaunchKernelGGL(kern, __VA_ARGS__);    \
     } while (0)
 
 constexpr int RING_SLOTS = 2048;  // bound-key ring (each entry: HJ_MAX_DIM keys)
@@ -221,6 +229,12 @@ struct hj_ctx {
     // make_tiling's answer per (NT, R, KH, vec, nbuf): it depends on nothing else that changes after hj_ctx_create, and the
     // enumeration it runs (64 row extents in 3-D, 64^2 in 4-D) was paid on EVERY launch (round 4: host cost of small grids)
     mutable std::map<long long, hjh::Tiling> tiling_cache;
+    // hj_launch_record (test hook, off by default): host-stub addresses of the library's kernels this context launched -- or, dry, planned
+    // to launch -- since the record was last read.  Run-time (hipRTC) kernels are no library symbols and are left out.
+    bool rec_on = false;
+    std::set<const void*> rec;
+    // (dry == 2 is a planning look from a live context, hj_inst.hip launch_scheme: nothing it visits is launched)
+    template <typename K> void note_kernel(K kern) { if (rec_on && dry != 2) rec.insert(reinterpret_cast<const void*>(kern)); }
 };
 
 namespace hjh {

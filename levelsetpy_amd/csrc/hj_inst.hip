@@ -52,6 +52,7 @@ int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
         c->last_plan.wg_per_cu = occ_blocks; c->last_plan.lds_bytes = t.lds_bytes;
         if (c->dry) {
             c->last_kernel = PAIR ? "fused_pair_kernel" : "fused_substep_kernel";
+            c->note_kernel(kern0);
             c->last_E[0] = t.chunk;
             for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
             return HJ_OK;
@@ -87,6 +88,7 @@ int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
     if (produce) A.npairs = 0;        // the output reduction of the intended WENO5 pairs planes in ascending order
     auto kern = tiled_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PD, MODE, PAIR>();
     c->last_kernel = PAIR ? "fused_pair_kernel" : "fused_substep_kernel";
+    c->note_kernel(kern);
     c->last_E[0] = t.chunk;
     for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
     if (t.lds_bytes > 64 * 1024) {
@@ -131,6 +133,7 @@ int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
         S.prod = c->eps_prod;
         S.nprod = t.nblocks;
         S.rows = c->eps_rows;
+        c->note_kernel(eps_seam_kernel<T, ND>);
         hipLaunchKernelGGL((eps_seam_kernel<T, ND>), dim3(HJ_EPS_ROWS), dim3(1024), 0, call_stream(c, s), S);
         HIP_TRY(hipGetLastError());
         c->eps_ready = true;
@@ -223,6 +226,7 @@ int launch_pair4_mode(hj_ctx* c, const SubstepCall& s) {
     c->last_plan.wg_per_cu = wg_per_cu; c->last_plan.lds_bytes = t.lds_bytes;
     if (c->dry) {
         c->last_kernel = "fused_pair4_kernel";
+        c->note_kernel(kern);
         c->last_E[0] = t.chunk;
         for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
         return HJ_OK;
@@ -245,6 +249,7 @@ int launch_pair4_mode(hj_ctx* c, const SubstepCall& s) {
     A.npairs = 0;
     c->last_nbuf = 2;
     c->last_kernel = "fused_pair4_kernel";
+    c->note_kernel(kern);
     c->last_E[0] = t.chunk;
     for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
     if (t.lds_bytes > 64 * 1024) {
@@ -328,6 +333,7 @@ int launch_flat4_mode(hj_ctx* c, const SubstepCall& s) {
     c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
     c->last_plan.wg_per_cu = wg_per_cu; c->last_plan.lds_bytes = t.lds_bytes;
     c->last_kernel = "fused_flat4_kernel";
+    c->note_kernel(kern);
     c->last_E[0] = t.chunk;
     for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
     if (c->dry) return HJ_OK;
@@ -477,6 +483,7 @@ int launch_direct(hj_ctx* c, const SubstepCall& s) {
         c->last_plan.ntiles = 0; c->last_plan.nchunks = 1; c->last_plan.threads = 256; c->last_plan.wg_per_cu = 8; c->last_plan.lds_bytes = 0;
         c->last_plan.nblocks = (int)std::min<long long>((cells + 255) / 256, 256 * 16);
         c->last_kernel = "direct_substep_kernel";
+        c->note_kernel(direct_substep_kernel<T, HAM, SCHEME>);
         for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
         return HJ_OK;
     }
@@ -523,6 +530,7 @@ int launch_direct(hj_ctx* c, const SubstepCall& s) {
         if (cells <= 0) continue;
         int blocks = (int)std::min<long long>((cells + 255) / 256, 256 * 16);
         c->last_kernel = "direct_substep_kernel";
+        c->note_kernel(direct_substep_kernel<T, HAM, SCHEME>);
         for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
         hipLaunchKernelGGL((direct_substep_kernel<T, HAM, SCHEME>), dim3(blocks), dim3(256), 0, call_stream(c, s), A);
         HIP_TRY(hipGetLastError());
@@ -567,33 +575,29 @@ int launch_coop_cpt(hj_ctx* c, const CoopCall& s, int nblocks) {
     for (int x = 0; x < 8; ++x) c->coop_xcd[x] += (unsigned long long)(s.order - 1) * nper[x];
     c->coop_all += (unsigned long long)(s.order - 1) * nx;
     c->last_kernel = "coop_rk_kernel";
+    c->note_kernel(kern);
     for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
     return HJ_OK;
 }
 
 template <typename T, typename HAM, int SCHEME>
 int launch_coop_scheme(hj_ctx* c, const CoopCall& s) {
-    // resident workgroups of the 1-cell instantiation decide the shape: as many 256-thread workgroups as fit at once, then 1, 2 or 4
-    // cells per thread (51^3 = 132 651 cells: 519 workgroups x 1 cell when three fit per CU)
+    // One cell per thread, as many 256-thread workgroups as are resident at once (51^3 = 132 651 cells: 519 workgroups when three fit per CU);
+    // a larger grid takes the stage launches.  (Shapes with 2 and 4 cells per thread were built until the instantiations were compared one by
+    // one: the rule could take them only for launches that fill the device -- on an MI355X 14 of the 20 fp64 shapes never, a 2-cell launch
+    // fitting behind a 1-cell one only where it keeps more than half the workgroups resident -- that is from ~200 000 cells up, where a step
+    // in one launch is slower than its stage launches, profiles/r06_small_grids.txt, and where a launch that needs EVERY workgroup resident
+    // is least safe beside other work on the device.)
     const long long total = c->total;
-    auto cap_of = [&](const void* k) {
-        auto it = c->occ_cache.find(std::make_pair(k, (size_t)0));
-        if (it == c->occ_cache.end()) {
-            int nb = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, 256, 0) != hipSuccess || nb < 1) nb = 1;
-            it = c->occ_cache.emplace(std::make_pair(k, (size_t)0), nb).first;
-        }
-        return (long long)it->second * c->num_cus;
-    };
-    const long long need1 = (total + 255) / 256;
     const void* k1 = reinterpret_cast<const void*>(coop_rk_kernel<T, HAM, SCHEME, 1>);
-    const void* k2 = reinterpret_cast<const void*>(coop_rk_kernel<T, HAM, SCHEME, 2>);
-    const void* k4 = reinterpret_cast<const void*>(coop_rk_kernel<T, HAM, SCHEME, 4>);
-    if (need1 <= cap_of(k1)) return launch_coop_cpt<T, HAM, SCHEME, 1>(c, s, (int)need1);
-    const long long need2 = (total + 511) / 512;
-    if (need2 <= cap_of(k2)) return launch_coop_cpt<T, HAM, SCHEME, 2>(c, s, (int)need2);
-    const long long need4 = (total + 1023) / 1024;
-    if (need4 <= cap_of(k4)) return launch_coop_cpt<T, HAM, SCHEME, 4>(c, s, (int)need4);
+    auto it = c->occ_cache.find(std::make_pair(k1, (size_t)0));
+    if (it == c->occ_cache.end()) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k1, 256, 0) != hipSuccess || nb < 1) nb = 1;
+        it = c->occ_cache.emplace(std::make_pair(k1, (size_t)0), nb).first;
+    }
+    const long long need1 = (total + 255) / 256;
+    if (need1 <= (long long)it->second * c->num_cus) return launch_coop_cpt<T, HAM, SCHEME, 1>(c, s, (int)need1);
     return HJ_XP_FALLBACK;
 }
 
@@ -955,6 +959,7 @@ int launch_fused12(hj_ctx* c, const Stage12Call& s, Tiling12 t) {
     constexpr int ND = HAM::ND;
     auto kern = stage12_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PAIR>();
     c->last_kernel = PAIR ? "fused12_pair_kernel" : "fused12_kernel";
+    c->note_kernel(kern);
     if (t.lds_bytes > 64 * 1024)
         HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
     const auto key = std::make_pair(reinterpret_cast<const void*>(kern), t.lds_bytes);
@@ -982,6 +987,8 @@ int launch_fused12(hj_ctx* c, const Stage12Call& s, Tiling12 t) {
         t.nblocks = t.nchunks * t.ntiles;
         t.bpx = (t.nblocks + 7) / 8;
     }
+    c->last_E[0] = t.chunk;
+    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
     if (c->debug) {
         fprintf(stderr, "[hj] fused12%s NT=%d R=%d KH=%d OCC=%d E=(%d,%d) nA=%d nH=%d ntiles=%d chunk=%d nchunks=%d blocks=%d wg/CU=%d lds=%zu score=%.3f\n",
                 PAIR ? " pair" : "", NT, R, KH, OCC, t.E[1], ND > 2 ? t.E[2] : 0, t.nA, t.nH, t.ntiles, t.chunk, t.nchunks, t.nblocks, it->second, t.lds_bytes, t.score);

@@ -80,6 +80,7 @@ int launch_xp_mode(hj_ctx* c, const SubstepCall& s, int nbuf) {
     c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
     c->last_plan.wg_per_cu = occ_blocks; c->last_plan.lds_bytes = t.lds_bytes;
     c->last_kernel = "fused_pair_kernel (march along axis 1)";
+    c->note_kernel(kern);
     c->last_E[0] = t.chunk;
     for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < 3 ? t.E[d] : 0;
     c->last_nbuf = nbuf;

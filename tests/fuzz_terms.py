@@ -20,8 +20,6 @@ import levelsetpy_amd as L  # noqa: E402
 from levelsetpy_amd.context import device_grid  # noqa: E402
 from oracle import hj_oracle as O  # noqa: E402
 
-budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 4242
 DERIV = {"ENO2": L.upwindFirstENO2, "ENO3": L.upwindFirstENO3, "WENO5_ASSHIPPED": L.upwindFirstWENO5, "WENO5": L.upwindFirstWENO5Intended}
 
 
@@ -155,13 +153,16 @@ def case(rng, k):
     return ok, kind + ":" + used
 
 
-t_end = time.time() + budget
-k, used_all = 0, {}
-while time.time() < t_end:
-    ok, used = case(np.random.default_rng(seed0 + k), k)
-    used_all[used] = used_all.get(used, 0) + 1
-    if not ok:
-        print("FAILED: replay with  python tests/fuzz_terms.py 1 %d" % (seed0 + k))
-        sys.exit(1)
-    k += 1
-print("term fuzz: %d cases ok in %.0f s; %s" % (k, budget, used_all))
+if __name__ == "__main__":
+    budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
+    seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 4242
+    t_end = time.time() + budget
+    k, used_all = 0, {}
+    while time.time() < t_end:
+        ok, used = case(np.random.default_rng(seed0 + k), k)
+        used_all[used] = used_all.get(used, 0) + 1
+        if not ok:
+            print("FAILED: replay with  python tests/fuzz_terms.py 1 %d" % (seed0 + k))
+            sys.exit(1)
+        k += 1
+    print("term fuzz: %d cases ok in %.0f s; %s" % (k, budget, used_all))
