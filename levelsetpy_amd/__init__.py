@@ -31,5 +31,6 @@ from .curvature import (curvatureSecond, hessianSecond, laplacianSecond,      # 
 from .trace_hessian import (termTraceHessian, termDiscount,                     # noqa: F401
                             cellMatrixMultiply, cellMatrixTrace)
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind                     # noqa: F401
+from .query import eval_u, eval_costate, proj, augmentPeriodicData             # noqa: F401
 
 __version__ = "0.1.0"

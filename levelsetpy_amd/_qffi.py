@@ -1,0 +1,87 @@
+"""ctypes binding of libhj_query.so (include/hj_query.h): value-function queries at states.
+
+A library of its own beside libhj_mi355x.so (_ffi.py): stateless entry points, a plain grid descriptor and a
+HIP stream per call.  As there, a missing library is an error -- there is no CPU fallback.
+"""
+import ctypes as C
+import os
+
+from . import _ffi
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.environ.get("HJ_QUERY_LIB") or os.path.join(HERE, "csrc", "libhj_query.so")
+
+MAX_DIM = 4
+OP_MIN, OP_MAX = 0, 1
+POINT_SCHEMES = (_ffi.ENO2, _ffi.ENO3, _ffi.WENO5_ASSHIPPED)      # the schemes hjq_costate_points instantiates
+
+
+class Grid(C.Structure):
+    """hjq_grid."""
+    _fields_ = [("ndim", C.c_int32), ("dtype", C.c_int32),
+                ("N", C.c_int64 * MAX_DIM), ("xmin", C.c_double * MAX_DIM), ("xlast", C.c_double * MAX_DIM),
+                ("dx", C.c_double * MAX_DIM), ("bc", C.c_int32 * MAX_DIM), ("toward_zero", C.c_int32 * MAX_DIM)]
+
+
+_vp, _i, _i64, _u = C.c_void_p, C.c_int, C.c_int64, C.c_uint
+_pg = C.POINTER(Grid)
+
+# name -> (restype, argtypes): every symbol the header declares
+SIGNATURES = {
+    "hjq_interp_points": (_i, [_pg, _vp, _i64, _i64, _vp, _i64, _vp, _i, _vp]),
+    "hjq_costate_points": (_i, [_pg, _i, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp]),
+    "hjq_project_minmax": (_i, [_pg, _vp, _i64, _i64, _u, _i, _vp, _vp]),
+    "hjq_last_error": (C.c_char_p, []),
+    "hjq_last_kernel": (C.c_char_p, []),
+}
+
+_lib = None
+
+
+def lib():
+    """The loaded library; raises RuntimeError (loudly) if it is not built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
+                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
+        # torch first, as _ffi.lib(): the process must share the HIP runtime its wheel bundles
+        try:
+            import torch  # noqa: F401
+        except ImportError:
+            pass
+        L = C.CDLL(LIB_PATH)
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)
+            fn.restype = res
+            fn.argtypes = args
+        _lib = L
+    return _lib
+
+
+def check(rc):
+    """Non-zero return code -> ValueError (Unsupported for HJ_EUNSUPPORTED), as _ffi.check."""
+    if rc != 0:
+        msg = lib().hjq_last_error()
+        text = (msg or b"hj_query error").decode("utf-8", "replace") + " (code %d)" % rc
+        raise (_ffi.Unsupported if rc == -3 else ValueError)(text)
+
+
+def last_kernel():
+    return (lib().hjq_last_kernel() or b"").decode()
+
+
+def grid_descriptor(ndim, N, xmin, xlast, dx, bc, tz, dtype_name):
+    g = Grid()
+    g.ndim = int(ndim)
+    g.dtype = _ffi.F64 if dtype_name == "float64" else _ffi.F32
+    for d in range(MAX_DIM):
+        inside = d < ndim
+        g.N[d] = int(N[d]) if inside else 1
+        g.xmin[d] = float(xmin[d]) if inside else 0.0
+        g.xlast[d] = float(xlast[d]) if inside else 0.0
+        g.dx[d] = float(dx[d]) if inside else 1.0
+        g.bc[d] = int(bc[d]) if inside else 0
+        g.toward_zero[d] = int(tz[d]) if inside else 0
+    return g

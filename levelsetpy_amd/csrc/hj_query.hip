@@ -1,0 +1,515 @@
+// libhj_query.so (include/hj_query.h): value-function queries at states for gfx950.
+//   interp_points_kernel   V at states: one thread per (field, state)
+//   costate_points_kernel  grad V at states: 2^ndim lanes per (field, state), one corner node each; the 7-point stencils of
+//                          the corner go through hj_device.h's ghost_value and upwind<SCHEME> -- the solver's own source,
+//                          so a corner costate has the bits computeGradients gives that node
+//   project_minmax_kernel  min / max over a subset of axes, a thread or a wavefront per output node
+// The interpolation arithmetic is hji_solver._eval_point's, operation by operation (contraction off: `v += wt * val`
+// must stay a multiply and an add), so the fp64 results equal the host loop's bit for bit.
+#include <hip/hip_runtime.h>
+#include <cstdarg>
+#include <cstdio>
+#include <cmath>
+#include "hj_device.h"
+#include "../../include/hj_query.h"
+
+namespace hjq {
+
+static thread_local char g_err[512] = "";
+static thread_local const char* g_kernel = "";
+
+static int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
+    } while (0)
+
+constexpr int MAXD = HJ_MAX_DIM;
+
+// grid as the kernels see it (kernel argument: lives in SGPRs)
+struct QGrid {
+    int ndim;
+    int n[MAXD];
+    int per[MAXD];
+    long long stride[MAXD];
+    double xmin[MAXD], xlast[MAXD], dx[MAXD];
+};
+
+template <typename T> struct QStencil {
+    T km[MAXD];
+    T K[MAXD][hj::HJ_NK];
+};
+
+// cell index and weight of every axis; false when the state is outside an extrapolated axis (or not finite)
+__device__ __forceinline__ bool locate(const QGrid& G, const double* __restrict__ x, int* lo, double* w) {
+#pragma clang fp contract(off)
+    bool inside = true;
+    for (int d = 0; d < G.ndim; ++d) {
+        double xd = x[d];
+        const double vs0 = G.xmin[d], dx = G.dx[d];
+        const int n = G.n[d];
+        int i;
+        if (!(xd - xd == 0.0)) {          // NaN / inf state
+            inside = false;
+            xd = vs0;
+        }
+        if (G.per[d]) {
+            const double period = (double)n * dx;
+            double mod = fmod(xd - vs0, period);          // Python's %: the sign of the divisor
+            if (mod != 0.0) {
+                if (mod < 0.0) mod += period;
+            } else {
+                mod = 0.0;
+            }
+            xd = vs0 + mod;
+            i = (int)floor((xd - vs0) / dx);
+            if (i > n - 1) i = n - 1;
+        } else {
+            if (xd < vs0 || xd > G.xlast[d]) {
+                inside = false;
+                xd = vs0;
+            }
+            i = (int)floor((xd - vs0) / dx);
+            if (i > n - 2) i = n - 2;
+        }
+        if (i < 0) i = 0;
+        lo[d] = i;
+        w[d] = (xd - (vs0 + (double)i * dx)) / dx;
+    }
+    return inside;
+}
+
+// element offset and weight of corner `c`
+__device__ __forceinline__ double corner(const QGrid& G, const int* lo, const double* w, int c, long long& off) {
+#pragma clang fp contract(off)
+    double wt = 1.0;
+    off = 0;
+    for (int d = 0; d < G.ndim; ++d) {
+        const int up = (c >> d) & 1;
+        int j = lo[d] + up;
+        if (G.per[d] && j >= G.n[d]) j -= G.n[d];
+        off += (long long)j * G.stride[d];
+        wt *= up ? w[d] : (1.0 - w[d]);
+    }
+    return wt;
+}
+
+template <typename T>
+__device__ __forceinline__ void put(void* out, long long i, double v, int out_f64) {
+    if (out_f64) ((double*)out)[i] = v;
+    else ((T*)out)[i] = (T)v;
+}
+
+// ---- (a) V at states: thread t -> field t / M, state t % M
+template <typename T>
+__global__ __launch_bounds__(256) void interp_points_kernel(const T* __restrict__ data, long long field_stride, long long nfields,
+                                                            const double* __restrict__ xs, long long M, QGrid G,
+                                                            void* __restrict__ out, int out_f64) {
+#pragma clang fp contract(off)
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= nfields * M) return;
+    const long long f = t / M, m = t - f * M;
+    int lo[MAXD];
+    double w[MAXD];
+    double v;
+    if (!locate(G, xs + m * G.ndim, lo, w)) {
+        v = __builtin_nan("");
+    } else {
+        const T* __restrict__ field = data + f * field_stride;
+        v = 0.0;
+        for (int c = 0; c < (1 << G.ndim); ++c) {
+            long long off;
+            const double wt = corner(G, lo, w, c, off);
+            if (wt != 0.0) {
+                const double val = (double)field[off];
+                const double p = wt * val;
+                v = v + p;
+            }
+        }
+    }
+    put<T>(out, t, v, out_f64);
+}
+
+// ---- (b) grad V at states
+template <typename T> __device__ __forceinline__ bool finite(T v) { return v - v == T(0); }
+// computeGradients' replacement of NaN / +-inf by a large number before the differences
+template <typename T> __device__ __forceinline__ T ld_work(const T* p) {
+    const T v = *p;
+    return finite(v) ? v : T(1e6);
+}
+
+// the seven values phi[i-3 .. i+3] along one axis of the node at `pc0` (index i on that axis), ghosts as the solver's
+// gather_stencils (hj_split.h): wrap on a periodic axis, ghost_value from the edge node and its inner neighbour otherwise
+template <typename T>
+__device__ __forceinline__ void gather_axis(const T* pc0, long long s, int i, int n, bool per, T km, T centre, T* v) {
+    bool ghost = false;
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        if (k == 3) { v[k] = centre; continue; }
+        int j = i + k - 3;
+        if (j < 0) {
+            if (per) j += n; else { j = 0; ghost = true; }
+        } else if (j >= n) {
+            if (per) j -= n; else { j = n - 1; ghost = true; }
+        }
+        v[k] = ld_work(pc0 + (long long)(j - i) * s);
+    }
+    if (ghost) {
+        const T* line = pc0 - (long long)i * s;
+        if (i < HJ_STENCIL) {
+            const T e = ld_work(line), in = ld_work(line + s);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (i + k - 3 < 0) v[k] = hj::ghost_value(e, in, T(3 - k - i) * km);
+        }
+        if (i + HJ_STENCIL >= n) {
+            const T e = ld_work(line + (long long)(n - 1) * s), in = ld_work(line + (long long)(n - 2) * s);
+#pragma unroll
+            for (int k = 4; k < 7; ++k)
+                if (i + k - 3 >= n) v[k] = hj::ghost_value(e, in, T(i + k - 3 - n + 1) * km);
+        }
+    }
+}
+
+struct CostateOut {
+    void* costate;
+    void* derivL;
+    void* derivR;
+    void* value;
+    int out_f64;
+};
+
+// the group's first lane adds the corners' terms in ascending corner number (the order of interp_points_kernel)
+__device__ __forceinline__ double group_sum(double term, int used, int lanes) {
+#pragma clang fp contract(off)
+    double v = 0.0;
+    for (int c = 0; c < lanes; ++c) {
+        const double p = __shfl(term, c, lanes);
+        const int u = __shfl(used, c, lanes);
+        if (u) v = v + p;
+    }
+    return v;
+}
+
+template <typename T, int SCHEME>
+__global__ __launch_bounds__(256) void costate_points_kernel(const T* __restrict__ data, long long field_stride, long long nfields,
+                                                             const double* __restrict__ xs, long long M, QGrid G, QStencil<T> S,
+                                                             CostateOut O) {
+    const int lanes = 1 << G.ndim;                 // 2 .. 16: divides the wavefront, groups never straddle one
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long grp = t / lanes;
+    const int c = (int)(t - grp * lanes);
+    if (grp >= nfields * M) return;                // whole groups leave together
+    const long long f = grp / M, m = grp - f * M;
+    int lo[MAXD];
+    double w[MAXD];
+    const bool inside = locate(G, xs + m * G.ndim, lo, w);
+    long long off;
+    const double wt = corner(G, lo, w, c, off);
+    const int used = wt != 0.0;
+    T cC[MAXD], cL[MAXD], cR[MAXD];
+    T raw = T(0);
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) cC[d] = cL[d] = cR[d] = T(0);
+    if (inside && used) {
+        const T* pc0 = data + f * field_stride + off;
+        raw = *pc0;
+        if (!finite(raw)) {
+            // the node's own NaN / inf is put back after the differences (computeGradients: NaN stays NaN, +-inf becomes +inf)
+            const T back = raw != raw ? raw : T(__builtin_inf());
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) cC[d] = cL[d] = cR[d] = back;
+        } else {
+#pragma unroll
+            for (int d = 0; d < MAXD; ++d) {
+                if (d >= G.ndim) break;
+                int j = lo[d] + ((c >> d) & 1);
+                if (G.per[d] && j >= G.n[d]) j -= G.n[d];
+                T v[7];
+                gather_axis<T>(pc0, G.stride[d], j, G.n[d], G.per[d] != 0, S.km[d], raw, v);
+                T L, R;
+                hj::upwind<SCHEME, T>(v, S.K[d], T(0), L, R);
+                cL[d] = L;
+                cR[d] = R;
+                cC[d] = T(0.5) * (L + R);
+            }
+        }
+    }
+    const double nan = __builtin_nan("");
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) {
+        if (d >= G.ndim) break;
+        double p, q, r;
+        {
+#pragma clang fp contract(off)
+            p = wt * (double)cC[d];
+            q = wt * (double)cL[d];
+            r = wt * (double)cR[d];
+        }
+        const double sC = group_sum(p, used, lanes);
+        if (c == 0) put<T>(O.costate, grp * G.ndim + d, inside ? sC : nan, O.out_f64);
+        if (O.derivL) {
+            const double sL = group_sum(q, used, lanes);
+            if (c == 0) put<T>(O.derivL, grp * G.ndim + d, inside ? sL : nan, O.out_f64);
+        }
+        if (O.derivR) {
+            const double sR = group_sum(r, used, lanes);
+            if (c == 0) put<T>(O.derivR, grp * G.ndim + d, inside ? sR : nan, O.out_f64);
+        }
+    }
+    if (O.value) {
+        double p;
+        {
+#pragma clang fp contract(off)
+            p = wt * (double)raw;
+        }
+        const double sV = group_sum(p, used, lanes);
+        if (c == 0) put<T>(O.value, grp, inside ? sV : nan, O.out_f64);
+    }
+}
+
+// ---- (c) min / max over a subset of axes
+struct ProjArgs {
+    int nkeep, nrem;
+    int keep_n[MAXD], rem_n[MAXD];                  // sizes, in axis order (removed axes right-aligned, see the kernel)
+    long long keep_s[MAXD], rem_s[MAXD];            // strides in the input
+    long long nout;                                 // product of keep_n
+    long long field_stride, nfields;
+    int op;
+};
+
+// running min / max that remembers a NaN (np.amin / np.amax: any NaN in the set gives NaN)
+template <typename T> struct Red {
+    T v;
+    int nan;
+    __device__ __forceinline__ void take(T x, int op) {
+        if (x != x) nan = 1;
+        else if (op == HJQ_MIN ? x < v : x > v) v = x;
+    }
+};
+
+template <typename T>
+__device__ __forceinline__ long long proj_base(const ProjArgs& A, long long o) {
+    long long base = 0;
+    for (int k = A.nkeep - 1; k >= 0; --k) {
+        const long long q = o / A.keep_n[k];
+        base += (o - q * A.keep_n[k]) * A.keep_s[k];
+        o = q;
+    }
+    return base;
+}
+
+// WAVE = false: the last axis is kept -- one thread per output node, neighbouring threads read neighbouring elements.
+// WAVE = true:  the last axis is removed -- one wavefront per output node; its lanes stride the last axis (neighbouring
+//               lanes read neighbouring elements) inside loops over the other removed axes.
+// The removed axes sit at the END of rem_n / rem_s (unused leading slots have n = 1), so the loops need no index division.
+template <typename T, bool WAVE>
+__global__ __launch_bounds__(256) void project_minmax_kernel(const T* __restrict__ data, T* __restrict__ out, ProjArgs A) {
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long node = WAVE ? t / 64 : t;
+    const int lane = WAVE ? (int)(t & 63) : 0;
+    if (node >= A.nfields * A.nout) return;         // WAVE: whole wavefronts leave together
+    const long long f = node / A.nout, o = node - f * A.nout;
+    const T* __restrict__ p = data + f * A.field_stride + proj_base<T>(A, o);
+    const T start = A.op == HJQ_MIN ? T(__builtin_inf()) : -T(__builtin_inf());
+    Red<T> acc{start, 0};
+    static_assert(MAXD == 4, "three loops: at most MAXD - 1 removed axes");
+    for (int i0 = 0; i0 < A.rem_n[1]; ++i0)
+        for (int i1 = 0; i1 < A.rem_n[2]; ++i1) {
+            const T* __restrict__ row = p + i0 * A.rem_s[1] + i1 * A.rem_s[2];
+            for (int i2 = lane; i2 < A.rem_n[3]; i2 += WAVE ? 64 : 1) acc.take(row[i2 * A.rem_s[3]], A.op);
+        }
+    if (WAVE) {
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) {
+            const T ov = __shfl_xor(acc.v, s, 64);
+            const int on = __shfl_xor(acc.nan, s, 64);
+            acc.nan |= on;
+            acc.take(ov, A.op);
+        }
+        if (lane != 0) return;
+    }
+    out[node] = acc.nan ? T(__builtin_nan("")) : acc.v;
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
+    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
+    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    G.ndim = g->ndim;
+    total = 1;
+    for (int d = 0; d < MAXD; ++d) {
+        G.n[d] = 1; G.per[d] = 0; G.stride[d] = 0; G.xmin[d] = 0; G.xlast[d] = 0; G.dx[d] = 1;
+    }
+    for (int d = g->ndim - 1; d >= 0; --d) {
+        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
+            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
+        G.n[d] = (int)g->N[d];
+        G.per[d] = g->bc[d] == HJ_BC_PERIODIC;
+        G.stride[d] = total;
+        G.xmin[d] = g->xmin[d];
+        G.xlast[d] = g->xlast[d];
+        G.dx[d] = g->dx[d];
+        total *= g->N[d];
+    }
+    return HJ_OK;
+}
+
+static int check_points(const hjq_grid* g, const QGrid& G, long long total, const void* data, int64_t nfields, int64_t field_stride,
+                 const double* xs, int64_t nstates, bool costate) {
+    if (!data || !xs) return fail(HJ_EINVAL, "null argument");
+    if (nfields < 1 || nstates < 1) return fail(HJ_EINVAL, "nfields and nstates must be positive");
+    if (nfields > 1 && field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    for (int d = 0; d < G.ndim; ++d) {
+        // an extrapolated axis interpolates between nodes i and i+1 <= N-1; the stencils reach HJ_STENCIL nodes (hj_upwind's limit)
+        const int need = costate ? HJ_STENCIL : (G.per[d] ? 1 : 2);
+        if (G.n[d] < need) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], need);
+    }
+    return HJ_OK;
+}
+
+static int blocks_for(long long threads, unsigned& blocks) {
+    const long long b = (threads + 255) / 256;
+    if (b > 0x7fffffffll) return fail(HJ_EINVAL, "too many (field, state) pairs for one launch");
+    blocks = (unsigned)b;
+    return HJ_OK;
+}
+
+template <typename T>
+static int interp_launch(const QGrid& G, const void* data, int64_t nfields, int64_t field_stride, const double* xs, int64_t M,
+                  void* out, int out_f64, hipStream_t stream, const char* name) {
+    unsigned blocks;
+    int rc = blocks_for((long long)nfields * M, blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL((interp_points_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)data, (long long)field_stride,
+                       (long long)nfields, xs, (long long)M, G, out, out_f64);
+    HIP_TRY(hipGetLastError());
+    g_kernel = name;
+    return HJ_OK;
+}
+
+template <typename T, int SCHEME>
+static int costate_launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t nfields, int64_t field_stride, const double* xs,
+                   int64_t M, const CostateOut& O, hipStream_t stream, const char* name) {
+    QStencil<T> S;
+    for (int d = 0; d < MAXD; ++d) {
+        S.km[d] = (d < G.ndim && g->toward_zero[d]) ? T(-1) : T(1);
+        hj::fill_stencil_constants<T>(G.dx[d], S.K[d]);
+    }
+    unsigned blocks;
+    int rc = blocks_for((long long)nfields * M * (1ll << G.ndim), blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL((costate_points_kernel<T, SCHEME>), dim3(blocks), dim3(256), 0, stream, (const T*)data,
+                       (long long)field_stride, (long long)nfields, xs, (long long)M, G, S, O);
+    HIP_TRY(hipGetLastError());
+    g_kernel = name;
+    return HJ_OK;
+}
+
+template <typename T, bool WAVE>
+static int project_launch(const void* data, void* out, const ProjArgs& A, hipStream_t stream, const char* name) {
+    unsigned blocks;
+    int rc = blocks_for(A.nfields * A.nout * (WAVE ? 64 : 1), blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL((project_minmax_kernel<T, WAVE>), dim3(blocks), dim3(256), 0, stream, (const T*)data, (T*)out, A);
+    HIP_TRY(hipGetLastError());
+    g_kernel = name;
+    return HJ_OK;
+}
+
+}  // namespace hjq
+
+using namespace hjq;
+
+extern "C" {
+
+int hjq_interp_points(const hjq_grid* g, const void* data, int64_t nfields, int64_t field_stride, const double* xs,
+                      int64_t nstates, void* out, int out_f64, void* stream) {
+    QGrid G;
+    long long total;
+    int rc = make_grid(g, G, total);
+    if (rc) return rc;
+    if (!out) return fail(HJ_EINVAL, "null argument");
+    if ((rc = check_points(g, G, total, data, nfields, field_stride, xs, nstates, false))) return rc;
+    if (g->dtype == HJ_F64)
+        return interp_launch<double>(G, data, nfields, field_stride, xs, nstates, out, out_f64, (hipStream_t)stream, "interp_points_kernel<double>");
+    return interp_launch<float>(G, data, nfields, field_stride, xs, nstates, out, out_f64, (hipStream_t)stream, "interp_points_kernel<float>");
+}
+
+int hjq_costate_points(const hjq_grid* g, int scheme, const void* data, int64_t nfields, int64_t field_stride, const double* xs,
+                       int64_t nstates, void* costate, void* derivL, void* derivR, void* value, int out_f64, void* stream) {
+    QGrid G;
+    long long total;
+    int rc = make_grid(g, G, total);
+    if (rc) return rc;
+    if (!costate) return fail(HJ_EINVAL, "null argument");
+    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
+        return fail(HJ_EUNSUPPORTED, "scheme %d has no point kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
+    if ((rc = check_points(g, G, total, data, nfields, field_stride, xs, nstates, true))) return rc;
+    const CostateOut O{costate, derivL, derivR, value, out_f64};
+    hipStream_t s = (hipStream_t)stream;
+#define HJQ_COSTATE(T, SCH) return costate_launch<T, SCH>(g, G, data, nfields, field_stride, xs, nstates, O, s, "costate_points_kernel<" #T ", " #SCH ">")
+    if (g->dtype == HJ_F64) {
+        if (scheme == HJ_ENO2) HJQ_COSTATE(double, 0);
+        if (scheme == HJ_ENO3) HJQ_COSTATE(double, 1);
+        HJQ_COSTATE(double, 3);
+    }
+    if (scheme == HJ_ENO2) HJQ_COSTATE(float, 0);
+    if (scheme == HJ_ENO3) HJQ_COSTATE(float, 1);
+    HJQ_COSTATE(float, 3);
+#undef HJQ_COSTATE
+}
+
+int hjq_project_minmax(const hjq_grid* g, const void* data, int64_t nfields, int64_t field_stride, unsigned remove_mask, int op,
+                       void* out, void* stream) {
+    QGrid G;
+    long long total;
+    int rc = make_grid(g, G, total);
+    if (rc) return rc;
+    if (!data || !out) return fail(HJ_EINVAL, "null argument");
+    if (nfields < 1) return fail(HJ_EINVAL, "nfields must be positive");
+    if (nfields > 1 && field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    if (op != HJQ_MIN && op != HJQ_MAX) return fail(HJ_EINVAL, "unknown projection %d", op);
+    const unsigned all = (1u << G.ndim) - 1u;
+    if ((remove_mask & ~all) || remove_mask == 0 || remove_mask == all)
+        return fail(HJ_EINVAL, "remove_mask %#x must name a non-empty proper subset of the %d axes", remove_mask, G.ndim);
+    ProjArgs A;
+    A.nkeep = A.nrem = 0;
+    A.nout = 1;
+    for (int d = 0; d < MAXD; ++d) { A.keep_n[d] = A.rem_n[d] = 1; A.keep_s[d] = A.rem_s[d] = 0; }
+    for (int d = 0; d < G.ndim; ++d) {
+        if (remove_mask >> d & 1u) {
+            ++A.nrem;
+        } else {
+            A.keep_n[A.nkeep] = G.n[d]; A.keep_s[A.nkeep] = G.stride[d]; ++A.nkeep; A.nout *= G.n[d];
+        }
+    }
+    for (int d = G.ndim - 1, k = MAXD - 1; d >= 0; --d)          // removed axes right-aligned: the last one is the innermost loop
+        if (remove_mask >> d & 1u) { A.rem_n[k] = G.n[d]; A.rem_s[k] = G.stride[d]; --k; }
+    A.field_stride = field_stride;
+    A.nfields = nfields;
+    A.op = op;
+    const bool wave = remove_mask >> (G.ndim - 1) & 1u;
+    hipStream_t s = (hipStream_t)stream;
+    if (g->dtype == HJ_F64)
+        return wave ? project_launch<double, true>(data, out, A, s, "project_minmax_kernel<double, true>")
+                    : project_launch<double, false>(data, out, A, s, "project_minmax_kernel<double, false>");
+    return wave ? project_launch<float, true>(data, out, A, s, "project_minmax_kernel<float, true>")
+                : project_launch<float, false>(data, out, A, s, "project_minmax_kernel<float, false>");
+}
+
+const char* hjq_last_error(void) { return g_err; }
+const char* hjq_last_kernel(void) { return g_kernel; }
+
+}  // extern "C"

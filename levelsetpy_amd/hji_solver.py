@@ -76,10 +76,15 @@ class _Ops(object):
 def _eval_point(g, data, x):
     """eval_u(g, data, x) for ONE state (ValueFuncs/evaluate_u.py:15,64: multilinear interpolation,
     periodic axes augmented by one wrapped node and the state wrapped into the period).  `data` may
-    live on the GPU: only the 2^dim corner values are read.  Outside an extrapolated axis -> NaN."""
+    live on the GPU: it is then evaluated there by interp_points_kernel (query.py; one launch and one host
+    synchronisation, the same operations in the same order: the same bits).  Outside an extrapolated axis -> NaN."""
     x = np.asarray(x, dtype=np.float64).ravel()
     if x.size != g.dim:
         error('stopInit must be a vector of length g.dim!')
+    if is_tensor(data) and data.is_cuda and g.dim <= 4 and tuple(data.shape) == tuple(int(n) for n in np.asarray(g.N).ravel()):
+        from .query import interp_states, _device_data, _device_states
+        t = _device_data(data)
+        return float(interp_states(g, t, _device_states(x.reshape(1, -1), t.device), out_f64=True)[0, 0])
     bc, _ = grid_bc(g)
     N = [int(v) for v in np.asarray(g.N).ravel()]
     lo, w = [], []

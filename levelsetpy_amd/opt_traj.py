@@ -20,11 +20,25 @@ optimal trajectory (tests).  Visualisation (extraArgs.visualize) is outside the 
 """
 import numpy as np
 
+from .context import is_tensor
 from .gradients import computeGradients
 from .hji_solver import _eval_point
+from .query import interp_states, costate_states, _device_data, _device_states, _point_scheme
+from .spatial import upwindFirstWENO5
 from .utilities import isfield, error
 
 __all__ = ["computeOptTraj", "find_earliest_BRS_ind"]
+
+
+def _bisect(inside_at, upper, lower):
+    """The toolbox's bisection over `inside_at(index)`; the index it settles on, also for non-monotone data."""
+    while upper > lower:
+        mid = (upper + lower + 1) // 2
+        if inside_at(mid):
+            lower = mid            # inside: everything before mid is settled
+        else:
+            upper = mid - 1        # too late
+    return upper
 
 
 def find_earliest_BRS_ind(g, data, x, upper=None, lower=0):
@@ -32,16 +46,16 @@ def find_earliest_BRS_ind(g, data, x, upper=None, lower=0):
     time-first with the reachable sets SHRINKING along the time axis (the flipped output of HJIPDE_solve:
     index 0 = the full horizon, last index = the target itself); returns the largest index in [lower, upper]
     whose set still contains x (value < 1e-4), i.e. the earliest moment of the remaining horizon at which x is
-    inside.  `lower` if none does."""
+    inside.  `lower` if none does.  A device-resident table is evaluated at x in ALL its stored sets by one
+    launch of the interpolation kernel (query.py); the same bisection then runs on the host over those numbers."""
     upper = (data.shape[0] - 1) if upper is None else upper
     small = 1e-4
-    while upper > lower:
-        mid = (upper + lower + 1) // 2
-        if _eval_point(g, data[mid], x) < small:
-            lower = mid            # inside: everything before mid is settled
-        else:
-            upper = mid - 1        # too late
-    return upper
+    if is_tensor(data) and data.is_cuda and upper > lower:
+        t = _device_data(data)
+        xs = _device_states(np.asarray(x, dtype=np.float64).reshape(1, -1), t.device)
+        vals = interp_states(g, t, xs, out_f64=True)[:, 0].cpu().numpy()
+        return _bisect(lambda mid: vals[mid] < small, upper, lower)
+    return _bisect(lambda mid: _eval_point(g, data[mid], x) < small, upper, lower)
 
 
 def computeOptTraj(g, data, tau, dynSys, extraArgs=None):
@@ -64,10 +78,20 @@ def computeOptTraj(g, data, tau, dynSys, extraArgs=None):
         if tEarliest == tauLength - 1:
             break                                                            # the trajectory has entered the target (:114-116)
         BRS_at_t = data[tEarliest]                                           # :91
-        Deriv, _, _ = computeGradients(g, BRS_at_t)                          # :119
+        # the costate at the state (:119): the 2^dim corner stencils only, one launch per sub-sample (eval_costate's
+        # kernel); derivative functions it does not cover go through computeGradients as before
+        sid = _point_scheme(upwindFirstWENO5)
+        if sid is not None:
+            onDevice = _device_data(BRS_at_t)                                # a NumPy table: this set goes over once per step
+        else:
+            Deriv, _, _ = computeGradients(g, BRS_at_t)
         for _ in range(subSamples):                                          # :121-131
             x = np.asarray(dynSys.x, dtype=np.float64).ravel()
-            deriv = [_eval_point(g, Deriv[d], x) for d in range(g.dim)]
+            if sid is not None:
+                xs = _device_states(x.reshape(1, -1), onDevice.device)
+                deriv = costate_states(g, onDevice, xs, sid, out_f64=True)[0][0, 0].cpu().numpy().tolist()
+            else:
+                deriv = [_eval_point(g, Deriv[d], x) for d in range(g.dim)]
             u = dynSys.get_opt_u(tau[tEarliest], deriv, uMode, x)
             d = dynSys.get_opt_v(tau[tEarliest], deriv, dMode, x) if hasattr(dynSys, 'get_opt_v') else None
             xt = dynSys.update_state(u, dtSmall, x, d)

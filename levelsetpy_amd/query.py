@@ -1,0 +1,444 @@
+"""Value-function queries on the device: eval_u, eval_costate, proj, augmentPeriodicData (reference
+ValueFuncs/evaluate_u.py:15, data_proj.py:18, augment_periodic.py:12) -- what a caller does with the result of
+HJIPDE_solve: V(x) and grad V(x) at many states, projections and slices.
+
+All of it runs in libhj_query.so (include/hj_query.h): `interp_points_kernel` (V at states),
+`costate_points_kernel` (grad V at states from the solver's own upwind source, without full-grid derivative
+arrays) and `project_minmax_kernel`.  NumPy in -> NumPy out (fp64); a device tensor or HostView in -> a tensor
+on the same device, in the data's dtype.  Stored value functions with a time axis are time FIRST, as
+everywhere in this package.
+
+Parity.  The reference's eval_u returns `v.take(0)` -- ONE value whatever the number of states --, raises on
+every grid with a periodic axis >= 1 (augmentPeriodicData indexes `data[i, ...]`), and raises "out of bounds"
+for states beyond the last node of a periodic axis 0; its proj raises for 'min', 'max' and slices alike.
+Pinned to the reference (tests/golden/query.npz): eval_u of single in-domain states on non-periodic grids and
+on grids periodic in axis 0.  UNPINNED, checked against the NumPy restatement tests/query_ref.py: many states,
+every other periodic case, eval_costate, proj, augmentPeriodicData (the intended helperOC semantics).
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi, _qffi
+from .context import grid_bc, is_tensor, require_gpu, _raw_stream_getter
+from .lazy import HostView, DeviceArray
+from .utilities import Bundle, error, warn
+
+__all__ = ["eval_u", "eval_costate", "proj", "augmentPeriodicData"]
+
+
+# ------------------------------------------------------------------------------------------ marshalling
+def _grid_numbers(g):
+    N = [int(v) for v in np.asarray(g.N).ravel()]
+    dx = [float(v) for v in np.asarray(g.dx).ravel()]
+    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
+    bc, tz = grid_bc(g)
+    return N, dx, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], bc, tz
+
+
+def _descriptor(g, dtype_name):
+    N, dx, x0, x1, bc, tz = _grid_numbers(g)
+    if g.dim > _qffi.MAX_DIM:
+        error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
+    return _qffi.grid_descriptor(g.dim, N, x0, x1, dx, bc, tz, dtype_name), tuple(N)
+
+
+def _unlazy(a):
+    if isinstance(a, HostView):
+        return a.device_tensor() if a.device_tensor() is not None else a.__array__()
+    if isinstance(a, DeviceArray) and a.device_tensor() is not None:
+        return a.device_tensor()
+    return a
+
+
+def _wants_tensor(a):
+    """NumPy in -> NumPy out; a device tensor or a HostView in -> a tensor out."""
+    return is_tensor(a) or isinstance(a, HostView)
+
+
+def _from_numpy(torch, a):
+    arr = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
+    return torch.from_numpy(arr if arr.flags.writeable else arr.copy())
+
+
+def _device_data(a):
+    """-> contiguous fp64 / fp32 tensor on the GPU (NumPy and other dtypes: fp64, as the reference path)."""
+    torch = require_gpu()
+    a = _unlazy(a)
+    if is_tensor(a):
+        t = a if a.is_cuda else a.to("cuda")
+        if t.dtype not in (torch.float64, torch.float32):
+            t = t.to(torch.float64)
+        return t.contiguous()               # never read a view with the strides of its base
+    return _from_numpy(torch, a).to("cuda")
+
+
+def _device_states(xs, device):
+    torch = require_gpu()
+    xs = _unlazy(xs)
+    if is_tensor(xs):
+        return xs.detach().to(device=device, dtype=torch.float64).contiguous()
+    return _from_numpy(torch, xs).to(device)
+
+
+def _stream(torch, device):
+    return C.c_void_p(_raw_stream_getter(torch)(device.index))
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _fields(t, N):
+    """(nfields, field_stride) of a contiguous tensor holding one grid array or a stack of them (time first)."""
+    total = int(np.prod(N))
+    shape = tuple(int(v) for v in t.shape)
+    if shape == tuple(N) or shape == tuple(N) + (1,):
+        return 1, total
+    if len(shape) == len(N) + 1 and shape[1:] == tuple(N) and shape[0] >= 1:
+        return shape[0], total
+    error('data parameter does not agree in array size with grid')
+
+
+def interp_states(g, data, xs, out_f64=False):
+    """V at states for one array or a stack on grid g: device tensors in, a (F, M) tensor out (F = 1 for one array).
+    `xs` is an (M, dim) fp64 device tensor.  out_f64: the unrounded fp64 sum whatever the data's dtype."""
+    torch = require_gpu()
+    dname = "float32" if data.dtype == torch.float32 else "float64"
+    desc, N = _descriptor(g, dname)
+    F, stride = _fields(data, N)
+    if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
+        error('states must be an (M, %d) array' % g.dim)
+    M = int(xs.shape[0])
+    out = torch.empty((F, M), dtype=torch.float64 if out_f64 else data.dtype, device=data.device)
+    with torch.cuda.device(data.device):
+        _qffi.check(_qffi.lib().hjq_interp_points(C.byref(desc), _ptr(data), F, stride, _ptr(xs), M, _ptr(out),
+                                                  int(bool(out_f64)), _stream(torch, data.device)))
+    return out
+
+
+def costate_states(g, data, xs, scheme, out_f64=False, want_lr=False, want_value=False):
+    """grad V at states: (F, M, dim) costates [, derivL, derivR (same shape), V (F, M)] from hjq_costate_points."""
+    torch = require_gpu()
+    dname = "float32" if data.dtype == torch.float32 else "float64"
+    desc, N = _descriptor(g, dname)
+    F, stride = _fields(data, N)
+    if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
+        error('states must be an (M, %d) array' % g.dim)
+    M = int(xs.shape[0])
+    odt = torch.float64 if out_f64 else data.dtype
+    mk = lambda *s: torch.empty(s, dtype=odt, device=data.device)       # noqa: E731
+    cs = mk(F, M, g.dim)
+    dl, dr = (mk(F, M, g.dim), mk(F, M, g.dim)) if want_lr else (None, None)
+    val = mk(F, M) if want_value else None
+    with torch.cuda.device(data.device):
+        _qffi.check(_qffi.lib().hjq_costate_points(C.byref(desc), int(scheme), _ptr(data), F, stride, _ptr(xs), M,
+                                                   _ptr(cs), _ptr(dl), _ptr(dr), _ptr(val), int(bool(out_f64)),
+                                                   _stream(torch, data.device)))
+    return cs, dl, dr, val
+
+
+def _give(t, proto, squeeze0=False):
+    """The result in the array type of `proto`."""
+    if squeeze0:
+        t = t[0]
+    if _wants_tensor(proto):
+        p = _unlazy(proto)
+        return t if (not is_tensor(p) or p.is_cuda) else t.to(p.device)
+    return t.detach().cpu().numpy()
+
+
+def _states_2d(g, xs):
+    """States as rows: a vector is one state; a matrix whose column count is not g.dim is transposed (evaluate_u.py:83).
+    Works on a copy -- the caller's array is never modified (the reference wraps it in place)."""
+    xs = _unlazy(xs)
+    nd = xs.dim() if is_tensor(xs) else np.ndim(xs)
+    if not is_tensor(xs):
+        xs = np.asarray(xs, dtype=np.float64)
+    if nd == 1:
+        xs = xs.reshape(1, -1)
+    elif nd != 2:
+        error('states must be a vector or a matrix with one state per row')
+    if xs.shape[1] != g.dim:
+        xs = xs.T
+    if xs.shape[1] != g.dim:
+        error('states must have g.dim = %d columns' % g.dim)
+    return xs
+
+
+def _is_single_state(g, xs):
+    xs = _unlazy(xs)
+    shape = tuple(xs.shape) if hasattr(xs, "shape") else np.shape(np.asarray(xs, dtype=np.float64))
+    return len(shape) == 1 or (len(shape) == 2 and 1 in shape and int(np.prod(shape)) == g.dim)
+
+
+def _ndim(a):
+    a = _unlazy(a)
+    return a.dim() if is_tensor(a) else np.ndim(a)
+
+
+# ------------------------------------------------------------------------------------------ eval_u
+def _eval_single(g, data, xs):
+    """One grid; one array (-> (M,)) or a time-first stack (-> (T, M))."""
+    nd = _ndim(data)
+    gd = len(np.asarray(g.N).ravel())
+    if nd not in (gd, gd + 1):
+        error('Dimensions of input data and grid don\'t match!')
+    t = _device_data(data)
+    x = _device_states(_states_2d(g, xs), t.device)
+    out = interp_states(g, t, x)
+    if nd == gd + 1 and _is_single_state(g, xs):
+        return _give(out[:, 0], data)                   # option 2: one value per array
+    return _give(out, data, squeeze0=(nd == gd))
+
+
+def eval_u(gs, datas, xs, interp_method='linear'):
+    """evaluate_u.py:15: the multilinear interpolant of value function(s) at state(s).
+
+      1. one grid, one array, many states (one per row)           -> ALL M values, shape (M,)
+      2. one grid, a list or a time-first stack of arrays, one state -> one value per array, shape (T,)
+      3. lists of grids, arrays and states of equal length        -> one result per triple
+
+    A time-first stack with many states gives (T, M).  Periodic axes wrap the state into the period (any number of
+    periods away); a state outside an extrapolated axis gives NaN.  `xs` is transposed when its column count is not
+    g.dim, as the reference does.
+
+    Deviations from the shipped reference: its option 1 returns `v.take(0)`, the value at the FIRST state only --
+    a defect, all M values are returned here; it modifies the caller's `xs` and grid in place -- neither is touched
+    here; it raises on periodic axes >= 1 and past the last node of a periodic axis 0 (module docstring)."""
+    if interp_method != 'linear':
+        error('interp_method %r is not implemented: only \'linear\'' % (interp_method,))
+    if isinstance(gs, Bundle) and not isinstance(datas, (list, tuple)):
+        if not (is_tensor(_unlazy(xs)) or isinstance(xs, (np.ndarray, list, tuple))):
+            error('Unrecognized combination of input data types!')
+        return _eval_single(gs, datas, xs)                                     # options 1 and 2 (stack)
+    if isinstance(gs, Bundle) and isinstance(datas, (list, tuple)):
+        if not _is_single_state(gs, xs):                                       # option 2 wants ONE state
+            error('Unrecognized combination of input data types!')
+        if len(datas) == 0:
+            error('datas is empty')
+        vals = [_eval_single(gs, d, xs) for d in datas]
+        return _stack(vals, datas[0], flat=True)
+    if isinstance(gs, (list, tuple)) and isinstance(datas, (list, tuple)) and isinstance(xs, (list, tuple)):
+        if not (len(gs) == len(datas) == len(xs)) or len(gs) == 0:
+            error('the numbers of grids, value functions and states must be equal')
+        vals = [_eval_single(gi, di, xi) for gi, di, xi in zip(gs, datas, xs)]
+        return _stack(vals, datas[0], flat=all(_is_single_state(gi, xi) for gi, xi in zip(gs, xs)))
+    error('Unrecognized combination of input data types!')
+
+
+def _stack(vals, proto, flat):
+    if _wants_tensor(proto):
+        torch = require_gpu()
+        if flat:
+            return torch.cat([v.reshape(-1) for v in vals])
+        return torch.stack(vals) if len(set(tuple(v.shape) for v in vals)) == 1 else vals
+    if flat:
+        return np.concatenate([np.asarray(v).reshape(-1) for v in vals])
+    return np.stack(vals) if len(set(np.shape(v) for v in vals)) == 1 else vals
+
+
+# ------------------------------------------------------------------------------------------ eval_costate
+def _point_scheme(derivFunc):
+    """Scheme id for hjq_costate_points, or None when the derivative function has no point kernel: a foreign
+    function, or the intended WENO5 (its epsilon is a reduction over the whole grid)."""
+    from .spatial import scheme_id_of
+    sid = scheme_id_of(derivFunc)
+    if sid is None:
+        return None
+    sid = {4: _ffi.ENO2, 5: _ffi.ENO3}.get(sid, sid)      # the 'fast' ENO modes: hj_upwind computes the base scheme for them too
+    return sid if sid in _qffi.POINT_SCHEMES else None
+
+
+def eval_costate(g, data, xs, derivFunc=None, dims=None):
+    """grad V at states: an (M, g.dim) array, (T, M, g.dim) for a time-first stack.
+
+    Equal, bit for bit, to eval_u applied to computeGradients' derivC arrays of the same data -- the corner nodes'
+    upwind derivatives come from the same source (hj_device.h upwind<>), 0.5 (L + R) and the interpolation are the
+    same operations -- but only the 2^dim corner stencils of each state are read, and no full-grid array is written.
+    derivFunc defaults to upwindFirstWENO5, dims (a mask) to every dimension, as computeGradients; columns of
+    dimensions left out hold NaN.  upwindFirstENO2 / ENO3 / WENO5 (as shipped) run in costate_points_kernel; the
+    intended WENO5 and foreign derivative functions take computeGradients and then the interpolation kernel.
+    Non-finite data as computeGradients: a NaN / inf node counts as 1e6 in its neighbours' stencils and contributes
+    NaN / inf itself.  Parity UNPINNED (the reference has no such function)."""
+    from .spatial import upwindFirstWENO5
+    if dims is None or (not is_tensor(dims) and not np.any(dims)):
+        dims = np.ones(g.dim, dtype=bool)
+    dims = np.asarray(dims).astype(bool).ravel()
+    if dims.size != g.dim:
+        error('dims must have one entry per grid dimension')
+    if derivFunc is None:
+        derivFunc = upwindFirstWENO5
+    nd = _ndim(data)
+    if nd not in (g.dim, g.dim + 1):
+        error('Dimensions of input data and grid don\'t match!')
+    sid = _point_scheme(derivFunc)
+    if sid is not None:
+        t = _device_data(data)
+        x = _device_states(_states_2d(g, xs), t.device)
+        cs = costate_states(g, t, x, sid)[0]
+    else:
+        cs = _costate_fallback(g, data, xs, derivFunc, dims)
+    if not dims.all():
+        cs[..., np.nonzero(~dims)[0].tolist()] = float('nan')
+    return _give(cs, data, squeeze0=(nd == g.dim))
+
+
+def _costate_fallback(g, data, xs, derivFunc, dims, out_f64=False):
+    """computeGradients, then the interpolation kernel on its arrays -> (F, M, dim) tensor."""
+    from .gradients import computeGradients
+    torch = require_gpu()
+    derivC, _, _ = computeGradients(g, _unlazy(data), dims, derivFunc)
+    cols, x = [], None
+    for d in range(g.dim):
+        if not dims[d]:
+            cols.append(None)
+            continue
+        t = _device_data(derivC[d])
+        if x is None:
+            x = _device_states(_states_2d(g, xs), t.device)
+        cols.append(interp_states(g, t, x, out_f64))
+    first = next(c for c in cols if c is not None)
+    cols = [torch.full_like(first, float('nan')) if c is None else c for c in cols]
+    return torch.stack(cols, dim=-1)
+
+
+# ------------------------------------------------------------------------------------------ proj
+def augmentPeriodicData(g, data):
+    """augment_periodic.py:12 with the semantics it was ported from (helperOC augmentPeriodicData.m): every periodic
+    axis gains one node, vs[-1] + dx, that holds the data of index 0 ALONG THAT AXIS (the shipped reference takes
+    `data[i, ...]`, plane i of axis 0, and raises for i >= 1).  Returns (gOut, dataOut) on copies: the caller's grid
+    and array are not modified.  A time-first stack is augmented along its grid axes.  Parity UNPINNED."""
+    bc, _ = grid_bc(g)
+    gOut = Bundle(dict((k, v) for k, v in g.__dict__.items() if not k.startswith("_hj")))
+    gOut.vs = [np.array(v, dtype=np.float64) for v in g.vs]
+    data = _unlazy(data)
+    lead = _ndim(data) - g.dim
+    if lead not in (0, 1):
+        error('Dimensions of input data and grid don\'t match!')
+    out = data.clone() if is_tensor(data) else np.array(data)
+    dx = np.asarray(g.dx, dtype=np.float64).ravel()
+    for i in range(g.dim):
+        if bc[i] != _ffi.BC_PERIODIC:
+            continue
+        v = gOut.vs[i]
+        gOut.vs[i] = np.concatenate((v, np.reshape(v.ravel()[-1] + dx[i], (1,) * v.ndim)), 0)
+        if is_tensor(out):
+            torch = require_gpu()
+            out = torch.cat((out, out.narrow(lead + i, 0, 1)), lead + i)
+        else:
+            out = np.concatenate((out, np.take(out, [0], axis=lead + i)), lead + i)
+    return gOut, out
+
+
+def _kept_grid(g, keep, N, process):
+    """gOut as data_proj.py:136-150 builds it: min / max / bdry of the kept axes, N, processGrid when asked."""
+    from .grids import processGrid
+    gmin, gmax = np.asarray(g.min, dtype=np.float64).reshape(-1, 1), np.asarray(g.max, dtype=np.float64).reshape(-1, 1)
+    gOut = Bundle(dict(dim=len(keep), min=gmin[keep], max=gmax[keep]))
+    gOut.bdry = [g.bdry[i] for i in keep]
+    if hasattr(g, "bdryData") and g.bdryData is not None:
+        gOut.bdryData = [g.bdryData[i] for i in keep]
+    gOut.N = np.asarray(N, dtype=np.int64).reshape(-1, 1)
+    return processGrid(gOut) if process else gOut
+
+
+def proj(g, data, dimsToRemove, xs=None, NOut=None, process=True):
+    """data_proj.py:18: (gOut, dataOut) = the data on the grid of the axes NOT marked in dimsToRemove.
+
+      xs None / 'min' / 'max'   union / intersection over the removed axes (project_minmax_kernel)
+      xs a vector               the slice at that point of the removed axes, multilinear, periodic removed axes wrapped
+                                (interp_points_kernel at the kept axes' nodes x the fixed coordinates)
+      NOut                      nodes of the output grid when they differ from the kept axes' N: the result is
+                                resampled onto gOut's nodes through the interpolation kernel
+
+    `data` may carry a time axis, time FIRST (the result is then (T,) + gOut.shape), or be a list of arrays.  gOut is
+    built as the reference builds it.  Keeping every dimension returns the inputs with a warning.  The shipped
+    reference raises for every kind of projection: parity UNPINNED, checked against tests/query_ref.py."""
+    rem = np.asarray(_unlazy(dimsToRemove) if not is_tensor(dimsToRemove) else dimsToRemove.cpu().numpy()).astype(bool).ravel()
+    if rem.size != g.dim:
+        error('Dimensions are inconsistent!')
+    if not rem.any():
+        warn('Input and output dimensions are the same!')
+        return g, data
+    if rem.all():
+        error('proj cannot remove every dimension')
+    if xs is None:
+        xs = 'min'
+    if isinstance(xs, str):
+        if xs not in ('min', 'max'):
+            error('xs must be a vector, \'min\', or \'max\'!')
+    else:
+        xs = np.asarray(_unlazy(xs).cpu().numpy() if is_tensor(_unlazy(xs)) else xs, dtype=np.float64).ravel()
+        if xs.size != int(rem.sum()):
+            error('Dimension of xs and dims do not match!')
+    if isinstance(data, (list, tuple)):
+        if len(data) == 0:
+            error('Inconsistent input data dimensions!')
+        proto = data[0]
+        if _wants_tensor(proto):
+            data = require_gpu().stack([_device_data(d) for d in data])
+        else:
+            data = np.stack([np.asarray(d, dtype=np.float64) for d in data])
+    else:
+        proto = data
+    nd = _ndim(data)
+    if nd not in (g.dim, g.dim + 1):
+        error('Inconsistent input data dimensions!')
+    keep = [i for i in range(g.dim) if not rem[i]]
+    gone = [i for i in range(g.dim) if rem[i]]
+    Nall = [int(v) for v in np.asarray(g.N).ravel()]
+    Nkeep = [Nall[i] for i in keep]
+    if NOut is None:
+        Nout = list(Nkeep)
+    else:
+        Nout = [int(v) for v in np.asarray(NOut).ravel()]
+        if len(Nout) == 1:
+            Nout = Nout * len(keep)
+        if len(Nout) != len(keep) or min(Nout) < 1:
+            error('NOut must be a scalar or have one entry per kept dimension')
+    gOut = _kept_grid(g, keep, Nout, process)
+    torch = require_gpu()
+    t = _device_data(data)
+    dname = "float32" if t.dtype == torch.float32 else "float64"
+    desc, N = _descriptor(g, dname)
+    F, stride = _fields(t, N)
+    resample = Nout != Nkeep
+    if isinstance(xs, str):
+        out = torch.empty((F,) + tuple(Nkeep), dtype=t.dtype, device=t.device)
+        mask = sum(1 << i for i in gone)
+        with torch.cuda.device(t.device):
+            _qffi.check(_qffi.lib().hjq_project_minmax(C.byref(desc), _ptr(t), F, stride, mask,
+                                                       _qffi.OP_MIN if xs == 'min' else _qffi.OP_MAX, _ptr(out),
+                                                       _stream(torch, t.device)))
+        if resample:
+            gK = _kept_grid(g, keep, Nkeep, True)
+            out = interp_states(gK, out, _device_states(_node_states(gK, gOut, range(len(keep)), [], []), t.device))
+            out = out.reshape((F,) + tuple(Nout))
+    else:
+        pts = _node_states(g, gOut if resample else None, keep, gone, xs)
+        out = interp_states(g, t, _device_states(pts, t.device)).reshape((F,) + tuple(Nout))
+    return gOut, _give(out, proto, squeeze0=(nd == g.dim))
+
+
+def _nodes(gOut, k):
+    """Nodes of axis k of an output grid (processGrid's linspace, :204, also when the grid was not processed)."""
+    if hasattr(gOut, "vs"):
+        return np.asarray(gOut.vs[k], dtype=np.float64).ravel()
+    return np.linspace(float(np.asarray(gOut.min).ravel()[k]), float(np.asarray(gOut.max).ravel()[k]),
+                       num=int(np.asarray(gOut.N).ravel()[k]))
+
+
+def _node_states(g, gOut, keep, gone, fixed):
+    """(M, g.dim) states: the nodes of the kept axes (gOut's when resampling, else g's own) in C order x the fixed
+    coordinates of the removed axes."""
+    axes = [(_nodes(gOut, k) if gOut is not None else np.asarray(g.vs[i], dtype=np.float64).ravel())
+            for k, i in enumerate(keep)]
+    mesh = np.meshgrid(*axes, indexing='ij') if axes else []
+    M = int(np.prod([a.size for a in axes])) if axes else 1
+    pts = np.empty((M, g.dim), dtype=np.float64)
+    for k, i in enumerate(keep):
+        pts[:, i] = mesh[k].ravel()
+    for k, i in enumerate(gone):
+        pts[:, i] = fixed[k]
+    return pts
