@@ -23,6 +23,9 @@ from . import _ffi, _qffi
 from .context import grid_bc, is_tensor, require_gpu, _raw_stream_getter
 from .lazy import HostView, DeviceArray
 from .utilities import Bundle, error, warn
+from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, from_numpy as _from_numpy,      # noqa: F401
+                       device_data as _device_data, device_states as _device_states, stream as _stream, ptr as _ptr,
+                       fields as _fields)
 
 __all__ = ["eval_u", "eval_costate", "proj", "augmentPeriodicData"]
 
@@ -41,63 +44,6 @@ def _descriptor(g, dtype_name):
     if g.dim > _qffi.MAX_DIM:
         error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
     return _qffi.grid_descriptor(g.dim, N, x0, x1, dx, bc, tz, dtype_name), tuple(N)
-
-
-def _unlazy(a):
-    if isinstance(a, HostView):
-        return a.device_tensor() if a.device_tensor() is not None else a.__array__()
-    if isinstance(a, DeviceArray) and a.device_tensor() is not None:
-        return a.device_tensor()
-    return a
-
-
-def _wants_tensor(a):
-    """NumPy in -> NumPy out; a device tensor or a HostView in -> a tensor out."""
-    return is_tensor(a) or isinstance(a, HostView)
-
-
-def _from_numpy(torch, a):
-    arr = np.ascontiguousarray(np.asarray(a), dtype=np.float64)
-    return torch.from_numpy(arr if arr.flags.writeable else arr.copy())
-
-
-def _device_data(a):
-    """-> contiguous fp64 / fp32 tensor on the GPU (NumPy and other dtypes: fp64, as the reference path)."""
-    torch = require_gpu()
-    a = _unlazy(a)
-    if is_tensor(a):
-        t = a if a.is_cuda else a.to("cuda")
-        if t.dtype not in (torch.float64, torch.float32):
-            t = t.to(torch.float64)
-        return t.contiguous()               # never read a view with the strides of its base
-    return _from_numpy(torch, a).to("cuda")
-
-
-def _device_states(xs, device):
-    torch = require_gpu()
-    xs = _unlazy(xs)
-    if is_tensor(xs):
-        return xs.detach().to(device=device, dtype=torch.float64).contiguous()
-    return _from_numpy(torch, xs).to(device)
-
-
-def _stream(torch, device):
-    return C.c_void_p(_raw_stream_getter(torch)(device.index))
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _fields(t, N):
-    """(nfields, field_stride) of a contiguous tensor holding one grid array or a stack of them (time first)."""
-    total = int(np.prod(N))
-    shape = tuple(int(v) for v in t.shape)
-    if shape == tuple(N) or shape == tuple(N) + (1,):
-        return 1, total
-    if len(shape) == len(N) + 1 and shape[1:] == tuple(N) and shape[0] >= 1:
-        return shape[0], total
-    error('data parameter does not agree in array size with grid')
 
 
 def interp_states(g, data, xs, out_f64=False):
