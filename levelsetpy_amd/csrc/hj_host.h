@@ -198,7 +198,7 @@ struct hj_ctx {
     unsigned long long coop_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, coop_all = 0;      // what they read once every launch issued so far has run
     int coop_ok = -1;                               // device attribute hipDeviceAttributeCooperativeLaunch (-1: not asked yet)
     int xp_max_planes = 0;                          // HJ_XP_MAX_PLANES: auto mode takes windows of at most this many planes (0: the built-in rule)
-    // Auto mode, per (scheme, plane range): the launch form.  `prior` is what the two launch PLANS say (launch_scheme's cost model; all a dry
+    // Auto mode, per (scheme, plane range): the launch form.  `prior` is what the two launch PLANS say (hj_inst.hip, xp_prior's cost model; all a dry
     // context has); a live context then TIMES both forms on its first calls -- same bits either way: runs of XP_RUN consecutive calls of one
     // form (two RK3 steps: every stage kind, and the cache state that form leaves for itself) between a pair of events, the forms taking
     // turns, each run read back without waiting at a later call of the key; after HJ_XP_TRIALS runs of each the faster form (minimum against
@@ -233,7 +233,7 @@ struct hj_ctx {
     // to launch -- since the record was last read.  Run-time (hipRTC) kernels are no library symbols and are left out.
     bool rec_on = false;
     std::set<const void*> rec;
-    // (dry == 2 is a planning look from a live context, hj_inst.hip launch_scheme: nothing it visits is launched)
+    // (dry == 2 is a planning look from a live context, hj_inst.hip PlanLook: nothing it visits is launched)
     template <typename K> void note_kernel(K kern) { if (rec_on && dry != 2) rec.insert(reinterpret_cast<const void*>(kern)); }
 };
 

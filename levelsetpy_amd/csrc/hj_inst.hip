@@ -1,7 +1,6 @@
 // The fused / direct RK-substep kernels of ONE (dtype, Hamiltonian) pair and their launch code.
 // Compiled once per pair with -DHJ_INST_T=<double|float> -DHJ_INST_HAM=<HamDubinsRel|...> (Makefile), so
 // the kernel instantiations build in parallel.  gfx950 only.
-#include <mutex>
 #include "hj_host.h"
 #include "hj_fused.h"
 #include "hj_fused12.h"
@@ -31,38 +30,20 @@ auto tiled_kernel() {
 template <typename T, typename HAM, int SCHEME, int NT, int R, int KH, int OCC, int PD, int MODE, bool PAIR = false>
 int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
     constexpr int ND = HAM::ND;
+    auto kern = tiled_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PD, MODE, PAIR>();
+    const int occ_blocks = wg_per_cu(c, reinterpret_cast<const void*>(kern), NT, t.lds_bytes, OCC);
     EdgePlan ep;
     {
-        auto kern0 = tiled_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PD, MODE, PAIR>();
-        const auto key = std::make_pair(reinterpret_cast<const void*>(kern0), t.lds_bytes);
-        auto it = c->occ_cache.find(key);
-        int occ_blocks = it != c->occ_cache.end() ? it->second : 0;
-        if (it == c->occ_cache.end()) {
-            // (planning without a device -- or a planning look from a live context, c->dry == 2, which must not cache its estimate: the launch
-            //  bound's waves per SIMD, and the CU's 160 KB of LDS)
-            if (c->dry) occ_blocks = std::max(1, std::min(OCC * 256 / NT, (int)((size_t)(160 * 1024) / std::max<size_t>(1, t.lds_bytes))));
-            else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_blocks, key.first, NT, t.lds_bytes) != hipSuccess || occ_blocks < 1) occ_blocks = 1;
-            if (c->dry != 2) c->occ_cache.emplace(key, occ_blocks);
-        }
-        {
-            const int rc_plan = plan_chunks(c, s, t, occ_blocks, ep);
-            if (rc_plan) return rc_plan;
-        }
-        c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
-        c->last_plan.wg_per_cu = occ_blocks; c->last_plan.lds_bytes = t.lds_bytes;
-        if (c->dry) {
-            c->last_kernel = PAIR ? "fused_pair_kernel" : "fused_substep_kernel";
-            c->note_kernel(kern0);
-            c->last_E[0] = t.chunk;
-            for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
-            return HJ_OK;
-        }
-        if (c->debug) {
-            fprintf(stderr, "[hj] %stiling NT=%d R=%d KH=%d PD=%d OCC=%d E=(%d,%d,%d) pitch=%d ntiles=%d chunk=%d nchunks=%d blocks=%d wg/CU=%d lds=%zu score=%.3f\n",
-                    PAIR ? "pair " : "", NT, R, KH, PD, OCC, t.E[1], c->ndim > 2 ? t.E[2] : 0, c->ndim > 3 ? t.E[3] : 0, t.lpitch, t.ntiles, t.chunk,
-                    t.nchunks, t.nblocks, occ_blocks, t.lds_bytes, t.score);
-            c->debug = 0;
-        }
+        const int rc_plan = plan_chunks(c, s, t, occ_blocks, ep);
+        if (rc_plan) return rc_plan;
+    }
+    record_plan(c, t, NT, occ_blocks, PAIR ? "fused_pair_kernel" : "fused_substep_kernel", reinterpret_cast<const void*>(kern), ND);
+    if (c->dry) return HJ_OK;
+    if (c->debug) {
+        fprintf(stderr, "[hj] %stiling NT=%d R=%d KH=%d PD=%d OCC=%d E=(%d,%d,%d) pitch=%d ntiles=%d chunk=%d nchunks=%d blocks=%d wg/CU=%d lds=%zu score=%.3f\n",
+                PAIR ? "pair " : "", NT, R, KH, PD, OCC, t.E[1], c->ndim > 2 ? t.E[2] : 0, c->ndim > 3 ? t.E[3] : 0, t.lpitch, t.ntiles, t.chunk,
+                t.nchunks, t.nblocks, occ_blocks, t.lds_bytes, t.score);
+        c->debug = 0;
     }
     if (c->debug > 1 && s.gated) fprintf(stderr, "[hj] gated launch: %d edge workgroups + %d, chunk %d, %d tiles\n", ep.edge_count, t.nblocks - ep.edge_count, t.chunk, t.ntiles);
     FusedArgs<T, ND> A;
@@ -86,41 +67,13 @@ int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
         if (rc_fill) return rc_fill;
     }
     if (produce) A.npairs = 0;        // the output reduction of the intended WENO5 pairs planes in ascending order
-    auto kern = tiled_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PD, MODE, PAIR>();
-    c->last_kernel = PAIR ? "fused_pair_kernel" : "fused_substep_kernel";
-    c->note_kernel(kern);
-    c->last_E[0] = t.chunk;
-    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
-    if (t.lds_bytes > 64 * 1024) {
-        // once per (device, kernel), raised but never lowered: the attribute belongs to the function, not to a context
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& granted = granted_by_kernel[std::make_pair(c->device, reinterpret_cast<const void*>(kern))];
-        if (granted < t.lds_bytes) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
-            granted = t.lds_bytes;
-        }
-    }
-    const char* dump = c->timing_dump;              // HJ_TIMING_DUMP (read at ctx creation): per-workgroup start/end clocks of every launch
     unsigned long long* tbuf = nullptr;
-    if (dump && *dump) {
-        HIP_TRY(hipMalloc(&tbuf, (size_t)t.nblocks * 12 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(tbuf, 0, (size_t)t.nblocks * 12 * sizeof(unsigned long long), call_stream(c, s)));
+    {
+        int rc = timing_begin(c, s, t.nblocks, tbuf);
         A.timing = tbuf;
+        if (!rc) rc = enqueue(c, s, kern, grid_blocks, NT, t.lds_bytes, A);
+        if (rc) return rc;
     }
-    if (c->launch_stop) {
-        // completion signal attached to the dispatch packet itself: a separate hipEventRecord costs a
-        // marker packet and ~6 us of bubble before the next kernel of the stream (slab timeline)
-        hipExtLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), (unsigned)t.lds_bytes, call_stream(c, s), nullptr, c->launch_stop, 0,
-                              (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-        c->launch_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), t.lds_bytes, call_stream(c, s), (const T*)s.y, (const T*)s.y0,
-                           (T*)s.out, A);
-    }
-    HIP_TRY(hipGetLastError());
     if (produce) {
         // tile / chunk seams and wrap pairs of the output + the fold of the launch's rows: HJ_EPS_ROWS rows for the next launch
         SeamArgs<T, ND> S;
@@ -138,31 +91,16 @@ int launch_tiled_mode(hj_ctx* c, const SubstepCall& s, Tiling t) {
         HIP_TRY(hipGetLastError());
         c->eps_ready = true;
     }
-    if (tbuf) {
-        std::vector<unsigned long long> h((size_t)t.nblocks * 12);
-        HIP_TRY(hipStreamSynchronize(call_stream(c, s)));
-        HIP_TRY(hipMemcpy(h.data(), tbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        HIP_TRY(hipFree(tbuf));
-        if (FILE* f = fopen(dump, "a")) {
-            fprintf(f, "# launch nblocks=%d ntiles=%d chunk=%d stage=%d\n", t.nblocks, t.ntiles, t.chunk, s.stage);
-            for (int i = 0; i < t.nblocks; ++i) {
-                fprintf(f, "%d %llu %llu %llu %llu", i, h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]);
-                // HJ_STAMP builds: shader-clock sums of the four phases of wave 0 and of the last wave (else zeros)
-                const unsigned long long* ph = h.data() + 4 * (size_t)t.nblocks + 8 * (size_t)i;
-                fprintf(f, " %llu %llu %llu %llu %llu %llu %llu %llu\n", ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7]);
-            }
-            fclose(f);
-        }
-    }
-    return HJ_OK;
+    return timing_end(c, s, t, tbuf);
 }
 
-// plain RK stages (no clamp, no post-step operator, not ydot-only) run the flag-free instantiations
+// one of the three stage classes of a configuration (stage_mode, hj_launch.h)
 template <typename T, typename HAM, int SCHEME, int NT, int R, int KH, int OCC, int PD, bool PAIR = false>
 int launch_tiled(hj_ctx* c, const SubstepCall& s, const Tiling& t) {
-    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0 && !c->no_plain;
-    if (plain && s.stage == HJ_STAGE_EULER) return launch_tiled_mode<T, HAM, SCHEME, NT, R, KH, OCC, PD, 1, PAIR>(c, s, t);
-    if (plain) return launch_tiled_mode<T, HAM, SCHEME, NT, R, KH, OCC, PD, 2, PAIR>(c, s, t);
+    switch (stage_mode(c, s)) {
+        case 1: return launch_tiled_mode<T, HAM, SCHEME, NT, R, KH, OCC, PD, 1, PAIR>(c, s, t);
+        case 2: return launch_tiled_mode<T, HAM, SCHEME, NT, R, KH, OCC, PD, 2, PAIR>(c, s, t);
+    }
     return launch_tiled_mode<T, HAM, SCHEME, NT, R, KH, OCC, PD, 0, PAIR>(c, s, t);
 }
 
@@ -188,105 +126,6 @@ inline bool tile4_fits(const hj_ctx* c, int e1, int e2, int e3) {
     return true;
 }
 
-template <typename T, typename HAM, int SCHEME, int NT, int R, int E1, int E2, int E3, int OCC, bool PG, int MODE>
-int launch_pair4_mode(hj_ctx* c, const SubstepCall& s) {
-    using G = hj::Tile4<E1, E2, E3>;
-    constexpr bool ROWS = hj::ham_has_rows<HAM>::value;
-    constexpr int ER = hj::RowAxis<HAM, ROWS>::value == 1 ? E1 : E2;
-    auto kern = fused_pair4_kernel<T, HAM, SCHEME, NT, R, E1, E2, E3, OCC, PG, MODE>;
-    Tiling t;
-    memset(&t, 0, sizeof(t));
-    t.ok = true;
-    const int Ed[4] = {1, E1, E2, E3};
-    t.ntiles = 1;
-    for (int d = 0; d < HJ_MAX_DIM; ++d) { t.E[d] = 1; t.ntile[d] = 1; }
-    for (int d = 1; d < 4; ++d) {
-        t.E[d] = Ed[d];
-        t.ntile[d] = (int)((c->N[d] + Ed[d] - 1) / Ed[d]);
-        t.ntiles *= t.ntile[d];
-    }
-    t.lpitch = G::PITCH;
-    const size_t base_lds = 512 + 2 * (size_t)G::PLANE * sizeof(T);
-    // two workgroups per CU (OCC waves per SIMD of NT threads): each may take half the CU's LDS; the row table of a chunk
-    // (ER rows x ROWF values per plane) has to fit in what the plane buffers leave
-    const int wg_per_cu = std::max(1, OCC * 256 / NT);
-    const size_t lds_cap = (size_t)(160 * 1024) / wg_per_cu - 256;
-    int64_t chunk_max = 0;
-    if (ROWS) {
-        if (base_lds + (size_t)ER * G::ROWF * sizeof(T) * 8 > lds_cap) return hjh::fail(HJ_EUNSUPPORTED, "4-D tile leaves no LDS for the row table");
-        chunk_max = (int64_t)((lds_cap - base_lds) / ((size_t)ER * G::ROWF * sizeof(T)));
-    }
-    EdgePlan ep;
-    {
-        const int rc_plan = plan_chunks(c, s, t, wg_per_cu, ep, chunk_max);
-        if (rc_plan) return rc_plan;
-    }
-    t.lds_bytes = base_lds + (ROWS ? (size_t)t.chunk * ER * G::ROWF * sizeof(T) : 0);
-    c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
-    c->last_plan.wg_per_cu = wg_per_cu; c->last_plan.lds_bytes = t.lds_bytes;
-    if (c->dry) {
-        c->last_kernel = "fused_pair4_kernel";
-        c->note_kernel(kern);
-        c->last_E[0] = t.chunk;
-        for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
-        return HJ_OK;
-    }
-    if (c->debug) {
-        fprintf(stderr, "[hj] pair4 tiling NT=%d R=%d OCC=%d E=(%d,%d,%d) pitch=%d ntiles=%d chunk=%d nchunks=%d blocks=%d lds=%zu PG=%d MODE=%d\n",
-                NT, R, OCC, E1, E2, E3, G::PITCH, t.ntiles, t.chunk, t.nchunks, t.nblocks, t.lds_bytes, (int)PG, MODE);
-        c->debug = 0;
-    }
-    FusedArgs<T, 4> A;
-    memset(&A, 0, sizeof(A));
-    A.bound = s.bound;
-    unsigned grid_blocks = 0;
-    {
-        const int rc_fill = fill_fused_args<T, 4>(c, s, t, ep, SCHEME, true, A, grid_blocks);
-        if (rc_fill) return rc_fill;
-    }
-    A.lds_nbuf = 2;
-    A.halo_ahead = 0;
-    A.npairs = 0;
-    c->last_nbuf = 2;
-    c->last_kernel = "fused_pair4_kernel";
-    c->note_kernel(kern);
-    c->last_E[0] = t.chunk;
-    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
-    if (t.lds_bytes > 64 * 1024) {
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& granted = granted_by_kernel[std::make_pair(c->device, reinterpret_cast<const void*>(kern))];
-        if (granted < t.lds_bytes) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
-            granted = t.lds_bytes;
-        }
-    }
-    if (c->launch_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), (unsigned)t.lds_bytes, call_stream(c, s), nullptr, c->launch_stop, 0,
-                              (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-        c->launch_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), t.lds_bytes, call_stream(c, s), (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-    }
-    HIP_TRY(hipGetLastError());
-    return HJ_OK;
-}
-
-template <typename T, typename HAM, int SCHEME, int NT, int R, int E1, int E2, int E3, int OCC>
-int launch_pair4(hj_ctx* c, const SubstepCall& s) {
-    // PG: can a halo cell of a plane axis be a ghost (an extrapolated axis among 1..3)?  All-periodic grids take the lean instantiation
-    const bool pg = c->bc[1] != HJ_BC_PERIODIC || c->bc[2] != HJ_BC_PERIODIC || c->bc[3] != HJ_BC_PERIODIC;
-    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0 && !c->no_plain;
-    const int mode = plain ? (s.stage == HJ_STAGE_EULER ? 1 : 2) : 0;
-#define HJ_P4(PG_, MODE_) return launch_pair4_mode<T, HAM, SCHEME, NT, R, E1, E2, E3, OCC, PG_, MODE_>(c, s)
-    if (pg) { if (mode == 1) HJ_P4(true, 1); if (mode == 2) HJ_P4(true, 2); HJ_P4(true, 0); }
-    if (mode == 1) HJ_P4(false, 1);
-    if (mode == 2) HJ_P4(false, 2);
-    HJ_P4(false, 0);
-#undef HJ_P4
-}
-
 // ---- the 4-D fp32 kernel with full-row tiles and 16-byte row loads (hj_flat4v.h; round 6): (threads, pairs per thread, E1, E2, LDS row
 // pitch P3, waves/SIMD hint).  Taken ahead of the compile-time tiles above when the grid's contiguous axis fits a row of the box.
 #ifndef HJ_FLAT4
@@ -298,16 +137,43 @@ inline bool flat4_fits(const hj_ctx* c, int nt, int r, int e1, int e2, int p3) {
     return n3 >= 8 && n3 <= p3 - HJ_VPAD - 4 && nr * halfp <= (long long)nt * r && nr * ch <= nt && nh * ch <= 4ll * nt;
 }
 
-template <typename T, typename HAM, int SCHEME, int NT, int R, int E1, int E2, int P3, int OCC, bool PG, int MODE>
-int launch_flat4_mode(hj_ctx* c, const SubstepCall& s) {
-    using G = hj::Flat4<E1, E2, P3>;
-    constexpr bool ROWS = hj::ham_has_rows<HAM>::value;
-    constexpr int ER = hj::RowAxis<HAM, ROWS>::value == 1 ? E1 : E2;
-    auto kern = fused_flat4_kernel<T, HAM, SCHEME, NT, R, E1, E2, P3, OCC, PG, MODE>;
+// What the launcher of the two fixed-tile 4-D kernels needs to know of each (launch_tile4_mode): the kernel, the tile's extent along the
+// contiguous axis, the LDS of its plane buffers, and how many workgroups share a CU's LDS.
+template <typename T_, typename HAM_, int SCHEME_, int NT_, int R_, int E1_, int E2_, int E3, int OCC>
+struct Pair4Form {
+    using T = T_; using HAM = HAM_; using G = hj::Tile4<E1_, E2_, E3>;
+    static constexpr int SCHEME = SCHEME_, NT = NT_, R = R_, E1 = E1_, E2 = E2_, LPITCH = G::PITCH, OCC_HINT = OCC;
+    static constexpr const char *kernel_name = "fused_pair4_kernel", *tag = "pair4", *e3_note = "",
+                                *no_rows = "4-D tile leaves no LDS for the row table";
+    template <bool PG, int MODE> static auto kernel() { return fused_pair4_kernel<T, HAM, SCHEME, NT, R, E1, E2, E3, OCC, PG, MODE>; }
+    static int e3(const hj_ctx*) { return E3; }
+    static constexpr size_t base_lds = 512 + 2 * (size_t)G::PLANE * sizeof(T);
+    // two workgroups per CU (OCC waves per SIMD of NT threads): each may take half the CU's LDS
+    static int wg_per_cu() { return std::max(1, OCC * 256 / NT); }
+};
+template <typename T_, typename HAM_, int SCHEME_, int NT_, int R_, int E1_, int E2_, int P3, int OCC>
+struct Flat4Form {
+    using T = T_; using HAM = HAM_; using G = hj::Flat4<E1_, E2_, P3>;
+    static constexpr int SCHEME = SCHEME_, NT = NT_, R = R_, E1 = E1_, E2 = E2_, LPITCH = P3, OCC_HINT = OCC;
+    static constexpr const char *kernel_name = "fused_flat4_kernel", *tag = "flat4", *e3_note = "whole rows of ",
+                                *no_rows = "4-D full-row tile leaves no LDS for the row table";
+    template <bool PG, int MODE> static auto kernel() { return fused_flat4_kernel<T, HAM, SCHEME, NT, R, E1, E2, P3, OCC, PG, MODE>; }
+    static int e3(const hj_ctx* c) { return (int)c->N[3]; }
+    static constexpr size_t base_lds = 512 + (2 * (size_t)G::PLANE + 2 * (size_t)G::STAGE) * sizeof(T);
+    static int wg_per_cu() { return std::max(1, std::min(OCC * 256 / NT, (int)((size_t)(160 * 1024) / (base_lds + 4096)))); }
+};
+
+template <typename F, bool PG, int MODE>
+int launch_tile4_mode(hj_ctx* c, const SubstepCall& s) {
+    using T = typename F::T;
+    using G = typename F::G;
+    constexpr bool ROWS = hj::ham_has_rows<typename F::HAM>::value;
+    constexpr int ER = hj::RowAxis<typename F::HAM, ROWS>::value == 1 ? F::E1 : F::E2;
+    auto kern = F::template kernel<PG, MODE>();
     Tiling t;
     memset(&t, 0, sizeof(t));
     t.ok = true;
-    const int Ed[4] = {1, E1, E2, (int)c->N[3]};
+    const int Ed[4] = {1, F::E1, F::E2, F::e3(c)};
     t.ntiles = 1;
     for (int d = 0; d < HJ_MAX_DIM; ++d) { t.E[d] = 1; t.ntile[d] = 1; }
     for (int d = 1; d < 4; ++d) {
@@ -315,31 +181,26 @@ int launch_flat4_mode(hj_ctx* c, const SubstepCall& s) {
         t.ntile[d] = (int)((c->N[d] + Ed[d] - 1) / Ed[d]);
         t.ntiles *= t.ntile[d];
     }
-    t.lpitch = P3;
-    const size_t base_lds = 512 + (2 * (size_t)G::PLANE + 2 * (size_t)G::STAGE) * sizeof(T);
-    const int wg_per_cu = std::max(1, std::min(OCC * 256 / NT, (int)((size_t)(160 * 1024) / (base_lds + 4096))));
-    const size_t lds_cap = (size_t)(160 * 1024) / wg_per_cu - 256;
+    t.lpitch = F::LPITCH;
+    // the row table of a chunk (ER rows x ROWF values per plane) has to fit in what the plane buffers leave of a workgroup's share of the CU's LDS
+    const int occ_blocks = F::wg_per_cu();
+    const size_t lds_cap = (size_t)(160 * 1024) / occ_blocks - 256;
     int64_t chunk_max = 0;
     if (ROWS) {
-        if (base_lds + (size_t)ER * G::ROWF * sizeof(T) * 8 > lds_cap) return hjh::fail(HJ_EUNSUPPORTED, "4-D full-row tile leaves no LDS for the row table");
-        chunk_max = (int64_t)((lds_cap - base_lds) / ((size_t)ER * G::ROWF * sizeof(T)));
+        if (F::base_lds + (size_t)ER * G::ROWF * sizeof(T) * 8 > lds_cap) return hjh::fail(HJ_EUNSUPPORTED, F::no_rows);
+        chunk_max = (int64_t)((lds_cap - F::base_lds) / ((size_t)ER * G::ROWF * sizeof(T)));
     }
     EdgePlan ep;
     {
-        const int rc_plan = plan_chunks(c, s, t, wg_per_cu, ep, chunk_max);
+        const int rc_plan = plan_chunks(c, s, t, occ_blocks, ep, chunk_max);
         if (rc_plan) return rc_plan;
     }
-    t.lds_bytes = base_lds + (ROWS ? (size_t)t.chunk * ER * G::ROWF * sizeof(T) : 0);
-    c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
-    c->last_plan.wg_per_cu = wg_per_cu; c->last_plan.lds_bytes = t.lds_bytes;
-    c->last_kernel = "fused_flat4_kernel";
-    c->note_kernel(kern);
-    c->last_E[0] = t.chunk;
-    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = t.E[d];
+    t.lds_bytes = F::base_lds + (ROWS ? (size_t)t.chunk * ER * G::ROWF * sizeof(T) : 0);
+    record_plan(c, t, F::NT, occ_blocks, F::kernel_name, reinterpret_cast<const void*>(kern), 4);
     if (c->dry) return HJ_OK;
     if (c->debug) {
-        fprintf(stderr, "[hj] flat4 tiling NT=%d R=%d OCC=%d E=(%d,%d,whole rows of %d) pitch=%d ntiles=%d chunk=%d nchunks=%d blocks=%d lds=%zu PG=%d MODE=%d\n",
-                NT, R, OCC, E1, E2, (int)c->N[3], P3, t.ntiles, t.chunk, t.nchunks, t.nblocks, t.lds_bytes, (int)PG, MODE);
+        fprintf(stderr, "[hj] %s tiling NT=%d R=%d OCC=%d E=(%d,%d,%s%d) pitch=%d ntiles=%d chunk=%d nchunks=%d blocks=%d lds=%zu PG=%d MODE=%d\n",
+                F::tag, F::NT, F::R, F::OCC_HINT, F::E1, F::E2, F::e3_note, t.E[3], t.lpitch, t.ntiles, t.chunk, t.nchunks, t.nblocks, t.lds_bytes, (int)PG, MODE);
         c->debug = 0;
     }
     FusedArgs<T, 4> A;
@@ -347,45 +208,29 @@ int launch_flat4_mode(hj_ctx* c, const SubstepCall& s) {
     A.bound = s.bound;
     unsigned grid_blocks = 0;
     {
-        const int rc_fill = fill_fused_args<T, 4>(c, s, t, ep, SCHEME, true, A, grid_blocks);
+        const int rc_fill = fill_fused_args<T, 4>(c, s, t, ep, F::SCHEME, true, A, grid_blocks);
         if (rc_fill) return rc_fill;
     }
     A.lds_nbuf = 2;
     A.halo_ahead = 0;
     A.npairs = 0;
     c->last_nbuf = 2;
-    if (t.lds_bytes > 64 * 1024) {
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& granted = granted_by_kernel[std::make_pair(c->device, reinterpret_cast<const void*>(kern))];
-        if (granted < t.lds_bytes) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
-            granted = t.lds_bytes;
-        }
-    }
-    if (c->launch_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), (unsigned)t.lds_bytes, call_stream(c, s), nullptr, c->launch_stop, 0,
-                              (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-        c->launch_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), t.lds_bytes, call_stream(c, s), (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-    }
-    HIP_TRY(hipGetLastError());
-    return HJ_OK;
+    return enqueue(c, s, kern, grid_blocks, F::NT, t.lds_bytes, A);
 }
 
-template <typename T, typename HAM, int SCHEME, int NT, int R, int E1, int E2, int P3, int OCC>
-int launch_flat4(hj_ctx* c, const SubstepCall& s) {
+template <typename F, bool PG>
+int launch_tile4_pg(hj_ctx* c, const SubstepCall& s) {
+    switch (stage_mode(c, s)) {
+        case 1: return launch_tile4_mode<F, PG, 1>(c, s);
+        case 2: return launch_tile4_mode<F, PG, 2>(c, s);
+    }
+    return launch_tile4_mode<F, PG, 0>(c, s);
+}
+template <typename F>
+int launch_tile4(hj_ctx* c, const SubstepCall& s) {
+    // PG: can a halo cell of a plane axis be a ghost (an extrapolated axis among 1..3)?  All-periodic grids take the lean instantiation
     const bool pg = c->bc[1] != HJ_BC_PERIODIC || c->bc[2] != HJ_BC_PERIODIC || c->bc[3] != HJ_BC_PERIODIC;
-    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0 && !c->no_plain;
-    const int mode = plain ? (s.stage == HJ_STAGE_EULER ? 1 : 2) : 0;
-#define HJ_F4(PG_, MODE_) return launch_flat4_mode<T, HAM, SCHEME, NT, R, E1, E2, P3, OCC, PG_, MODE_>(c, s)
-    if (pg) { if (mode == 1) HJ_F4(true, 1); if (mode == 2) HJ_F4(true, 2); HJ_F4(true, 0); }
-    if (mode == 1) HJ_F4(false, 1);
-    if (mode == 2) HJ_F4(false, 2);
-    HJ_F4(false, 0);
-#undef HJ_F4
+    return pg ? launch_tile4_pg<F, true>(c, s) : launch_tile4_pg<F, false>(c, s);
 }
 
 // (threads, PAIRS per thread, halo slots per thread, waves/SIMD hint) of the pair kernel
@@ -478,13 +323,11 @@ int tune_end(hj_ctx* c, const SubstepCall& s, TuneTrial& tr, int rc, int scheme)
 template <typename T, typename HAM, int SCHEME>
 int launch_direct(hj_ctx* c, const SubstepCall& s) {
     constexpr int ND = HAM::ND;
+    record_launch(c, "direct_substep_kernel", reinterpret_cast<const void*>(direct_substep_kernel<T, HAM, SCHEME>));
     if (c->dry) {
         const long long cells = (s.p1 - s.p0) * (c->total / c->N[0]);
         c->last_plan.ntiles = 0; c->last_plan.nchunks = 1; c->last_plan.threads = 256; c->last_plan.wg_per_cu = 8; c->last_plan.lds_bytes = 0;
         c->last_plan.nblocks = (int)std::min<long long>((cells + 255) / 256, 256 * 16);
-        c->last_kernel = "direct_substep_kernel";
-        c->note_kernel(direct_substep_kernel<T, HAM, SCHEME>);
-        for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
         return HJ_OK;
     }
     DirectArgs<T, ND> A;
@@ -529,9 +372,6 @@ int launch_direct(hj_ctx* c, const SubstepCall& s) {
         const long long cells = A.cell_end - A.cell_begin;
         if (cells <= 0) continue;
         int blocks = (int)std::min<long long>((cells + 255) / 256, 256 * 16);
-        c->last_kernel = "direct_substep_kernel";
-        c->note_kernel(direct_substep_kernel<T, HAM, SCHEME>);
-        for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
         hipLaunchKernelGGL((direct_substep_kernel<T, HAM, SCHEME>), dim3(blocks), dim3(256), 0, call_stream(c, s), A);
         HIP_TRY(hipGetLastError());
     }
@@ -574,9 +414,7 @@ int launch_coop_cpt(hj_ctx* c, const CoopCall& s, int nblocks) {
     // what this launch adds to the counters (order - 1 barriers)
     for (int x = 0; x < 8; ++x) c->coop_xcd[x] += (unsigned long long)(s.order - 1) * nper[x];
     c->coop_all += (unsigned long long)(s.order - 1) * nx;
-    c->last_kernel = "coop_rk_kernel";
-    c->note_kernel(kern);
-    for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = 0;
+    record_launch(c, "coop_rk_kernel", reinterpret_cast<const void*>(kern));
     return HJ_OK;
 }
 
@@ -589,15 +427,9 @@ int launch_coop_scheme(hj_ctx* c, const CoopCall& s) {
     // in one launch is slower than its stage launches, profiles/r06_small_grids.txt, and where a launch that needs EVERY workgroup resident
     // is least safe beside other work on the device.)
     const long long total = c->total;
-    const void* k1 = reinterpret_cast<const void*>(coop_rk_kernel<T, HAM, SCHEME, 1>);
-    auto it = c->occ_cache.find(std::make_pair(k1, (size_t)0));
-    if (it == c->occ_cache.end()) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k1, 256, 0) != hipSuccess || nb < 1) nb = 1;
-        it = c->occ_cache.emplace(std::make_pair(k1, (size_t)0), nb).first;
-    }
+    const int resident = wg_per_cu(c, reinterpret_cast<const void*>(coop_rk_kernel<T, HAM, SCHEME, 1>), 256, 0, 1);      // (never dry: the hint is not read)
     const long long need1 = (total + 255) / 256;
-    if (need1 <= (long long)it->second * c->num_cus) return launch_coop_cpt<T, HAM, SCHEME, 1>(c, s, (int)need1);
+    if (need1 <= (long long)resident * c->num_cus) return launch_coop_cpt<T, HAM, SCHEME, 1>(c, s, (int)need1);
     return HJ_XP_FALLBACK;
 }
 
@@ -669,14 +501,14 @@ int launch_cfg(hj_ctx* c, const SubstepCall& s) {
                 if (c->pair != 0 && c->flat4 != 0 && flat_pays && c->pair_nt <= 0 && (c->total >= pair_from || c->pair == 2)) {
                     // full-row tiles with 16-byte row loads (hj_flat4v.h, round 6) when the contiguous axis fits a row of the box (HJ_FLAT4=0: never)
                     int kf = 0;          // (HJ_FLAT4_SEL = k: only the k-th shape of the list, for A/B runs)
-#define X(NT_, R_, E1_, E2_, P3_, OCC_) if ((c->flat4_sel < 0 || c->flat4_sel == kf) && flat4_fits(c, NT_, R_, E1_, E2_, P3_)) return launch_flat4<T, HAM, SCHEME, NT_, R_, E1_, E2_, P3_, OCC_>(c, s); ++kf;
+#define X(NT_, R_, E1_, E2_, P3_, OCC_) if ((c->flat4_sel < 0 || c->flat4_sel == kf) && flat4_fits(c, NT_, R_, E1_, E2_, P3_)) return launch_tile4<Flat4Form<T, HAM, SCHEME, NT_, R_, E1_, E2_, P3_, OCC_>>(c, s); ++kf;
                     HJ_FLAT4(X)
 #undef X
                 }
                 if (c->pair != 0 && c->pair4 != 0 && c->pair_nt <= 0 && (c->total >= pair_from || c->pair == 2)) {
                     // the first tile of the list that fits (HJ_TILE4_SEL = k: only the k-th, for A/B runs)
                     int k4 = 0;
-#define X(NT_, R_, E1_, E2_, E3_, OCC_) if ((c->tile4_sel < 0 || c->tile4_sel == k4) && tile4_fits(c, E1_, E2_, E3_)) return launch_pair4<T, HAM, SCHEME, NT_, R_, E1_, E2_, E3_, OCC_>(c, s); ++k4;
+#define X(NT_, R_, E1_, E2_, E3_, OCC_) if ((c->tile4_sel < 0 || c->tile4_sel == k4) && tile4_fits(c, E1_, E2_, E3_)) return launch_tile4<Pair4Form<T, HAM, SCHEME, NT_, R_, E1_, E2_, E3_, OCC_>>(c, s); ++k4;
                     HJ_TILE4(X)
 #undef X
                 }
@@ -705,12 +537,13 @@ int launch_cfg(hj_ctx* c, const SubstepCall& s) {
                 TuneTrial tr;
                 const Tiling tp = tune_begin<HAM::ND>(c, s, kp, 2, c->last_nbuf + (produce ? 2 : 0), key, tr);      // (+ the epsilon producer's two planes)
                 if (tp.ok) {
-                    int rc_t = -12345;
-#define X(NT_, R_, KH_, OCC_) if constexpr (cfg_built(SCHEME, HAM::ND, NT_, R_, true, (int)sizeof(T))) { if (rc_t == -12345 && kp.NT == NT_ && kp.R == R_ && kp.KH == KH_ && occp == OCC_) rc_t = launch_tiled<T, HAM, SCHEME, NT_, R_, KH_, OCC_, 2, true>(c, s, tp); }
+                    bool launched = false;
+                    int rc_t = HJ_OK;
+#define X(NT_, R_, KH_, OCC_) if constexpr (cfg_built(SCHEME, HAM::ND, NT_, R_, true, (int)sizeof(T))) { if (!launched && kp.NT == NT_ && kp.R == R_ && kp.KH == KH_ && occp == OCC_) { launched = true; rc_t = launch_tiled<T, HAM, SCHEME, NT_, R_, KH_, OCC_, 2, true>(c, s, tp); } }
                     if constexpr (HAM::ND == 4) { HJ_CONFIGS_PAIR_4D(X) }
                     else { HJ_CONFIGS_PAIR(X) }
 #undef X
-                    if (rc_t != -12345) return tune_end<HAM::ND>(c, s, tr, rc_t, SCHEME);
+                    if (launched) return tune_end<HAM::ND>(c, s, tr, rc_t, SCHEME);
                     if (c->pair_nt > 0 || c->pair_r > 0 || c->pair_kh > 0 || c->pair_occ > 0)
                         return hjh::fail(HJ_EUNSUPPORTED, "pair-kernel configuration (%d,%d,%d,%d) requested through HJ_PAIR_* is not built for scheme %d",
                                          kp.NT, kp.R, kp.KH, occp, SCHEME);
@@ -721,12 +554,13 @@ int launch_cfg(hj_ctx* c, const SubstepCall& s) {
             TuneTrial tr1;
             Tiling t = tune_begin<HAM::ND>(c, s, k, 1, produce ? 4 : 2, key1, tr1);
             if (t.ok) {
-                int rc_t = -12345;
-#define X(NT_, R_, KH_, OCC_, PD_) if constexpr (cfg_built(SCHEME, HAM::ND, NT_, R_, false, (int)sizeof(T))) { if (rc_t == -12345 && k.NT == NT_ && k.R == R_ && k.KH == KH_ && pd == PD_ && occ == OCC_) rc_t = launch_tiled<T, HAM, SCHEME, NT_, R_, KH_, OCC_, PD_>(c, s, t); }
+                bool launched = false;
+                int rc_t = HJ_OK;
+#define X(NT_, R_, KH_, OCC_, PD_) if constexpr (cfg_built(SCHEME, HAM::ND, NT_, R_, false, (int)sizeof(T))) { if (!launched && k.NT == NT_ && k.R == R_ && k.KH == KH_ && pd == PD_ && occ == OCC_) { launched = true; rc_t = launch_tiled<T, HAM, SCHEME, NT_, R_, KH_, OCC_, PD_>(c, s, t); } }
                 if constexpr (HAM::ND == 4) { HJ_CONFIGS_4D(X) }
                 else { HJ_CONFIGS(X) }
 #undef X
-                if (rc_t != -12345) return tune_end<HAM::ND>(c, s, tr1, rc_t, SCHEME);
+                if (launched) return tune_end<HAM::ND>(c, s, tr1, rc_t, SCHEME);
                 if (c->cfg_from_env)
                     return hjh::fail(HJ_EUNSUPPORTED, "kernel configuration (%d,%d,%d,%d,%d) requested through HJ_NT/HJ_R/HJ_KH/HJ_OCC/HJ_PD is not built for scheme %d",
                                      k.NT, k.R, k.KH, occ, pd, SCHEME);
@@ -739,121 +573,150 @@ int launch_cfg(hj_ctx* c, const SubstepCall& s) {
 extern template int launch_xp<double, HamDubinsRel<double>>(hj_ctx*, const SubstepCall&);
 extern template int launch_xp<float, HamDubinsRel<float>>(hj_ctx*, const SubstepCall&);
 
+// ---- launch-time choice between the axis-0 march and the transposed march (hj_ctx::XpTrial, hj_host.h), auto mode (HJ_XP=1).
+// PRIOR: the two launch plans.  Both forms are memory-system bound, so a launch costs about the cells its
+// workgroups stage -- workgroups x (chunk + 6 warm-up planes) x the tile and its 3-cell frame -- stretched where the workgroups do
+// not fill the CUs' slots evenly (x (1 + 0.4 (slots / workgroups - 1)), fitted on 19 shapes: profiles/r06_thin_slab.txt, "the auto choice over shapes");
+// transposed iff that says <= 0.975 of the axis-0 march.  The model ranks 17 of the 19 shapes correctly and is all a dry context has;
+// a LIVE context measures instead: runs of six calls of one form between two events, the forms taking turns --
+// same bits either way -- and after HJ_XP_TRIALS runs of each the faster form is kept for the life of the context.
+
+// A planning look from a live context: launches plan and return (c->dry == 2) and what they record of themselves is put back afterwards
+struct PlanLook {
+    hj_ctx* c;
+    decltype(hj_ctx::last_plan) plan;
+    const char* kernel;
+    int E[HJ_MAX_DIM], nbuf, dry;
+    explicit PlanLook(hj_ctx* c_) : c(c_), plan(c_->last_plan), kernel(c_->last_kernel), nbuf(c_->last_nbuf), dry(c_->dry) {
+        for (int d = 0; d < HJ_MAX_DIM; ++d) E[d] = c->last_E[d];
+        c->dry = 2;
+    }
+    ~PlanLook() {
+        c->dry = dry;
+        c->last_plan = plan; c->last_kernel = kernel; c->last_nbuf = nbuf;
+        for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = E[d];
+    }
+};
+
+// the plan-cost prior of a (scheme, plane range), and with it what is decided without a measurement
+template <typename T, typename HAM>
+hj_ctx::XpTrial xp_prior(hj_ctx* c, const SubstepCall& s) {
+    double c0 = -1, cx = -1;
+    {
+        PlanLook look(c);
+        SubstepCall a = s;
+        a.xp = false;
+        auto cost = [&]() {
+            const double wg = std::max(1, c->last_plan.nblocks);
+            const double cap = (double)std::max(1, c->num_cus) * std::max(1, c->last_plan.wg_per_cu);
+            const double slots = cap * std::ceil(wg / cap);
+            return wg * (c->last_E[0] + 2 * HJ_STENCIL) * (double)(c->last_E[1] + 2 * HJ_STENCIL) * (double)(c->last_E[2] + 2 * HJ_STENCIL) *
+                   (1.0 + 0.4 * (slots / wg - 1.0));
+        };
+        if (launch_scheme<T, HAM>(c, a) == HJ_OK && c->last_plan.ntiles > 0) c0 = cost();
+        if (launch_xp<T, HAM>(c, s) == HJ_OK) cx = cost();
+    }
+    hj_ctx::XpTrial t;
+    t.prior = cx > 0 && (c0 <= 0 || cx <= 0.975 * c0);
+    if (cx <= 0) t.decided = 0;                                  // this call has no transposed form
+    else if (c0 <= 0) t.decided = 1;
+    else if (c->dry || c->xp_trials == 0) t.decided = t.prior;
+    return t;
+}
+
+struct XpRun { hj_ctx::XpTrial* tr = nullptr; bool sample = false; };
+
+// The form of this launch (true: the transposed march): what was decided, else the prior -- or, live and undecided, the form of the timed run
+// under way / of the run this call begins.  Finished runs are read back here, without waiting.
+inline bool xp_begin(hj_ctx* c, const SubstepCall& s, XpRun& run) {
+    hj_ctx::XpTrial* tr = run.tr;
+    bool take = tr->decided >= 0 ? tr->decided == 1 : tr->prior;
+    if (!(tr->decided < 0 && !c->dry && !c->launch_stop)) return take;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(call_stream(c, s), &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+        (void)hipGetLastError();
+        tr->calls = 0;                                                 // (a run cut by a capture is dropped)
+        return take;
+    }
+    for (int f = 0; f < 2; ++f) {
+        if (!tr->pend[f] || hipEventQuery(tr->ev[f][1]) != hipSuccess) continue;
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, tr->ev[f][0], tr->ev[f][1]) == hipSuccess && ms > 0) {
+            tr->best[f] = std::min(tr->best[f], ms);
+            tr->n[f] += 1;
+        }
+        tr->pend[f] = false;
+    }
+    (void)hipGetLastError();                                       // (hipErrorNotReady is not this launch's error)
+    if (tr->calls == 0 && tr->n[0] >= c->xp_trials && tr->n[1] >= c->xp_trials) {
+        tr->decided = tr->best[1] < tr->best[0] ? 1 : 0;
+        take = tr->decided == 1;
+        if (c->debug_xp) fprintf(stderr, "[hj] planes [%lld, %lld): %d calls of the axis-0 march %.4f ms, of the transposed march %.4f ms (plan model: %s) -> %s\n",
+                                 (long long)s.p0, (long long)s.p1, (int)hj_ctx::XP_RUN, tr->best[0], tr->best[1], tr->prior ? "transposed" : "axis-0",
+                                 take ? "transposed" : "axis-0");
+    } else if (tr->calls > 0) {
+        take = tr->form == 1;                                      // inside a run
+        run.sample = true;
+    } else {
+        const int f = tr->n[1] + (tr->pend[1] ? 1 : 0) < tr->n[0] + (tr->pend[0] ? 1 : 0) ? 1 : 0;      // take turns, the axis-0 march first
+        if (!tr->ev[0][0]) {
+            bool ok = true;
+            for (int i = 0; i < 4; ++i) ok = ok && hipEventCreate(&tr->ev[i / 2][i % 2]) == hipSuccess;
+            if (!ok) { (void)hipGetLastError(); tr->decided = tr->prior; }
+        }
+        if (tr->decided < 0 && tr->started >= 4 * c->xp_trials + 40) {
+            // (never settled -- the stream is captured most of the time, or the tile-shape rotation never ends: what there is)
+            tr->decided = tr->n[0] > 0 && tr->n[1] > 0 ? (tr->best[1] < tr->best[0] ? 1 : 0) : (tr->prior ? 1 : 0);
+            take = tr->decided == 1;
+        } else if (tr->decided < 0 && !tr->pend[f] && tr->n[f] < c->xp_trials + 2) {
+            if (hipEventRecord(tr->ev[f][0], call_stream(c, s)) == hipSuccess) {
+                tr->form = f; tr->started += 1; tr->seq0 = c->tune_seq; take = f == 1; run.sample = true;
+            } else (void)hipGetLastError();
+        }
+    }
+    return take;
+}
+
+// a launch inside a timed run: the run's last call records the closing event
+inline int xp_end(hj_ctx* c, const SubstepCall& s, XpRun& run, int rc) {
+    hj_ctx::XpTrial* tr = run.tr;
+    if (!run.sample) return rc;
+    if (rc != HJ_OK) tr->calls = 0;
+    else if (++tr->calls >= (int)hj_ctx::XP_RUN) {
+        tr->calls = 0;
+        if (c->tune_seq != tr->seq0) {}       // the axis-0 march was trying tile shapes (synchronising trials): not its steady state
+        else if (hipEventRecord(tr->ev[tr->form][1], call_stream(c, s)) == hipSuccess) tr->pend[tr->form] = true;
+        else (void)hipGetLastError();
+    }
+    return rc;
+}
+
+// choose a form, launch it, fall back, account
 template <typename T, typename HAM>
 int launch_scheme(hj_ctx* c, const SubstepCall& s) {
     if constexpr (xp_available<T, HAM>()) {
         // the caller asked for the transposed march (thin slabs; HJ_XP=2): taken where the call has such a form, else the launch below
         if (s.xp && c->xp_mode != 0 && !c->force_direct && !c->cfg_from_env && c->pair != 0) {
-            // Auto mode (HJ_XP=1).  PRIOR: the two launch plans.  Both forms are memory-system bound, so a launch costs about the cells its
-            // workgroups stage -- workgroups x (chunk + 6 warm-up planes) x the tile and its 3-cell frame -- stretched where the workgroups do
-            // not fill the CUs' slots evenly (x (1 + 0.4 (slots / workgroups - 1)), fitted on 19 shapes: profiles/r06_thin_slab.txt, "the auto choice over shapes");
-            // transposed iff that says <= 0.975 of the axis-0 march.  The model ranks 17 of the 19 shapes correctly and is all a dry context has;
-            // a LIVE context measures instead (hj_host.h, XpTrial): runs of six calls of one form between two events, the forms taking turns --
-            // same bits either way -- and after HJ_XP_TRIALS runs of each the faster form is kept for the life of the context.
             bool take = true;
-            hj_ctx::XpTrial* tr = nullptr;
-            bool sample = false;
+            XpRun run;
             if (c->xp_mode == 1 && c->dry != 2) {
                 const long long key = ((long long)s.scheme << 56) ^ ((long long)(s.p0 & 0xffffff) << 24) ^ (long long)(s.p1 & 0xffffff);
                 auto it = c->xp_choice.find(key);
-                if (it == c->xp_choice.end()) {
-                    const auto keep_plan = c->last_plan;
-                    const char* keep_kernel = c->last_kernel;
-                    int keep_E[HJ_MAX_DIM], keep_nbuf = c->last_nbuf;
-                    for (int d = 0; d < HJ_MAX_DIM; ++d) keep_E[d] = c->last_E[d];
-                    const int keep_dry = c->dry;
-                    c->dry = 2;
-                    SubstepCall a = s;
-                    a.xp = false;
-                    auto cost = [&]() {
-                        const double wg = std::max(1, c->last_plan.nblocks);
-                        const double cap = (double)std::max(1, c->num_cus) * std::max(1, c->last_plan.wg_per_cu);
-                        const double slots = cap * std::ceil(wg / cap);
-                        return wg * (c->last_E[0] + 2 * HJ_STENCIL) * (double)(c->last_E[1] + 2 * HJ_STENCIL) * (double)(c->last_E[2] + 2 * HJ_STENCIL) *
-                               (1.0 + 0.4 * (slots / wg - 1.0));
-                    };
-                    double c0 = -1, cx = -1;
-                    if (launch_scheme<T, HAM>(c, a) == HJ_OK && c->last_plan.ntiles > 0) c0 = cost();
-                    if (launch_xp<T, HAM>(c, s) == HJ_OK) cx = cost();
-                    c->dry = keep_dry;
-                    c->last_plan = keep_plan; c->last_kernel = keep_kernel; c->last_nbuf = keep_nbuf;
-                    for (int d = 0; d < HJ_MAX_DIM; ++d) c->last_E[d] = keep_E[d];
-                    hj_ctx::XpTrial t;
-                    t.prior = cx > 0 && (c0 <= 0 || cx <= 0.975 * c0);
-                    if (cx <= 0) t.decided = 0;                                  // this call has no transposed form
-                    else if (c0 <= 0) t.decided = 1;
-                    else if (c->dry || c->xp_trials == 0) t.decided = t.prior;
-                    it = c->xp_choice.emplace(key, t).first;
-                }
-                tr = &it->second;
-                take = tr->decided >= 0 ? tr->decided == 1 : tr->prior;
-                if (tr->decided < 0 && !c->dry && !c->launch_stop) {
-                    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                    if (hipStreamIsCapturing(call_stream(c, s), &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
-                        (void)hipGetLastError();
-                        tr->calls = 0;                                                 // (a run cut by a capture is dropped)
-                    } else {
-                        for (int f = 0; f < 2; ++f) {
-                            if (!tr->pend[f] || hipEventQuery(tr->ev[f][1]) != hipSuccess) continue;
-                            float ms = 0;
-                            if (hipEventElapsedTime(&ms, tr->ev[f][0], tr->ev[f][1]) == hipSuccess && ms > 0) {
-                                tr->best[f] = std::min(tr->best[f], ms);
-                                tr->n[f] += 1;
-                            }
-                            tr->pend[f] = false;
-                        }
-                        (void)hipGetLastError();                                       // (hipErrorNotReady is not this launch's error)
-                        if (tr->calls == 0 && tr->n[0] >= c->xp_trials && tr->n[1] >= c->xp_trials) {
-                            tr->decided = tr->best[1] < tr->best[0] ? 1 : 0;
-                            take = tr->decided == 1;
-                            if (c->debug_xp) fprintf(stderr, "[hj] planes [%lld, %lld): %d calls of the axis-0 march %.4f ms, of the transposed march %.4f ms (plan model: %s) -> %s\n",
-                                                     (long long)s.p0, (long long)s.p1, (int)hj_ctx::XP_RUN, tr->best[0], tr->best[1], tr->prior ? "transposed" : "axis-0",
-                                                     take ? "transposed" : "axis-0");
-                        } else if (tr->calls > 0) {
-                            take = tr->form == 1;                                      // inside a run
-                            sample = true;
-                        } else {
-                            const int f = tr->n[1] + (tr->pend[1] ? 1 : 0) < tr->n[0] + (tr->pend[0] ? 1 : 0) ? 1 : 0;      // take turns, the axis-0 march first
-                            if (!tr->ev[0][0]) {
-                                bool ok = true;
-                                for (int i = 0; i < 4; ++i) ok = ok && hipEventCreate(&tr->ev[i / 2][i % 2]) == hipSuccess;
-                                if (!ok) { (void)hipGetLastError(); tr->decided = tr->prior; }
-                            }
-                            if (tr->decided < 0 && tr->started >= 4 * c->xp_trials + 40) {
-                                // (never settled -- the stream is captured most of the time, or the tile-shape rotation never ends: what there is)
-                                tr->decided = tr->n[0] > 0 && tr->n[1] > 0 ? (tr->best[1] < tr->best[0] ? 1 : 0) : (tr->prior ? 1 : 0);
-                                take = tr->decided == 1;
-                            } else if (tr->decided < 0 && !tr->pend[f] && tr->n[f] < c->xp_trials + 2) {
-                                if (hipEventRecord(tr->ev[f][0], call_stream(c, s)) == hipSuccess) {
-                                    tr->form = f; tr->started += 1; tr->seq0 = c->tune_seq; take = f == 1; sample = true;
-                                } else (void)hipGetLastError();
-                            }
-                        }
-                    }
-                }
+                if (it == c->xp_choice.end()) it = c->xp_choice.emplace(key, xp_prior<T, HAM>(c, s)).first;
+                run.tr = &it->second;
+                take = xp_begin(c, s, run);
             }
             int rc = HJ_XP_FALLBACK;
             if (take) {
                 rc = launch_xp<T, HAM>(c, s);
-                if (rc == HJ_XP_FALLBACK && tr) { tr->decided = 0; tr->calls = 0; sample = false; }
+                if (rc == HJ_XP_FALLBACK && run.tr) { run.tr->decided = 0; run.tr->calls = 0; run.sample = false; }
             }
-            if (rc == HJ_XP_FALLBACK && tr) {
+            if (rc == HJ_XP_FALLBACK && run.tr) {
                 SubstepCall a = s;
                 a.xp = false;
                 rc = launch_scheme<T, HAM>(c, a);
             }
-            if (rc != HJ_XP_FALLBACK) {
-                if (sample) {
-                    if (rc != HJ_OK) tr->calls = 0;
-                    else if (++tr->calls >= (int)hj_ctx::XP_RUN) {
-                        tr->calls = 0;
-                        if (c->tune_seq != tr->seq0) {}       // the axis-0 march was trying tile shapes (synchronising trials): not its steady state
-                        else if (hipEventRecord(tr->ev[tr->form][1], call_stream(c, s)) == hipSuccess) tr->pend[tr->form] = true;
-                        else (void)hipGetLastError();
-                    }
-                }
-                return rc;
-            }
+            if (rc != HJ_XP_FALLBACK) return xp_end(c, s, run, rc);
         }
     }
     switch (s.scheme) {
@@ -958,20 +821,14 @@ template <typename T, typename HAM, int SCHEME, int NT, int R, int KH, int OCC, 
 int launch_fused12(hj_ctx* c, const Stage12Call& s, Tiling12 t) {
     constexpr int ND = HAM::ND;
     auto kern = stage12_kernel<T, HAM, SCHEME, NT, R, KH, OCC, PAIR>();
-    c->last_kernel = PAIR ? "fused12_pair_kernel" : "fused12_kernel";
-    c->note_kernel(kern);
-    if (t.lds_bytes > 64 * 1024)
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
-    const auto key = std::make_pair(reinterpret_cast<const void*>(kern), t.lds_bytes);
-    auto it = c->occ_cache.find(key);
-    if (it == c->occ_cache.end()) {
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, key.first, NT, t.lds_bytes) != hipSuccess || nb < 1) nb = 1;
-        it = c->occ_cache.emplace(key, nb).first;
+    {
+        const int rc_grant = grant_dynamic_lds(c, reinterpret_cast<const void*>(kern), t.lds_bytes);
+        if (rc_grant) return rc_grant;
     }
+    const int occ_blocks = wg_per_cu(c, reinterpret_cast<const void*>(kern), NT, t.lds_bytes, OCC);
     {   // axis-0 chunking: whole rounds of resident workgroups; a chunk pays 12 planes of loads and 6 of stage 1
         const int64_t planes = c->N[0];
-        const int64_t capacity = (int64_t)c->num_cus * it->second;
+        const int64_t capacity = (int64_t)c->num_cus * occ_blocks;
         int64_t best_nch = 1;
         double best_cost = 1e300;
         for (int64_t nch = 1; nch <= std::max<int64_t>(1, planes / 8); ++nch) {
@@ -987,11 +844,10 @@ int launch_fused12(hj_ctx* c, const Stage12Call& s, Tiling12 t) {
         t.nblocks = t.nchunks * t.ntiles;
         t.bpx = (t.nblocks + 7) / 8;
     }
-    c->last_E[0] = t.chunk;
-    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < ND ? t.E[d] : 0;
+    record_launch(c, PAIR ? "fused12_pair_kernel" : "fused12_kernel", reinterpret_cast<const void*>(kern), t.chunk, t.E, ND);
     if (c->debug) {
         fprintf(stderr, "[hj] fused12%s NT=%d R=%d KH=%d OCC=%d E=(%d,%d) nA=%d nH=%d ntiles=%d chunk=%d nchunks=%d blocks=%d wg/CU=%d lds=%zu score=%.3f\n",
-                PAIR ? " pair" : "", NT, R, KH, OCC, t.E[1], ND > 2 ? t.E[2] : 0, t.nA, t.nH, t.ntiles, t.chunk, t.nchunks, t.nblocks, it->second, t.lds_bytes, t.score);
+                PAIR ? " pair" : "", NT, R, KH, OCC, t.E[1], ND > 2 ? t.E[2] : 0, t.nA, t.nH, t.ntiles, t.chunk, t.nchunks, t.nblocks, occ_blocks, t.lds_bytes, t.score);
         c->debug = 0;
     }
     Fused12Args<T, ND> A;

@@ -3,7 +3,6 @@
 // slabs of the 8-GPU configurations (C4: 64-65 planes of 513 x 513), which the axis-0 march cuts into 399 short workgroups on 256 CUs
 // (profiles/r05_thin_slab.txt).  Same per-cell arithmetic in the same order: bitwise the results of the axis-0 march.
 // Compiled once per (dtype, Hamiltonian) with -DHJ_INST_T / -DHJ_INST_HAM like hj_inst.hip.  gfx950 only.
-#include <mutex>
 #include "hj_host.h"
 #include "hj_fused.h"
 #include "hj_fusedv.h"
@@ -61,14 +60,7 @@ int launch_xp_mode(hj_ctx* c, const SubstepCall& s, int nbuf) {
     const KernelCfg kp{NT, R, KH};
     Tiling t = make_tiling_dims(c, kp, 2, nbuf, dims);
     if (!t.ok) return HJ_XP_FALLBACK;
-    const auto key = std::make_pair(reinterpret_cast<const void*>(kern), t.lds_bytes);
-    auto it = c->occ_cache.find(key);
-    int occ_blocks = it != c->occ_cache.end() ? it->second : 0;
-    if (it == c->occ_cache.end()) {
-        if (c->dry) occ_blocks = std::max(1, std::min(OCC * 256 / NT, (int)((size_t)(160 * 1024) / std::max<size_t>(1, t.lds_bytes))));
-        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ_blocks, key.first, NT, t.lds_bytes) != hipSuccess || occ_blocks < 1) occ_blocks = 1;
-        if (c->dry != 2) c->occ_cache.emplace(key, occ_blocks);     // (2: a planning look from a live context -- its estimate is not the device's answer)
-    }
+    const int occ_blocks = wg_per_cu(c, reinterpret_cast<const void*>(kern), NT, t.lds_bytes, OCC);
     // the span of a buffer descriptor: the rows of the window and its halo (fixed) + a chunk of the march and 3 rows either side
     const long long xbase = std::min<int64_t>(0, c->halo_lo ? s.p0 - HJ_STENCIL : 0);
     const long long hi = c->halo_hi ? std::max<long long>(s.p1 + HJ_STENCIL, N0) : N0;
@@ -77,12 +69,7 @@ int launch_xp_mode(hj_ctx* c, const SubstepCall& s, int nbuf) {
     choose_chunks(c, t, 0, N1, occ_blocks, 0, (double)N2 * (double)sizeof(T), fixed);
     if (!t.ok) return HJ_XP_FALLBACK;
     t.nchunks1 = t.nchunks;
-    c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = NT;
-    c->last_plan.wg_per_cu = occ_blocks; c->last_plan.lds_bytes = t.lds_bytes;
-    c->last_kernel = "fused_pair_kernel (march along axis 1)";
-    c->note_kernel(kern);
-    c->last_E[0] = t.chunk;
-    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = d < 3 ? t.E[d] : 0;
+    record_plan(c, t, NT, occ_blocks, "fused_pair_kernel (march along axis 1)", reinterpret_cast<const void*>(kern), 3);
     c->last_nbuf = nbuf;
     if (c->dry) return HJ_OK;
     if (c->debug) {
@@ -99,33 +86,14 @@ int launch_xp_mode(hj_ctx* c, const SubstepCall& s, int nbuf) {
         const int rc_fill = fill_fused_args_xp3<T>(c, s, t, SCHEME, A, grid_blocks);
         if (rc_fill) return rc_fill;
     }
-    if (t.lds_bytes > 64 * 1024) {
-        static std::mutex mu;
-        static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
-        std::lock_guard<std::mutex> lock(mu);
-        size_t& granted = granted_by_kernel[std::make_pair(c->device, reinterpret_cast<const void*>(kern))];
-        if (granted < t.lds_bytes) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
-            granted = t.lds_bytes;
-        }
-    }
-    if (c->launch_stop) {
-        hipExtLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), (unsigned)t.lds_bytes, call_stream(c, s), nullptr, c->launch_stop, 0,
-                              (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-        c->launch_stop = nullptr;
-    } else {
-        hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(NT), t.lds_bytes, call_stream(c, s), (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
-    }
-    HIP_TRY(hipGetLastError());
-    return HJ_OK;
+    return enqueue(c, s, kern, grid_blocks, NT, t.lds_bytes, A);
 }
 
 template <typename T, typename HAM, int SCHEME>
 int launch_xp_cfg(hj_ctx* c, const SubstepCall& s) {
     using HAMX = typename xposed_of<HAM>::type;
     static_assert(HAM::ND == 3, "transposed march: 3-D grids (4-D: hj_fused4v.h)");
-    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0 && !c->no_plain;
-    const int mode = plain ? (s.stage == HJ_STAGE_EULER ? 1 : 2) : 0;
+    const int mode = stage_mode(c, s);
     if constexpr (light_cfg(SCHEME, 3)) {
         // 512 threads x 2 pairs with the halo ring parked in LDS: the shape of the headline kernel
         const int nbuf = c->pair_ring == 0 ? 2 : 2 + c->pair_ah;

@@ -1,11 +1,111 @@
 // What every launch of a tiled substep kernel shares, whatever the Hamiltonian type: the chunk plan of the launch (second
-// plane range, edge ranges of a gated slab launch) and the FusedArgs block.  Used by the instantiations of hj_inst.hip
-// (built-in Hamiltonians) and by hj_rtc.hip (Hamiltonians compiled at run time with hipRTC).
+// plane range, edge ranges of a gated slab launch), the FusedArgs block, and the LAUNCH LAYER of the built-in kernels -- stage
+// class, occupancy, plan record, dynamic-LDS grant, enqueue, timing dump.  Used by the instantiations of hj_inst.hip / hj_instx.hip
+// (built-in Hamiltonians) and, for the plan and the arguments, by hj_rtc.hip (Hamiltonians compiled at run time with hipRTC).
 #pragma once
+#include <mutex>
 #include "hj_host.h"
 #include "hj_fused.h"
 
 namespace hjh {
+
+// MODE of the tiled kernels: plain RK stages (no clamp, no post-step operator, not ydot-only) run the flag-free instantiations -- 1 the
+// Euler stage, 2 the stages that blend with y0 -- and 0 carries every run-time flag.  (honour_no_plain = false: callers that never
+// read HJ_NO_PLAIN, hj_rtc.hip)
+inline int stage_mode(const hj_ctx* c, const SubstepCall& s, bool honour_no_plain = true) {
+    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0 && !(honour_no_plain && c->no_plain);
+    return plain ? (s.stage == HJ_STAGE_EULER ? 1 : 2) : 0;
+}
+
+// Resident workgroups per CU of (kernel, dynamic LDS bytes) on the context's device, asked once per context.  Planning without a device
+// estimates: the launch bound's waves per SIMD (occ_hint), and the CU's 160 KB of LDS -- and a planning look from a live context
+// (c->dry == 2) must not cache its estimate: it is not the device's answer.
+inline int wg_per_cu(hj_ctx* c, const void* kern, int nt, size_t lds_bytes, int occ_hint) {
+    const auto key = std::make_pair(kern, lds_bytes);
+    auto it = c->occ_cache.find(key);
+    if (it != c->occ_cache.end()) return it->second;
+    int nb = 0;
+    if (c->dry) nb = std::max(1, std::min(occ_hint * 256 / nt, (int)((size_t)(160 * 1024) / std::max<size_t>(1, lds_bytes))));
+    else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, nt, lds_bytes) != hipSuccess || nb < 1) nb = 1;
+    if (c->dry != 2) c->occ_cache.emplace(key, nb);
+    return nb;
+}
+
+// What hj_last_kernel / hj_last_tile / hj_launch_record report of a launch: chunk length and tile extents (E null: a kernel without tiles)
+inline void record_launch(hj_ctx* c, const char* name, const void* kern, int chunk = 0, const int* E = nullptr, int nd = 0) {
+    c->last_kernel = name;
+    c->note_kernel(kern);
+    c->last_E[0] = chunk;
+    for (int d = 1; d < HJ_MAX_DIM; ++d) c->last_E[d] = (E && d < nd) ? E[d] : 0;
+}
+// ... and what hj_plan_substep reports of a tiled launch; a dry context returns right after this
+inline void record_plan(hj_ctx* c, const Tiling& t, int nt, int occ_blocks, const char* name, const void* kern, int nd) {
+    c->last_plan.ntiles = t.ntiles; c->last_plan.nchunks = t.nchunks; c->last_plan.nblocks = t.nblocks; c->last_plan.threads = nt;
+    c->last_plan.wg_per_cu = occ_blocks; c->last_plan.lds_bytes = t.lds_bytes;
+    record_launch(c, name, kern, t.chunk, t.E, nd);
+}
+
+// More than 64 KB of dynamic LDS has to be granted to the function: once per (device, kernel), raised but never lowered -- the attribute
+// belongs to the function, not to a context.  One table for the whole library (an inline function's statics are shared by its objects).
+inline int grant_dynamic_lds(const hj_ctx* c, const void* kern, size_t lds_bytes) {
+    if (lds_bytes <= 64 * 1024) return HJ_OK;
+    static std::mutex mu;
+    static std::map<std::pair<int, const void*>, size_t> granted_by_kernel;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t& granted = granted_by_kernel[std::make_pair(c->device, kern)];
+    if (granted < lds_bytes) {
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        granted = lds_bytes;
+    }
+    return HJ_OK;
+}
+
+// The launch of a tiled substep kernel (y, y0, out, FusedArgs) on the call's stream, its LDS granted first
+template <typename K, typename T, int ND>
+int enqueue(hj_ctx* c, const SubstepCall& s, K kern, unsigned grid_blocks, int nt, size_t lds_bytes, const FusedArgs<T, ND>& A) {
+    const int rc = grant_dynamic_lds(c, reinterpret_cast<const void*>(kern), lds_bytes);
+    if (rc) return rc;
+    if (c->launch_stop) {
+        // completion signal attached to the dispatch packet itself: a separate hipEventRecord costs a
+        // marker packet and ~6 us of bubble before the next kernel of the stream (slab timeline)
+        hipExtLaunchKernelGGL(kern, dim3(grid_blocks), dim3(nt), (unsigned)lds_bytes, call_stream(c, s), nullptr, c->launch_stop, 0,
+                              (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
+        c->launch_stop = nullptr;
+    } else {
+        hipLaunchKernelGGL(kern, dim3(grid_blocks), dim3(nt), lds_bytes, call_stream(c, s), (const T*)s.y, (const T*)s.y0, (T*)s.out, A);
+    }
+    HIP_TRY(hipGetLastError());
+    return HJ_OK;
+}
+
+// HJ_TIMING_DUMP (read at ctx creation): per-workgroup start/end clocks of every launch.  timing_begin hands the launch its buffer
+// (FusedArgs::timing; null: no dump asked for), timing_end waits for the launch and appends its rows to the file
+// (tools/block_timing.py, tools/stamp_summary.py).
+inline int timing_begin(hj_ctx* c, const SubstepCall& s, int nblocks, unsigned long long*& tbuf) {
+    tbuf = nullptr;
+    if (!(c->timing_dump && *c->timing_dump)) return HJ_OK;
+    HIP_TRY(hipMalloc(&tbuf, (size_t)nblocks * 12 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(tbuf, 0, (size_t)nblocks * 12 * sizeof(unsigned long long), call_stream(c, s)));
+    return HJ_OK;
+}
+inline int timing_end(hj_ctx* c, const SubstepCall& s, const Tiling& t, unsigned long long* tbuf) {
+    if (!tbuf) return HJ_OK;
+    std::vector<unsigned long long> h((size_t)t.nblocks * 12);
+    HIP_TRY(hipStreamSynchronize(call_stream(c, s)));
+    HIP_TRY(hipMemcpy(h.data(), tbuf, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIP_TRY(hipFree(tbuf));
+    if (FILE* f = fopen(c->timing_dump, "a")) {
+        fprintf(f, "# launch nblocks=%d ntiles=%d chunk=%d stage=%d\n", t.nblocks, t.ntiles, t.chunk, s.stage);
+        for (int i = 0; i < t.nblocks; ++i) {
+            fprintf(f, "%d %llu %llu %llu %llu", i, h[4 * i], h[4 * i + 1], h[4 * i + 2], h[4 * i + 3]);
+            // HJ_STAMP builds: shader-clock sums of the four phases of wave 0 and of the last wave (else zeros)
+            const unsigned long long* ph = h.data() + 4 * (size_t)t.nblocks + 8 * (size_t)i;
+            fprintf(f, " %llu %llu %llu %llu %llu %llu %llu %llu\n", ph[0], ph[1], ph[2], ph[3], ph[4], ph[5], ph[6], ph[7]);
+        }
+        fclose(f);
+    }
+    return HJ_OK;
+}
 
 struct EdgePlan { int echunk = 0, ne[2] = {0, 0}, edge_count = 0; };
 

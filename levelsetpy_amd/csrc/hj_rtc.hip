@@ -378,9 +378,8 @@ static int launch_user_nd(hj_ctx* c, const SubstepCall& s, UserHam& u) {
     constexpr bool F32 = sizeof(T) == 4;
     const char* tname = F32 ? "float" : "double";
     HIP_TRY(hipSetDevice(c->device));        // the modules below belong to this device
-    // MODE 1 / 2: the flag-free instantiations of plain RK stages (hj_inst.hip, launch_tiled); 0: every run-time flag; 3: the range pass
-    const bool plain = s.stage != HJ_STAGE_YDOT && s.restrict_sign == 0 && s.post_op == 0;
-    const int mode = plain ? (s.stage == HJ_STAGE_EULER ? 1 : 2) : 0;
+    // MODE 1 / 2: the flag-free instantiations of plain RK stages (hj_launch.h, stage_mode; HJ_NO_PLAIN is not read here); 0: every run-time flag; 3: the range pass
+    const int mode = stage_mode(c, s, false);
     const bool light = light_scheme(s.scheme);
     const bool dynamic = (u.flags & HJ_HAM_RANGE) != 0;
     const int spill_key = ((F32 ? 1 : 0) * 8 + s.scheme) * 4 + mode;      // (scheme ids run to HJ_ENO3_FAST = 5: radix 8)

@@ -58,7 +58,7 @@ def case(rng, k):
             n = [int(rng.integers(340, 372)) for _ in range(3)]
         if rng.random() < 0.25:                      # round 6: THIN grids (few axis-0 planes, long axis 1): the library marches them along axis 1 by itself
             n = [int(rng.integers(8, 100)), int(rng.integers(300, 520)), int(rng.integers(180, 420))]
-            # a live context tries both forms in runs of six launches before it settles (hj_inst.hip, launch_scheme): enough steps to be in the middle of
+            # a live context tries both forms in runs of six launches before it settles (hj_inst.hip, xp_begin): enough steps to be in the middle of
             # that, or -- HJ_XP_TRIALS=0 -- the plan model alone, the transposed form from the first launch where it says so
             nsteps = int(rng.integers(2, 7))
             if rng.random() < 0.5:

@@ -24,7 +24,7 @@ STUB = "__device_stub__"
 SCHEME_NAMES = {0: "ENO2", 1: "ENO3", 2: "WENO5", 3: "WENO5_ASSHIPPED", 4: "ENO2_FAST", 5: "ENO3_FAST"}
 HAM_IDS = {"HamDubinsRel": 0, "HamDubinsRelX": 0, "HamDoubleIntegrator": 1, "HamDoublePendulum": 2}
 HAM_NDIM = {"HamDubinsRel": 3, "HamDubinsRelX": 3, "HamDoubleIntegrator": 2, "HamDoublePendulum": 4}
-# the stage a recipe runs for each stage class MODE of the tiled kernels (hj_inst.hip, launch_tiled): 0 carries the flags (ydot only,
+# the stage a recipe runs for each stage class MODE of the tiled kernels (hj_launch.h, stage_mode): 0 carries the flags (ydot only,
 # clamp, post-step operator), 1 is the plain Euler stage, 2 the plain stages that combine with y0
 MODE_STAGE = {0: _ffi.STAGE_YDOT, 1: _ffi.STAGE_EULER, 2: _ffi.STAGE_RK3_HALF}
 

@@ -543,7 +543,7 @@ def test_runtime_kernel_table_keeps_fast_eno_fp64_and_eno_fp32_apart():
 
 
 def test_thin_grids_take_the_transposed_march_by_default(monkeypatch):
-    """The auto rule (hj_api.hip xp_wanted: thin 3-D ranges without neighbours at the pair kernel's sizes; hj_inst.hip launch_scheme: the plan model,
+    """The auto rule (hj_api.hip xp_wanted: thin 3-D ranges without neighbours at the pair kernel's sizes; hj_inst.hip xp_prior / xp_begin: the plan model,
     then -- on a live context -- runs of both forms timed against each other): hj_rk_integrate ends up on the transposed launch BY ITSELF on a grid
     where it is ~20 % faster, gives the bits of the axis-0 march (HJ_XP=0) while it is still trying both, and HJ_XP_TRIALS=0 (the model alone) takes
     the transposed launch from the first call."""

@@ -1,5 +1,5 @@
 """round 6: axis-0 march against the transposed march on thin 3-D grids of several shapes (no neighbours), with the two launch plans beside
-the times -- the data the auto rule (hj_inst.hip, launch_scheme) is calibrated on.  argv: shapes as n0xn1xn2 ..."""
+the times -- the data the auto rule (hj_inst.hip, xp_prior) is calibrated on.  argv: shapes as n0xn1xn2 ..."""
 import os, sys, time, ctypes as C
 import numpy as np, torch
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "."))
