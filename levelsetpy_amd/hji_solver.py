@@ -8,7 +8,8 @@ previous step, data0, targets; obstacle masking) are hj_minmax_with, the NaN gua
 Stopping conditions (stopInit via multilinear point evaluation, stopSetInclude / stopSetIntersect with
 stopLevel, stopConverge with ignoreBoundary) and the discounting steps (default and 'Kene' mode,
 discountAnneal) are applied to the device-resident state as well; flipOutput reverses the stored time
-axis.  Visualisation, noise injection (addGaussianNoiseStandardDeviation) and trajectory extraction are
+axis.  extraArgs.computeTTR records the time-to-reach function of the solve on the device (ttr.py; extraOuts.TTR).
+Visualisation, noise injection (addGaussianNoiseStandardDeviation) and trajectory extraction are
 outside the path.
 
 Deviations from the shipped reference, all listed in SURVEY Appendix D: the integrator honours
@@ -223,6 +224,19 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
             data[0] = data0_host()
     cur_np = None if dev_in else first        # host copy of the current state: kept only where it is consumed (SDModFunc)
 
+    # ---- time to reach (ttr.py): recorded from data0 at tau[0] (a given history is folded first), then from the state at every
+    # tau[i] reached -- what TD2TTR gives for the stack of the same solve in store-all mode, without the stack
+    ttr_rec = None
+    if bool(_get(extraArgs, 'computeTTR', False)):
+        from .ttr import Recorder
+        ttr_rec = Recorder(_get(extraArgs, 'ttrLevel', 0.0), _get(extraArgs, 'ttrCrossing', 'first'),
+                           bool(_get(extraArgs, 'ttrInterpolate', False)))
+        if hist is None:
+            ttr_rec.record(first, tau[0])
+        else:
+            nh = min(istart, int(data0.shape[0]))
+            ttr_rec.fold(data0[:nh] if dev_in else hist[:nh], tau[:nh])
+
     plan = native_plan(schemeData, first)
     dg = device_grid(g, "float64") if plan is not None else None
     ops = _Ops(dg)
@@ -342,6 +356,8 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
             cur_np = cur.detach().cpu().numpy() if is_tensor(cur) else np.asarray(cur)
         if store_all:
             data[i] = cur_np
+        if ttr_rec is not None:
+            ttr_rec.record(cur, tau[i])
 
         def stop_here():
             extraOuts.stoptau = tau[i]
@@ -393,6 +409,8 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
         data = torch.as_tensor(data, device=data0.device)
     if flipOutput and store_all:
         data = data.flip(0) if is_tensor(data) else np.flip(data, 0).copy()
+    if ttr_rec is not None:
+        extraOuts.TTR = ttr_rec.result(g.shape, data0)
     endTime = cputime()
     if not quiet:
         info('Total execution time %s seconds' % (endTime - startTime))
