@@ -34,5 +34,6 @@ from .opt_traj import computeOptTraj, find_earliest_BRS_ind                     
 from .query import eval_u, eval_costate, proj, augmentPeriodicData             # noqa: F401
 from .surface import extract_level_set, level_set_measure, implicit_mesh       # noqa: F401
 from .ttr import postTimeStepTTR, TD2TTR                                        # noqa: F401
+from .rollout import computeOptTrajs                                            # noqa: F401
 
 __version__ = "0.1.0"

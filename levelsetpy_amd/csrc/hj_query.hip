@@ -10,8 +10,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cmath>
-#include "hj_device.h"
-#include "../../include/hj_query.h"
+#include "hj_query_dev.h"
 
 namespace hjq {
 
@@ -31,76 +30,6 @@ static int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                         \
         if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
     } while (0)
-
-constexpr int MAXD = HJ_MAX_DIM;
-
-// grid as the kernels see it (kernel argument: lives in SGPRs)
-struct QGrid {
-    int ndim;
-    int n[MAXD];
-    int per[MAXD];
-    long long stride[MAXD];
-    double xmin[MAXD], xlast[MAXD], dx[MAXD];
-};
-
-template <typename T> struct QStencil {
-    T km[MAXD];
-    T K[MAXD][hj::HJ_NK];
-};
-
-// cell index and weight of every axis; false when the state is outside an extrapolated axis (or not finite)
-__device__ __forceinline__ bool locate(const QGrid& G, const double* __restrict__ x, int* lo, double* w) {
-#pragma clang fp contract(off)
-    bool inside = true;
-    for (int d = 0; d < G.ndim; ++d) {
-        double xd = x[d];
-        const double vs0 = G.xmin[d], dx = G.dx[d];
-        const int n = G.n[d];
-        int i;
-        if (!(xd - xd == 0.0)) {          // NaN / inf state
-            inside = false;
-            xd = vs0;
-        }
-        if (G.per[d]) {
-            const double period = (double)n * dx;
-            double mod = fmod(xd - vs0, period);          // Python's %: the sign of the divisor
-            if (mod != 0.0) {
-                if (mod < 0.0) mod += period;
-            } else {
-                mod = 0.0;
-            }
-            xd = vs0 + mod;
-            i = (int)floor((xd - vs0) / dx);
-            if (i > n - 1) i = n - 1;
-        } else {
-            if (xd < vs0 || xd > G.xlast[d]) {
-                inside = false;
-                xd = vs0;
-            }
-            i = (int)floor((xd - vs0) / dx);
-            if (i > n - 2) i = n - 2;
-        }
-        if (i < 0) i = 0;
-        lo[d] = i;
-        w[d] = (xd - (vs0 + (double)i * dx)) / dx;
-    }
-    return inside;
-}
-
-// element offset and weight of corner `c`
-__device__ __forceinline__ double corner(const QGrid& G, const int* lo, const double* w, int c, long long& off) {
-#pragma clang fp contract(off)
-    double wt = 1.0;
-    off = 0;
-    for (int d = 0; d < G.ndim; ++d) {
-        const int up = (c >> d) & 1;
-        int j = lo[d] + up;
-        if (G.per[d] && j >= G.n[d]) j -= G.n[d];
-        off += (long long)j * G.stride[d];
-        wt *= up ? w[d] : (1.0 - w[d]);
-    }
-    return wt;
-}
 
 template <typename T>
 __device__ __forceinline__ void put(void* out, long long i, double v, int out_f64) {
@@ -139,46 +68,6 @@ __global__ __launch_bounds__(256) void interp_points_kernel(const T* __restrict_
 }
 
 // ---- (b) grad V at states
-template <typename T> __device__ __forceinline__ bool finite(T v) { return v - v == T(0); }
-// computeGradients' replacement of NaN / +-inf by a large number before the differences
-template <typename T> __device__ __forceinline__ T ld_work(const T* p) {
-    const T v = *p;
-    return finite(v) ? v : T(1e6);
-}
-
-// the seven values phi[i-3 .. i+3] along one axis of the node at `pc0` (index i on that axis), ghosts as the solver's
-// gather_stencils (hj_split.h): wrap on a periodic axis, ghost_value from the edge node and its inner neighbour otherwise
-template <typename T>
-__device__ __forceinline__ void gather_axis(const T* pc0, long long s, int i, int n, bool per, T km, T centre, T* v) {
-    bool ghost = false;
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-        if (k == 3) { v[k] = centre; continue; }
-        int j = i + k - 3;
-        if (j < 0) {
-            if (per) j += n; else { j = 0; ghost = true; }
-        } else if (j >= n) {
-            if (per) j -= n; else { j = n - 1; ghost = true; }
-        }
-        v[k] = ld_work(pc0 + (long long)(j - i) * s);
-    }
-    if (ghost) {
-        const T* line = pc0 - (long long)i * s;
-        if (i < HJ_STENCIL) {
-            const T e = ld_work(line), in = ld_work(line + s);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-                if (i + k - 3 < 0) v[k] = hj::ghost_value(e, in, T(3 - k - i) * km);
-        }
-        if (i + HJ_STENCIL >= n) {
-            const T e = ld_work(line + (long long)(n - 1) * s), in = ld_work(line + (long long)(n - 2) * s);
-#pragma unroll
-            for (int k = 4; k < 7; ++k)
-                if (i + k - 3 >= n) v[k] = hj::ghost_value(e, in, T(i + k - 3 - n + 1) * km);
-        }
-    }
-}
-
 struct CostateOut {
     void* costate;
     void* derivL;
@@ -186,18 +75,6 @@ struct CostateOut {
     void* value;
     int out_f64;
 };
-
-// the group's first lane adds the corners' terms in ascending corner number (the order of interp_points_kernel)
-__device__ __forceinline__ double group_sum(double term, int used, int lanes) {
-#pragma clang fp contract(off)
-    double v = 0.0;
-    for (int c = 0; c < lanes; ++c) {
-        const double p = __shfl(term, c, lanes);
-        const int u = __shfl(used, c, lanes);
-        if (u) v = v + p;
-    }
-    return v;
-}
 
 template <typename T, int SCHEME>
 __global__ __launch_bounds__(256) void costate_points_kernel(const T* __restrict__ data, long long field_stride, long long nfields,

@@ -1,0 +1,402 @@
+// libhj_rollout.so (include/hj_rollout.h): computeOptTraj for many initial states in one launch, for gfx950.
+//   rollout_kernel<T, SCHEME, PLANT>  2^ndim lanes per trajectory, as costate_points_kernel: lane c owns corner c of the cell
+//                                     that holds the state, every lane of the group carries the state redundantly, and the
+//                                     corners' terms are added by hj_query_dev.h's group_sum in ascending corner order.  An
+//                                     interpolated value or costate therefore has the bits interp_points_kernel and
+//                                     costate_points_kernel give for that state, and the trajectory the bits computeOptTraj
+//                                     gives with the built-in system's own methods (levelsetpy_amd/dynamics.py).
+// Control flow is uniform inside a group (every lane holds the same state, bounds and flags) and predicated across groups: a
+// finished trajectory sets `done` and idles through the remaining time stamps, it never returns or breaks, so every __shfl of
+// group_sum runs with all lanes of its group active.  State, weights, controls and dynamics are fp64 with contraction off;
+// the stencil arithmetic is T, as in the costate kernel.
+#include <hip/hip_runtime.h>
+#include <cstdarg>
+#include <cstdio>
+#include <cmath>
+#include "hj_query_dev.h"
+#include "../../include/hj_rollout.h"
+
+namespace hjr {
+
+using hjq::MAXD;
+using hjq::QGrid;
+using hjq::QStencil;
+
+static thread_local char g_err[512] = "";
+static thread_local const char* g_kernel = "";
+
+static int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
+    } while (0)
+
+// +1 for s >= 0, -1 for s < 0, NaN for NaN: an exact zero is deterministic, a NaN costate poisons the state
+__device__ __forceinline__ double sgn(double s) { return s >= 0.0 ? 1.0 : (s < 0.0 ? -1.0 : __builtin_nan("")); }
+
+// ---- the plants: controls(costate p, state x) -> (c0, c1), f(x; c0, c1) -> xdot.  One operation per statement.
+template <int ID> struct Plant;
+
+template <> struct Plant<HJ_HAM_DUBINS_REL> {
+    static constexpr int ND = 3;
+    // c0 = a, the evader's turn rate (the control); c1 = b, the pursuer's (the disturbance)
+    __device__ static __forceinline__ void controls(const hjr_plant& P, const double* p, const double* x, double& a, double& b) {
+#pragma clang fp contract(off)
+        const double w = P.params[2];
+        const double s1 = p[0] * x[1];
+        const double s2 = p[1] * x[0];
+        double s = s1 - s2;
+        s = s - p[2];
+        a = w * sgn(s);
+        if (P.u_mode == HJR_MODE_MIN) a = -a;
+        b = w * sgn(p[2]);
+        if (P.d_mode == HJR_MODE_MIN) b = -b;
+    }
+    __device__ static __forceinline__ void f(const hjr_plant& P, const double* x, double a, double b, double* k) {
+#pragma clang fp contract(off)
+        const double ve = P.params[0], vp = P.params[1];
+        const double c = cos(x[2]);
+        const double s = sin(x[2]);
+        const double vc = vp * c;
+        const double drift = -ve + vc;
+        const double ax2 = a * x[1];
+        k[0] = drift + ax2;
+        const double vs = vp * s;
+        const double ax1 = a * x[0];
+        k[1] = vs - ax1;
+        k[2] = b - a;
+    }
+};
+
+template <> struct Plant<HJ_HAM_DOUBLE_INTEGRATOR> {
+    static constexpr int ND = 2;
+    __device__ static __forceinline__ void controls(const hjr_plant& P, const double* p, const double* x, double& u, double& unused) {
+#pragma clang fp contract(off)
+        u = P.params[0] * sgn(p[1]);
+        if (P.u_mode == HJR_MODE_MIN) u = -u;
+        unused = 0.0;
+    }
+    __device__ static __forceinline__ void f(const hjr_plant& P, const double* x, double u, double, double* k) {
+        k[0] = x[1];
+        k[1] = u;
+    }
+};
+
+template <> struct Plant<HJ_HAM_DOUBLE_PENDULUM> {
+    static constexpr int ND = 4;
+    __device__ static __forceinline__ void controls(const hjr_plant& P, const double* p, const double* x, double& u1, double& u2) {
+#pragma clang fp contract(off)
+        u1 = P.params[0] * sgn(p[1]);
+        u2 = P.params[0] * sgn(p[3]);
+        if (P.u_mode == HJR_MODE_MIN) { u1 = -u1; u2 = -u2; }
+    }
+    // the drift in the expression order of DoublePendulum4D._drift (every product and sum left to right)
+    __device__ static __forceinline__ void f(const hjr_plant& P, const double* x, double u1, double u2, double* k) {
+#pragma clang fp contract(off)
+        constexpr double G = 9.8, L1 = 1.0, L2 = 1.0, M1 = 1.0, M2 = 1.0;
+        const double w1 = x[1], w2 = x[3];
+        const double s1 = sin(x[0]), c1 = cos(x[0]), s2 = sin(x[2]), c2 = cos(x[2]);
+        const double a0 = s2 * c1, a1 = c2 * s1;
+        const double sd = a0 - a1;
+        const double b0 = c2 * c1, b1 = s2 * s1;
+        const double cd = b0 + b1;
+        const double m12 = M1 + M2;
+        double t = M2 * L1; t = t * cd; t = t * cd;
+        const double den1 = m12 * L1 - t;
+        double q1 = M2 * L1; q1 = q1 * w1; q1 = q1 * w1; q1 = q1 * sd; q1 = q1 * cd;
+        double q2 = M2 * G; q2 = q2 * s2; q2 = q2 * cd;
+        double q3 = M2 * L2; q3 = q3 * w2; q3 = q3 * w2; q3 = q3 * sd;
+        double q4 = m12 * G; q4 = q4 * s1;
+        double n1 = q1 + q2; n1 = n1 + q3; n1 = n1 - q4;
+        const double f1 = n1 / den1;
+        const double den2 = (L2 / L1) * den1;
+        double r1 = -M2 * L2; r1 = r1 * w2; r1 = r1 * w2; r1 = r1 * sd; r1 = r1 * cd;
+        double r2 = m12 * G; r2 = r2 * s1; r2 = r2 * cd;
+        double r3 = m12 * L1; r3 = r3 * w1; r3 = r3 * w1; r3 = r3 * sd;
+        double r4 = m12 * G; r4 = r4 * s2;
+        double n3 = r1 + r2; n3 = n3 - r3; n3 = n3 - r4;
+        const double f3 = n3 / den2;
+        k[0] = w1;
+        k[1] = f1 + u1;
+        k[2] = w2;
+        k[3] = f3 + u2;
+    }
+};
+
+// one classical RK4 step with the controls held, in the expression order of the Python systems' update_state
+template <typename PL>
+__device__ __forceinline__ void rk4(const hjr_plant& P, double* x, double dt, double c0, double c1) {
+#pragma clang fp contract(off)
+    constexpr int N = PL::ND;
+    double k1[N], k2[N], k3[N], k4[N], xa[N];
+    const double h = 0.5 * dt;
+    PL::f(P, x, c0, c1, k1);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = h * k1[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k2);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = h * k2[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k3);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = dt * k3[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k4);
+    const double sixth = dt / 6.0;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        const double a = 2.0 * k2[d];
+        double s = k1[d] + a;
+        const double b = 2.0 * k3[d];
+        s = s + b;
+        s = s + k4[d];
+        s = sixth * s;
+        x[d] = x[d] + s;
+    }
+}
+
+struct RolloutOut {
+    double* traj;
+    int* length;
+    int* t_earliest;
+    int* status;
+};
+
+template <typename T, int SCHEME, int PLANT>
+__global__ __launch_bounds__(256) void rollout_kernel(const T* __restrict__ data, long long field_stride, int ntimes,
+                                                      const double* __restrict__ x0, long long M, QGrid G, QStencil<T> S,
+                                                      int sub_samples, double dt_small, hjr_plant P, RolloutOut O) {
+    using PL = Plant<PLANT>;
+    constexpr int ND = PL::ND;                     // == G.ndim (checked by the host)
+    constexpr int lanes = 1 << ND;                 // 4 .. 16: divides the wavefront, groups never straddle one
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long m = t / lanes;
+    const int c = (int)(t - m * lanes);
+    if (m >= M) return;                            // whole groups leave together
+    const double nan = __builtin_nan("");
+    const double small = 1e-4;
+    double x[MAXD];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) x[d] = d < ND ? x0[m * ND + d] : 0.0;
+
+    // where the state is: the cell, this lane's corner of it and the corner's weight
+    int lo[MAXD];
+    double w[MAXD];
+    bool inside;
+    long long off;
+    double wt;
+    int used;
+    auto find = [&]() {
+        inside = hjq::locate(G, x, lo, w);
+        wt = hjq::corner(G, lo, w, c, off);
+        used = wt != 0.0;
+    };
+    // V[f](x) in fp64: costate_points_kernel's `value`, the bits of interp_points_kernel
+    auto value_at = [&](int f) -> double {
+        T raw = T(0);
+        if (inside && used) raw = data[(long long)f * field_stride + off];
+        double p;
+        {
+#pragma clang fp contract(off)
+            p = wt * (double)raw;
+        }
+        const double v = hjq::group_sum(p, used, lanes);
+        return inside ? v : nan;
+    };
+    // grad V[f](x) in fp64: costate_points_kernel's `costate`
+    auto costate_at = [&](int f, double* p) {
+        T cC[ND];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) cC[d] = T(0);
+        if (inside && used) {
+            const T* pc0 = data + (long long)f * field_stride + off;
+            const T raw = *pc0;
+            if (!hjq::finite(raw)) {
+                // the node's own NaN / inf is put back after the differences (computeGradients: NaN stays NaN, +-inf becomes +inf)
+                const T back = raw != raw ? raw : T(__builtin_inf());
+#pragma unroll
+                for (int d = 0; d < ND; ++d) cC[d] = back;
+            } else {
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    int j = lo[d] + ((c >> d) & 1);
+                    if (G.per[d] && j >= G.n[d]) j -= G.n[d];
+                    T v[7];
+                    hjq::gather_axis<T>(pc0, G.stride[d], j, G.n[d], G.per[d] != 0, S.km[d], raw, v);
+                    T L, R;
+                    hj::upwind<SCHEME, T>(v, S.K[d], T(0), L, R);
+                    cC[d] = T(0.5) * (L + R);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            double q;
+            {
+#pragma clang fp contract(off)
+                q = wt * (double)cC[d];
+            }
+            const double sC = hjq::group_sum(q, used, lanes);
+            p[d] = inside ? sC : nan;
+        }
+    };
+
+    double* __restrict__ row = O.traj + m * ND * (long long)ntimes;         // traj[m][d][col] = row[d * ntimes + col]
+    int* __restrict__ te_row = O.t_earliest ? O.t_earliest + m * (long long)ntimes : nullptr;
+    find();
+    if (c == 0) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) row[d * (long long)ntimes] = x[d];
+    }
+    int tE = 0, len = 1;
+    bool done = false, reached = false, left = !inside;
+    for (int it = 0; it < ntimes - 1; ++it) {
+        // the largest index of [tE, ntimes-1] whose set holds x: only the visited slices are interpolated
+        const bool active = !done;
+        int lower = tE, upper = active ? ntimes - 1 : tE;
+        while (upper > lower) {
+            const int mid = (upper + lower + 1) / 2;
+            if (value_at(mid) < small) lower = mid;
+            else upper = mid - 1;
+        }
+        if (active) {
+            tE = upper;
+            if (tE == ntimes - 1) done = reached = true;
+        }
+        if (te_row && c == 0) te_row[it] = active ? tE : -1;
+        if (!done) {
+            for (int s = 0; s < sub_samples; ++s) {
+                double p[ND], c0, c1;
+                costate_at(tE, p);
+                PL::controls(P, p, x, c0, c1);
+                rk4<PL>(P, x, dt_small, c0, c1);
+                find();
+            }
+            len = it + 2;
+            left = left || !inside;
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) row[d * (long long)ntimes + it + 1] = done ? nan : x[d];
+        }
+    }
+    if (c == 0) {
+        if (te_row) te_row[ntimes - 1] = -1;
+        O.length[m] = len;
+        O.status[m] = left ? HJR_LEFT_GRID : (reached ? HJR_REACHED : HJR_EXHAUSTED);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+// the descriptor as the kernels see it (the checks of hj_query.hip's make_grid)
+static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
+    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
+    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    G.ndim = g->ndim;
+    total = 1;
+    for (int d = 0; d < MAXD; ++d) {
+        G.n[d] = 1; G.per[d] = 0; G.stride[d] = 0; G.xmin[d] = 0; G.xlast[d] = 0; G.dx[d] = 1;
+    }
+    for (int d = g->ndim - 1; d >= 0; --d) {
+        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
+            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
+        G.n[d] = (int)g->N[d];
+        G.per[d] = g->bc[d] == HJ_BC_PERIODIC;
+        G.stride[d] = total;
+        G.xmin[d] = g->xmin[d];
+        G.xlast[d] = g->xlast[d];
+        G.dx[d] = g->dx[d];
+        total *= g->N[d];
+    }
+    return HJ_OK;
+}
+
+template <typename T, int SCHEME, int PLANT>
+static int launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                  int64_t M, int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O, hipStream_t stream,
+                  const char* name) {
+    QStencil<T> S;
+    for (int d = 0; d < MAXD; ++d) {
+        S.km[d] = (d < G.ndim && g->toward_zero[d]) ? T(-1) : T(1);
+        hj::fill_stencil_constants<T>(G.dx[d], S.K[d]);
+    }
+    const long long b = ((long long)M * (1ll << G.ndim) + 255) / 256;
+    if (b > 0x7fffffffll) return fail(HJ_EINVAL, "too many trajectories for one launch");
+    hipLaunchKernelGGL((rollout_kernel<T, SCHEME, PLANT>), dim3((unsigned)b), dim3(256), 0, stream, (const T*)data,
+                       (long long)field_stride, (int)ntimes, x0, (long long)M, G, S, sub_samples, dt_small, P, O);
+    HIP_TRY(hipGetLastError());
+    g_kernel = name;
+    return HJ_OK;
+}
+
+}  // namespace hjr
+
+using namespace hjr;
+
+extern "C" {
+
+int hjr_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                int64_t nstates, int sub_samples, double dt_small, const hjr_plant* plant, double* traj, int32_t* length,
+                int32_t* t_earliest, int32_t* status, void* stream) {
+    QGrid G;
+    long long total;
+    int rc = make_grid(g, G, total);
+    if (rc) return rc;
+    if (!plant) return fail(HJ_EINVAL, "null plant descriptor");
+    if (nstates < 0) return fail(HJ_EINVAL, "nstates must not be negative");
+    if (ntimes < 2 || ntimes > 0x7fffffffll) return fail(HJ_EINVAL, "ntimes %lld: a rollout needs at least two stored sets", (long long)ntimes);
+    if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
+    if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
+    if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
+        return fail(HJ_EUNSUPPORTED, "scheme %d has no rollout kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
+    int nd;
+    switch (plant->id) {
+        case HJ_HAM_DUBINS_REL: nd = 3; break;
+        case HJ_HAM_DOUBLE_INTEGRATOR: nd = 2; break;
+        case HJ_HAM_DOUBLE_PENDULUM: nd = 4; break;
+        default: return fail(HJ_EUNSUPPORTED, "plant %d has no rollout kernel", (int)plant->id);
+    }
+    if (nd != G.ndim) return fail(HJ_EINVAL, "plant %d has %d states, the grid %d dimensions", (int)plant->id, nd, G.ndim);
+    if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
+        return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
+    for (int d = 0; d < G.ndim; ++d)
+        if (G.n[d] < HJ_STENCIL) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], HJ_STENCIL);
+    if (nstates == 0) return HJ_OK;
+    if (!data || !x0 || !traj || !length || !status) return fail(HJ_EINVAL, "null argument");
+    const RolloutOut O{traj, length, t_earliest, status};
+    hipStream_t s = (hipStream_t)stream;
+#define HJR_GO(T, SCH, PL) \
+    return launch<T, SCH, PL>(g, G, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, O, s, "rollout_kernel<" #T ", " #SCH ", " #PL ">")
+#define HJR_PLANTS(T, SCH)                     \
+    do {                                       \
+        if (plant->id == 0) HJR_GO(T, SCH, 0); \
+        if (plant->id == 1) HJR_GO(T, SCH, 1); \
+        HJR_GO(T, SCH, 2);                     \
+    } while (0)
+    static_assert(HJ_HAM_DUBINS_REL == 0 && HJ_HAM_DOUBLE_INTEGRATOR == 1 && HJ_HAM_DOUBLE_PENDULUM == 2, "plant ids name the kernels");
+    if (g->dtype == HJ_F64) {
+        if (scheme == HJ_ENO2) HJR_PLANTS(double, 0);
+        if (scheme == HJ_ENO3) HJR_PLANTS(double, 1);
+        HJR_PLANTS(double, 3);
+    }
+    if (scheme == HJ_ENO2) HJR_PLANTS(float, 0);
+    if (scheme == HJ_ENO3) HJR_PLANTS(float, 1);
+    HJR_PLANTS(float, 3);
+#undef HJR_PLANTS
+#undef HJR_GO
+}
+
+const char* hjr_last_error(void) { return g_err; }
+const char* hjr_last_kernel(void) { return g_kernel; }
+
+}  // extern "C"

@@ -7,13 +7,18 @@ Each class keeps the reference's callback protocol -- `.hamiltonian(t, data, der
 use with foreign terms / dissipation functions -- and additionally advertises `native()` =
 (ham_id, params): termLaxFriedrichs and odeCFLn then run the fused HIP kernels instead of
 calling back into Python.
+
+Each class also implements the dynSys protocol of computeOptTraj -- attribute `x`, dynamics(t, x, u, d),
+get_opt_u(t, deriv, uMode, x), get_opt_v(t, deriv, dMode, x), update_state(u, dt, x, d) -- with the dynamics its own
+Hamiltonian is the optimum of.  One state at a time, in fp64, one operation per statement: rollout_kernel
+(csrc/hj_rollout.hip) restates these methods, so computeOptTrajs and computeOptTraj give the same bits.
 """
 import numpy as np
 
 from . import _ffi
 from .context import is_tensor
 
-__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "native_of", "native_again"]
+__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "native_of", "native_again", "native_plant"]
 
 
 def native_again(system):
@@ -24,6 +29,36 @@ def native_again(system):
         par = att.params(system)            # (a traced pair re-traces here and may change its registration: the id is read after)
         return att.reg.ham_id, par
     return system.native()
+
+
+def _sgn(s):
+    """+1 for s >= 0, -1 for s < 0, NaN for NaN: an exact zero is deterministic, a NaN costate poisons the state."""
+    s = float(s)
+    return 1.0 if s >= 0 else (-1.0 if s < 0 else float('nan'))
+
+
+def _mode(mode, default=None):
+    if mode is None and default is not None:
+        mode = default
+    if mode not in ('min', 'max'):
+        raise ValueError("mode must be 'min' or 'max', not %r" % (mode,))
+    return mode
+
+
+def _state(x):
+    return np.asarray(x, dtype=np.float64).ravel()
+
+
+def _rk4(f, x, dt):
+    """One classical RK4 step of xdot = f(x): h = .5 dt, k2 = f(x + h k1), ..., x + dt/6 (k1 + 2 k2 + 2 k3 + k4) left to
+    right.  f returns an fp64 array; every array operation here is one rounding per element."""
+    x = _state(x)
+    h = .5 * dt
+    k1 = f(x)
+    k2 = f(x + h * k1)
+    k3 = f(x + h * k2)
+    k4 = f(x + dt * k3)
+    return x + dt / 6 * (k1 + 2 * k2 + 2 * k3 + k4)
 
 
 def _xs(grid, i, like):
@@ -94,6 +129,51 @@ class DubinsVehicleRel(object):
             return _abs(self.v_p * _sin(_xs(self.grid, 2, data))) + _abs(self.w(1) * _xs(self.grid, 0, data))
         return self.w_e + self.w_p
 
+    # ---- the dynSys protocol (scalar bounds): u = a, the evader's turn rate; d = b, the pursuer's.  H = -max_a min_b p.f
+    x = None
+
+    def _need_scalar(self):
+        if not self._scalar:
+            raise ValueError('DubinsVehicleRel: the dynSys protocol needs scalar u_bound and w_bound')
+
+    def dynamics(self, t, x, u, d):
+        self._need_scalar()
+        x = _state(x)
+        a, b = float(u), float(d)
+        x1, x2, x3 = float(x[0]), float(x[1]), float(x[2])
+        ve, vp = float(self.v_e), float(self.v_p)
+        vc = vp * float(np.cos(x3))
+        drift = -ve + vc
+        ax2 = a * x2
+        f1 = drift + ax2
+        vs = vp * float(np.sin(x3))
+        ax1 = a * x1
+        f2 = vs - ax1
+        f3 = b - a
+        return np.array([f1, f2, f3])
+
+    def get_opt_u(self, t, deriv, uMode, x):
+        self._need_scalar()
+        x = _state(x)
+        p1, p2, p3 = float(deriv[0]), float(deriv[1]), float(deriv[2])
+        s1 = p1 * float(x[1])
+        s2 = p2 * float(x[0])
+        s = s1 - s2
+        s = s - p3
+        a = float(self.w(1)) * _sgn(s)
+        return a if _mode(uMode) == 'max' else -a
+
+    def get_opt_v(self, t, deriv, dMode, x):
+        """dMode None: 'min', the pursuer of the class's own Hamiltonian."""
+        self._need_scalar()
+        b = float(self.w(1)) * _sgn(deriv[2])
+        return b if _mode(dMode, 'min') == 'max' else -b
+
+    def update_state(self, u, dt, x, d=None):
+        d = 0.0 if d is None else d
+        self.x = _rk4(lambda z: self.dynamics(None, z, u, d), x, dt)
+        return self.x
+
 
 class DoubleIntegrator(object):
     """double_integrator.py:9: xddot = u, |u| <= u_bound."""
@@ -128,6 +208,24 @@ class DoubleIntegrator(object):
         t2 = (-x2 + np.emath.sqrt(-4 * x1 + 2 * x2 ** 2)) * below
         t3 = np.abs(x2) * on
         return (t1 + t2 + t3).real
+
+    # ---- the dynSys protocol: f = (x2, u), no disturbance
+    x = None
+
+    def dynamics(self, t, x, u, d=None):
+        x = _state(x)
+        return np.array([float(x[1]), float(u)])
+
+    def get_opt_u(self, t, deriv, uMode, x):
+        u = float(self.control_law) * _sgn(deriv[1])
+        return u if _mode(uMode) == 'max' else -u
+
+    def get_opt_v(self, t, deriv, dMode, x):
+        return None
+
+    def update_state(self, u, dt, x, d=None):
+        self.x = _rk4(lambda z: self.dynamics(None, z, u), x, dt)
+        return self.x
 
 
 class DoublePendulum4D(object):
@@ -168,6 +266,36 @@ class DoublePendulum4D(object):
     def dissipation(self, t, data, derivMin, derivMax, sd, dim):
         return _abs(self._drift(data)[dim]) + (self.u_max if dim in (1, 3) else 0.0)
 
+    # ---- the dynSys protocol: f = drift(x) + (0, u1, 0, u2), u = (u1, u2), no disturbance
+    x = None
+
+    def dynamics(self, t, x, u, d=None):
+        """The drift at ONE state, in the expression order of _drift (products and sums left to right)."""
+        x = _state(x)
+        th1, w1, th2, w2 = float(x[0]), float(x[1]), float(x[2]), float(x[3])
+        G, L1, L2, M1, M2 = self.G, self.L1, self.L2, self.M1, self.M2
+        s1, c1, s2, c2 = float(np.sin(th1)), float(np.cos(th1)), float(np.sin(th2)), float(np.cos(th2))
+        sd, cd = s2 * c1 - c2 * s1, c2 * c1 + s2 * s1
+        den1 = (M1 + M2) * L1 - M2 * L1 * cd * cd
+        f1 = (M2 * L1 * w1 * w1 * sd * cd + M2 * G * s2 * cd + M2 * L2 * w2 * w2 * sd
+              - (M1 + M2) * G * s1) / den1
+        den2 = (L2 / L1) * den1
+        f3 = (-M2 * L2 * w2 * w2 * sd * cd + (M1 + M2) * G * s1 * cd
+              - (M1 + M2) * L1 * w1 * w1 * sd - (M1 + M2) * G * s2) / den2
+        return np.array([w1, f1 + float(u[0]), w2, f3 + float(u[1])])
+
+    def get_opt_u(self, t, deriv, uMode, x):
+        u1 = float(self.u_max) * _sgn(deriv[1])
+        u2 = float(self.u_max) * _sgn(deriv[3])
+        return (u1, u2) if _mode(uMode) == 'max' else (-u1, -u2)
+
+    def get_opt_v(self, t, deriv, dMode, x):
+        return None
+
+    def update_state(self, u, dt, x, d=None):
+        self.x = _rk4(lambda z: self.dynamics(None, z, u), x, dt)
+        return self.x
+
 
 def native_of(hamFunc, partialFunc):
     """(system, ham_id, params) when hamFunc/partialFunc are the bound methods of ONE of the
@@ -197,3 +325,19 @@ def native_of(hamFunc, partialFunc):
     if nat is None:
         return None
     return sys_h, nat[0], nat[1]
+
+
+_PROTOCOL = ("native", "dynamics", "get_opt_u", "get_opt_v", "update_state")
+
+
+def native_plant(dynSys):
+    """(ham_id, params) when rollout_kernel computes exactly what dynSys's dynSys-protocol methods would: an instance of
+    one of the systems above whose native() and protocol methods are the ones of the class that owns the kernel (the
+    identity rule of native_of: a subclass that overrides one of them is NOT native), with scalar bounds.  Else None."""
+    owner = next((k for k in (DubinsVehicleRel, DoubleIntegrator, DoublePendulum4D) if isinstance(dynSys, k)), None)
+    if owner is None or getattr(dynSys, "_hj_native", None) is not None:
+        return None
+    for name in _PROTOCOL:
+        if getattr(type(dynSys), name, None) is not getattr(owner, name) or name in getattr(dynSys, "__dict__", {}):
+            return None
+    return dynSys.native()

@@ -93,6 +93,8 @@ def _eval_point(g, data, x):
         vs = np.asarray(g.vs[d], dtype=np.float64).ravel()
         dx = float(np.asarray(g.dx).ravel()[d])
         xd = float(x[d])
+        if not np.isfinite(xd):
+            return float('nan')                                   # as interp_points_kernel: no cell holds such a state
         if bc[d] == _ffi.BC_PERIODIC:
             period = N[d] * dx
             xd = vs[0] + ((xd - vs[0]) % period)

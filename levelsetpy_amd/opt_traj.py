@@ -10,6 +10,8 @@ kernels) evaluated at the state by multilinear interpolation (eval_u semantics; 
 read from the device), and the system integrates its own dynamics over `subSamples` sub-steps.  dynSys
 protocol as the reference calls it (:124-131): attribute `x`; get_opt_u(t, deriv, uMode, x);
 get_opt_v(t, deriv, dMode, x) (optional); update_state(u, dt, x, d) returning / storing the new state.
+The built-in systems of dynamics.py implement it; extraArgs.derivFunc (default upwindFirstWENO5) chooses the costates' scheme.
+computeOptTrajs (rollout.py) is this function for many initial states in one launch.
 
 Deviations from the shipped reference, which cannot run: `find_earliest_BRS_ind` is commented out (:88, so
 the time index never advances), the disturbance branch reads an undefined `var` (:126), the loop bound
@@ -62,6 +64,8 @@ def computeOptTraj(g, data, tau, dynSys, extraArgs=None):
     uMode = extraArgs.uMode if isfield(extraArgs, 'uMode') else 'min'        # :40-46
     dMode = extraArgs.dMode if isfield(extraArgs, 'dMode') else None         # :48-49
     subSamples = int(extraArgs.subSamples) if isfield(extraArgs, 'subSamples') else 4   # :64-65
+    # the derivative function of the costates (no such option in the reference, which always takes its WENO5)
+    derivFunc = extraArgs.derivFunc if isfield(extraArgs, 'derivFunc') and extraArgs.derivFunc is not None else upwindFirstWENO5
     tau = np.asarray(tau, dtype=np.float64).ravel()
     if np.any(np.diff(tau) < 0):
         error('Time stamps must be in ascending order!')                     # :67-68
@@ -80,11 +84,11 @@ def computeOptTraj(g, data, tau, dynSys, extraArgs=None):
         BRS_at_t = data[tEarliest]                                           # :91
         # the costate at the state (:119): the 2^dim corner stencils only, one launch per sub-sample (eval_costate's
         # kernel); derivative functions it does not cover go through computeGradients as before
-        sid = _point_scheme(upwindFirstWENO5)
+        sid = _point_scheme(derivFunc)
         if sid is not None:
             onDevice = _device_data(BRS_at_t)                                # a NumPy table: this set goes over once per step
         else:
-            Deriv, _, _ = computeGradients(g, BRS_at_t)
+            Deriv, _, _ = computeGradients(g, BRS_at_t, derivFunc=derivFunc)
         for _ in range(subSamples):                                          # :121-131
             x = np.asarray(dynSys.x, dtype=np.float64).ravel()
             if sid is not None:
