@@ -35,5 +35,6 @@ from .query import eval_u, eval_costate, proj, augmentPeriodicData             #
 from .surface import extract_level_set, level_set_measure, implicit_mesh       # noqa: F401
 from .ttr import postTimeStepTTR, TD2TTR                                        # noqa: F401
 from .rollout import computeOptTrajs                                            # noqa: F401
+from .batch import HJIPDE_solve_batch                                           # noqa: F401
 
 __version__ = "0.1.0"

@@ -1,0 +1,520 @@
+// libhj_batch.so (include/hj_batch.h): B Hamilton-Jacobi problems on one grid, every RK stage ONE launch for all of them, for gfx950.
+//   batch_substep_kernel<T, HAM, SCHEME>  direct_substep_kernel (hj_split.h) with a problem axis: one thread per cell, every stencil load
+//                                         issued unconditionally, blockIdx.y the problem.  The grid, the coordinate and aux tables and the
+//                                         stage ride in the kernel arguments; what differs per problem -- the Hamiltonian's parameters, dt,
+//                                         the source / y0 / destination pointers, the post-step operators -- is read from a device table
+//                                         through blockIdx.y: wave-uniform plain loads.  A problem whose entry is inactive returns at once.
+//   batch_bound_kernel<T, HAM>            per problem, the per-dimension maxima of alpha at zero costate (alpha_bound_kernel's evaluation)
+//   batch_nan_kernel<T>                   per problem, "does the state hold a NaN"
+// The per-cell functions (gather_stencils, upwind_cd, HAM::cell / plane / eval, lf_ydot, rk_stage_out, post_step) are the solver's own
+// source, compiled with the solver's flags: a problem's result has the bits direct_substep_kernel gives for it alone.  The library links
+// nothing of libhj_mi355x.so.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+#include <vector>
+#include "hj_split.h"
+#include "../../include/hj_batch.h"
+
+namespace hjb {
+
+using namespace hj;
+
+static thread_local char g_err[512] = "";
+static thread_local const char* g_kernel = "";
+
+static int fail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t e_ = (expr);                                                                         \
+        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
+    } while (0)
+
+constexpr long long MAX_Y = 65535;      // gridDim.y of one launch
+
+static_assert(sizeof(hjb_entry) == 64, "hjb_entry is 64 bytes (include/hj_batch.h)");
+
+// what every problem of a launch shares
+template <typename T, int ND> struct BatchArgs {
+    GridArgs<T, ND> G;
+    T sc[ND];                          // costate scale of the scheme (hj_device.h)
+    const T* coord[HJ_MAX_DIM];
+    const T* aux[4];
+    const double* par;                 // HJB_PAR_SLOTS per problem, first problem of this launch
+    const hjb_entry* tab;              // one entry per problem, first problem of this launch
+    int stage, restrict_sign;
+};
+
+template <typename T, int ND>
+__device__ __forceinline__ HamTables<T> problem_tables(const T* const* coord, const T* const* aux, const double* par) {
+    HamTables<T> P;
+#pragma unroll
+    for (int d = 0; d < HJ_MAX_DIM; ++d) P.coord[d] = coord[d];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) P.aux[s] = aux[s];
+#pragma unroll
+    for (int s = 0; s < HJ_PAR_SLOTS; ++s) P.par[s] = (T)par[s];     // rounded as the solver's host side rounds them (fill_ham)
+    P.range = nullptr;
+    P.local_mode = 0;
+    return P;
+}
+
+// min / max against an array: minmax_kernel's expression (hj_split.h), NaN propagating as NumPy's minimum / maximum
+template <typename T>
+__device__ __forceinline__ T array_op(int op, T a, T b) {
+    T r;
+    if (a != a) r = a;
+    else if (b != b) r = b;
+    else if (op == HJB_ARR_MIN) r = a < b ? a : b;
+    else if (op == HJB_ARR_MAX) r = a > b ? a : b;
+    else r = a > -b ? a : -b;
+    return r;
+}
+
+template <typename T, typename HAM, int SCHEME>
+__global__ __launch_bounds__(256) void batch_substep_kernel(const BatchArgs<T, HAM::ND> A) {
+    constexpr int ND = HAM::ND;
+    constexpr bool NP = np_order(SCHEME);
+    static_assert(SCHEME != HJ_WENO5, "the intended WENO5 needs a per-problem epsilon reduction");
+    // the problem's entry: a uniform index, so these are scalar loads.  A finished problem leaves before anything of it is touched
+    const hjb_entry* __restrict__ e = A.tab + blockIdx.y;
+    if (e->active == 0) return;
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= A.G.total) return;
+    const HamTables<T> P = problem_tables<T, ND>(A.coord, A.aux, A.par + (long long)blockIdx.y * HJB_PAR_SLOTS);
+    const T* __restrict__ y = (const T*)e->src;
+    const T* __restrict__ y0 = (const T*)e->y0;
+    T* __restrict__ out = (T*)e->dst;
+    const T dt = (T)e->dt;
+    const int stage = A.stage;
+    T eps[ND];
+    WenoK<T> wk[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        eps[d] = T(0);
+        wk[d].c13 = T(0); wk[d].c4 = T(0);
+    }
+    T ca = T(0), cb = T(1);
+    if (stage == HJ_STAGE_RK3_HALF) { ca = T(0.75); cb = T(0.25); }
+    else if (stage == HJ_STAGE_RK3_FULL) { ca = T(1.0 / 3.0); cb = T(2.0 / 3.0); }
+    else if (stage == HJ_STAGE_RK2_FULL) { ca = T(0.5); cb = T(0.5); }
+    const bool use_y0 = stage >= HJ_STAGE_RK3_HALF;
+    int idx[ND];
+    decode<T, ND>(A.G, t, idx);
+    const T* pc0 = y + t;
+    T v[ND][7];
+    const T centre = pc0[0];
+    const T y0v = use_y0 ? y0[t] : T(0);
+    const typename HAM::Cell hc = HAM::cell(P, idx, A.sc);
+    const typename HAM::Plane hp = HAM::plane(P, idx[0], A.sc);
+    gather_stencils<T, ND>(A.G, pc0, idx, centre, v);
+    T pc[ND], hd[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], eps[d], wk[d], pc[d], hd[d]);
+    T alpha[ND];
+    T ydot = lf_ydot<NP, HAM>(P, hc, hp, A.sc, pc, hd, alpha);
+    // termRestrictUpdate clamp, written like direct_substep_kernel's (a NaN stays a NaN)
+    if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
+    else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
+    T o;
+    if (stage == HJ_STAGE_YDOT) o = ydot;
+    else {
+        o = rk_stage_out<NP>(stage, ca, cb, dt, y0v, centre, ydot);
+        if (e->post_prev) o = post_step(e->post_prev, o, use_y0 ? y0v : centre);
+        if (e->op_a) o = array_op(e->op_a, o, ((const T*)e->post_a)[t]);
+        if (e->op_b) o = array_op(e->op_b, o, ((const T*)e->post_b)[t]);
+    }
+    out[t] = o;
+}
+
+// max over the grid of alpha_d at zero costate, per problem: the evaluation of alpha_bound_kernel (hj_split.h) -- HAM::eval with unit scales --
+// one workgroup maximum per dimension folded into keys[problem][d] (order-preserving keys, zero at launch)
+template <typename T, typename HAM>
+__global__ __launch_bounds__(256) void batch_bound_kernel(const GridArgs<T, HAM::ND> G, const hjb_tables tab, const double* par,
+                                                         unsigned long long* keys) {
+    constexpr int ND = HAM::ND;
+    const HamTables<T> P = problem_tables<T, ND>((const T* const*)tab.coord, (const T* const*)tab.aux, par + (long long)blockIdx.y * HJB_PAR_SLOTS);
+    double m[ND];
+    T one[ND], p[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) { m[d] = -1e300; one[d] = T(1); p[d] = T(0); }
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < G.total; t += (long long)gridDim.x * blockDim.x) {
+        int idx[ND];
+        decode<T, ND>(G, t, idx);
+        T H, a[ND];
+        HAM::eval(P, HAM::cell(P, idx, one), HAM::plane(P, idx[0], one), one, p, H, a);
+#pragma unroll
+        for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
+    }
+    __shared__ double red[4][ND];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const double w = wave_max(m[d]);
+        if (lane == 0) red[wv][d] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < ND) {
+        const int d = threadIdx.x;
+        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
+        if (w > -1e299) key_max(keys + (long long)blockIdx.y * HJ_MAX_DIM + d, w);
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void batch_nan_kernel(const hjb_entry* tab, long long n, int* flags) {
+    const hjb_entry* e = tab + blockIdx.y;
+    if (e->active == 0) return;
+    const T* __restrict__ y = (const T*)e->src;
+    bool bad = false;
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < n; t += (long long)gridDim.x * blockDim.x) {
+        const T a = y[t];
+        bad = bad || (a != a);
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(flags + blockIdx.y, 1);
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+static int ham_ndim(int ham) {
+    return ham == HJ_HAM_DUBINS_REL ? 3 : (ham == HJ_HAM_DOUBLE_INTEGRATOR ? 2 : (ham == HJ_HAM_DOUBLE_PENDULUM ? 4 : 0));
+}
+
+// the checks every entry point makes on (grid, tables, system); total = the number of cells
+static int check_setup(const hjq_grid* g, const hjb_tables* tab, int ham, long long& total) {
+    if (!g || !tab) return fail(HJ_EINVAL, "null grid descriptor or tables");
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    const int nd = ham_ndim(ham);
+    if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no batched kernel (the three built-in systems only)", ham);
+    if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
+    total = 1;
+    for (int d = 0; d < nd; ++d) {
+        if (g->N[d] < HJ_STENCIL || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range (need %d .. 2^30)", d, (long long)g->N[d], HJ_STENCIL);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d])) return fail(HJ_EINVAL, "axis %d: dx must be positive and finite", d);
+        if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
+        total *= g->N[d];
+        if (total > (1ll << 38)) return fail(HJ_EINVAL, "grid too large");
+    }
+    const int naux = ham == HJ_HAM_DUBINS_REL ? 2 : (ham == HJ_HAM_DOUBLE_PENDULUM ? 4 : 0);
+    for (int s = 0; s < naux; ++s)
+        if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
+    return HJ_OK;
+}
+
+// fill_grid of the solver (hj_host.h) from the descriptor: a single domain, no slab halos
+template <typename T, int ND> static void fill_grid(const hjq_grid* g, GridArgs<T, ND>& G) {
+    long long s = 1;
+    for (int d = ND - 1; d >= 0; --d) {
+        G.n[d] = (int)g->N[d];
+        G.bc[d] = g->bc[d];
+        G.km[d] = g->toward_zero[d] ? T(-1) : T(1);
+        G.inv_dx[d] = (T)(1.0 / g->dx[d]);
+        fill_stencil_constants<T>(g->dx[d], G.K[d]);
+        G.stride[d] = s;
+        s *= g->N[d];
+    }
+    G.halo_lo = 0;
+    G.halo_hi = 0;
+    G.total = s;
+}
+
+template <typename T, typename HAM, int SCHEME>
+static int launch_substep(const hjq_grid* g, const hjb_tables* tab, int stage, int restrict_sign, const double* params,
+                          const hjb_entry* entries, int64_t B, hipStream_t stream, const char* name) {
+    constexpr int ND = HAM::ND;
+    BatchArgs<T, ND> A;
+    memset(&A, 0, sizeof(A));
+    fill_grid<T, ND>(g, A.G);
+    for (int d = 0; d < ND; ++d) A.sc[d] = scheme_scale<T>(SCHEME, g->dx[d]);
+    for (int d = 0; d < HJ_MAX_DIM; ++d) A.coord[d] = (const T*)tab->coord[d];
+    for (int s = 0; s < 4; ++s) A.aux[s] = (const T*)tab->aux[s];
+    A.stage = stage;
+    A.restrict_sign = restrict_sign;
+    const long long bx = (A.G.total + 255) / 256;
+    if (bx > 0x7fffffffll) return fail(HJ_EINVAL, "grid too large for one thread per cell");
+    for (int64_t off = 0; off < B; off += MAX_Y) {
+        const int64_t nb = std::min<int64_t>(MAX_Y, B - off);
+        A.par = params + off * HJB_PAR_SLOTS;
+        A.tab = entries + off;
+        hipLaunchKernelGGL((batch_substep_kernel<T, HAM, SCHEME>), dim3((unsigned)bx, (unsigned)nb), dim3(256), 0, stream, A);
+        HIP_TRY(hipGetLastError());
+    }
+    g_kernel = name;
+    return HJ_OK;
+}
+
+static int dispatch_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, int stage, int restrict_sign,
+                            const double* params, const hjb_entry* entries, int64_t B, hipStream_t stream) {
+#define HJB_GO(T, HAM, SCH) \
+    return launch_substep<T, HAM<T>, SCH>(g, tab, stage, restrict_sign, params, entries, B, stream, "batch_substep_kernel<" #T ", " #HAM ", " #SCH ">")
+#define HJB_HAMS(T, SCH)                                                \
+    do {                                                                \
+        if (ham == HJ_HAM_DUBINS_REL) HJB_GO(T, HamDubinsRel, SCH);     \
+        if (ham == HJ_HAM_DOUBLE_INTEGRATOR) HJB_GO(T, HamDoubleIntegrator, SCH); \
+        HJB_GO(T, HamDoublePendulum, SCH);                              \
+    } while (0)
+    static_assert(HJ_ENO2 == 0 && HJ_ENO3 == 1 && HJ_WENO5_ASSHIPPED == 3, "scheme ids name the kernels");
+    if (g->dtype == HJ_F64) {
+        if (scheme == HJ_ENO2) HJB_HAMS(double, 0);
+        if (scheme == HJ_ENO3) HJB_HAMS(double, 1);
+        HJB_HAMS(double, 3);
+    }
+    if (scheme == HJ_ENO2) HJB_HAMS(float, 0);
+    if (scheme == HJ_ENO3) HJB_HAMS(float, 1);
+    HJB_HAMS(float, 3);
+#undef HJB_HAMS
+#undef HJB_GO
+}
+
+static int check_scheme(int scheme) {
+    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
+        return fail(HJ_EUNSUPPORTED, "scheme %d has no batched kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
+    return HJ_OK;
+}
+
+template <typename T, typename HAM>
+static int launch_bound(const hjq_grid* g, const hjb_tables* tab, const double* params, int64_t B, unsigned long long* keys,
+                        hipStream_t stream) {
+    constexpr int ND = HAM::ND;
+    GridArgs<T, ND> G;
+    memset(&G, 0, sizeof(G));
+    fill_grid<T, ND>(g, G);
+    const unsigned bx = (unsigned)std::min<long long>((G.total + 255) / 256, 64);
+    for (int64_t off = 0; off < B; off += MAX_Y) {
+        const int64_t nb = std::min<int64_t>(MAX_Y, B - off);
+        hipLaunchKernelGGL((batch_bound_kernel<T, HAM>), dim3(bx, (unsigned)nb), dim3(256), 0, stream, G, *tab,
+                           params + off * HJB_PAR_SLOTS, keys + off * HJ_MAX_DIM);
+        HIP_TRY(hipGetLastError());
+    }
+    g_kernel = "batch_bound_kernel";
+    return HJ_OK;
+}
+
+static double key_to_double(unsigned long long k) {
+    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+
+// the time a step of `order` from t with deltaT = dt reaches: the expressions of hj_rk_step (ode_cfl_1/2/3.py)
+static double step_time(int order, double t0, double dt) {
+    if (order == 1) return t0 + dt;
+    const double t1 = t0 + dt, t2 = t1 + dt;
+    if (order == 2) return 0.5 * (t0 + t2);
+    const double tHalf = 0.25 * (3 * t0 + t2);
+    const double tThreeHalf = tHalf + dt;
+    return (1.0 / 3.0) * (t0 + 2 * tThreeHalf);
+}
+
+// one problem's steps over [t0, tf]: dts gets deltaT of every step (may be null), t the time reached
+static int plan_problem(int order, double sb, double t0, double tf, double factor_cfl, double max_step, double stop_tol,
+                        std::vector<double>* dts, double& t, int64_t b) {
+    // the loop of odeCFLn (ode_cfl_3.py:125): while tf - t >= small*|tf|, small = 100*eps (:81); stop_tol >= 0: HJIPDE_solve's
+    const double small = 100.0 * 2.220446049250313e-16;
+    t = t0;
+    int64_t steps = 0;
+    auto more = [&]() { return stop_tol < 0 ? (tf - t >= small * std::fabs(tf)) : (t < tf - stop_tol); };
+    if (!(sb > 0.0)) return fail(HJ_EINVAL, "problem %lld: the step bound must be positive (got %g)", (long long)b, sb);
+    while (more()) {
+        // deltaT = min(factorCFL*stepBound, tspan[1]-t, maxStep)  (ode_cfl_3.py:142)
+        const double dt = std::min(std::min(factor_cfl * sb, tf - t), max_step);
+        const double tn = step_time(order, t, dt);
+        if (!(tn > t)) return fail(HJ_ESTATE, "problem %lld: time step underflow at t=%g (dt=%g)", (long long)b, t, dt);
+        if (++steps > (1ll << 24)) return fail(HJ_ESTATE, "problem %lld: more than 2^24 steps in one interval", (long long)b);
+        if (dts) dts->push_back(dt);
+        t = tn;
+    }
+    return HJ_OK;
+}
+
+}  // namespace hjb
+
+using namespace hjb;
+
+extern "C" {
+
+int hjb_step_bounds(const hjq_grid* g, const hjb_tables* tab, int ham, const double* params, int64_t B, void* keys,
+                    double* sb_host, double* amax_host, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, total);
+    if (rc) return rc;
+    if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
+    if (B == 0) return HJ_OK;
+    if (!params || !keys || !sb_host) return fail(HJ_EINVAL, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* k = (unsigned long long*)keys;
+    HIP_TRY(hipMemsetAsync(k, 0, sizeof(unsigned long long) * HJ_MAX_DIM * (size_t)B, s));
+#define HJB_B(T)                                                                                                   \
+    rc = ham == HJ_HAM_DUBINS_REL ? launch_bound<T, HamDubinsRel<T>>(g, tab, params, B, k, s)                       \
+       : ham == HJ_HAM_DOUBLE_INTEGRATOR ? launch_bound<T, HamDoubleIntegrator<T>>(g, tab, params, B, k, s)         \
+                                         : launch_bound<T, HamDoublePendulum<T>>(g, tab, params, B, k, s)
+    if (g->dtype == HJ_F64) HJB_B(double);
+    else HJB_B(float);
+#undef HJB_B
+    if (rc) return rc;
+    std::vector<unsigned long long> h((size_t)B * HJ_MAX_DIM);
+    HIP_TRY(hipMemcpyAsync(h.data(), k, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int64_t b = 0; b < B; ++b) {
+        // stepBound = 1 / sum_d max alpha_d / dx_d, summed in dimension order (hj_static_step_bound)
+        double inv = 0.0;
+        for (int d = 0; d < g->ndim; ++d) {
+            const double a = key_to_double(h[(size_t)b * HJ_MAX_DIM + d]);
+            if (amax_host) amax_host[b * HJ_MAX_DIM + d] = a;
+            inv += a / g->dx[d];
+        }
+        for (int d = g->ndim; d < HJ_MAX_DIM && amax_host; ++d) amax_host[b * HJ_MAX_DIM + d] = 0.0;
+        sb_host[b] = 1.0 / inv;
+    }
+    return HJ_OK;
+}
+
+int hjb_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, int stage, int restrict_sign,
+                const double* params, const hjb_entry* entries, int64_t B, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, total);
+    if (rc) return rc;
+    if ((rc = check_scheme(scheme))) return rc;
+    if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
+    if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
+    if (B == 0) return HJ_OK;
+    if (!params || !entries) return fail(HJ_EINVAL, "null argument");
+    return dispatch_substep(g, tab, scheme, ham, stage, restrict_sign, params, entries, B, (hipStream_t)stream);
+}
+
+int hjb_plan(int order, const double* sb_host, int64_t B, double t0, double tf, double factor_cfl, double max_step,
+             double stop_tol, double* t_host, int64_t* steps_host) {
+    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    if (B < 0 || (B > 0 && !sb_host)) return fail(HJ_EINVAL, "null argument");
+    for (int64_t b = 0; b < B; ++b) {
+        std::vector<double> dts;
+        double t;
+        int rc = plan_problem(order, sb_host[b], t0, tf, factor_cfl, max_step, stop_tol, &dts, t, b);
+        if (rc) return rc;
+        if (t_host) t_host[b] = t;
+        if (steps_host) steps_host[b] = (int64_t)dts.size();
+    }
+    return HJ_OK;
+}
+
+int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, int order, int restrict_sign, int post_prev,
+                  const double* params, const double* sb_host, const hjb_problem* problems_host, int64_t B, double t0,
+                  double tf, double factor_cfl, double max_step, double stop_tol, void* table, int64_t table_bytes,
+                  double* t_host, int64_t* steps_host, int32_t* result_in_host, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, total);
+    if (rc) return rc;
+    if ((rc = check_scheme(scheme))) return rc;
+    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
+    if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
+    if (B == 0) return HJ_OK;
+    if (!params || !sb_host || !problems_host) return fail(HJ_EINVAL, "null argument");
+    std::vector<std::vector<double>> dts((size_t)B);
+    std::vector<double> tend((size_t)B);
+    int64_t nmax = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        const hjb_problem& p = problems_host[b];
+        if (!p.y_in || !p.buf_a || !p.buf_b) return fail(HJ_EINVAL, "problem %lld: null buffer", (long long)b);
+        if (order >= 2 && !p.work) return fail(HJ_EINVAL, "problem %lld: work buffer required for order >= 2", (long long)b);
+        if (p.buf_a == p.buf_b || p.buf_a == p.y_in || p.buf_b == p.y_in || p.work == p.y_in || p.work == p.buf_a || p.work == p.buf_b)
+            return fail(HJ_EINVAL, "problem %lld: buffers must be distinct", (long long)b);
+        if (p.op_a < HJB_ARR_NONE || p.op_a > HJB_ARR_MAX_NEG || p.op_b < HJB_ARR_NONE || p.op_b > HJB_ARR_MAX_NEG)
+            return fail(HJ_EINVAL, "problem %lld: unknown array operator", (long long)b);
+        if ((p.op_a && !p.post_a) || (p.op_b && !p.post_b)) return fail(HJ_EINVAL, "problem %lld: an array operator without its array", (long long)b);
+        if ((rc = plan_problem(order, sb_host[b], t0, tf, factor_cfl, max_step, stop_tol, &dts[(size_t)b], tend[(size_t)b], b))) return rc;
+        nmax = std::max<int64_t>(nmax, (int64_t)dts[(size_t)b].size());
+    }
+    const int64_t launches = nmax * order;
+    const int64_t need = launches * B * (int64_t)sizeof(hjb_entry);
+    if (launches > 0 && (!table || table_bytes < need))
+        return fail(HJ_EINVAL, "the schedule needs %lld bytes of table (%lld launches x %lld problems), got %lld", (long long)need,
+                    (long long)launches, (long long)B, (long long)table_bytes);
+    hipStream_t s = (hipStream_t)stream;
+    if (launches > 0) {
+        // entry (step k, stage j, problem b) at [(k*order + j)*B + b]; zero = inactive
+        std::vector<hjb_entry> sched((size_t)(launches * B));
+        memset(sched.data(), 0, sched.size() * sizeof(hjb_entry));
+        for (int64_t b = 0; b < B; ++b) {
+            const hjb_problem& p = problems_host[b];
+            void* outs[2] = {p.buf_a, p.buf_b};
+            const void* cur = p.y_in;
+            const int64_t n = (int64_t)dts[(size_t)b].size();
+            for (int64_t k = 0; k < n; ++k) {
+                void* nxt = outs[k & 1];
+                hjb_entry* e = &sched[(size_t)((k * order) * B + b)];
+                // RK3: the first stage buffer doubles as the output; RK2: `work` is the first stage buffer (hj_rk_integrate)
+                if (order == 1) { e[0].src = cur; e[0].dst = nxt; }
+                else if (order == 2) {
+                    e[0].src = cur; e[0].dst = p.work;
+                    e[B].src = p.work; e[B].y0 = cur; e[B].dst = nxt;
+                } else {
+                    e[0].src = cur; e[0].dst = nxt;
+                    e[B].src = nxt; e[B].y0 = cur; e[B].dst = p.work;
+                    e[2 * B].src = p.work; e[2 * B].y0 = cur; e[2 * B].dst = nxt;
+                }
+                for (int j = 0; j < order; ++j) { e[j * B].dt = dts[(size_t)b][(size_t)k]; e[j * B].active = 1; }
+                hjb_entry& last = e[(order - 1) * B];
+                last.post_prev = post_prev;
+                last.post_a = p.op_a ? p.post_a : nullptr; last.op_a = p.op_a;
+                last.post_b = p.op_b ? p.post_b : nullptr; last.op_b = p.op_b;
+                cur = nxt;
+            }
+        }
+        // ONE copy for the whole interval; the wait keeps `sched` alive until the copy has read it
+        HIP_TRY(hipMemcpyAsync(table, sched.data(), sched.size() * sizeof(hjb_entry), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        static const int stages[3][3] = {{HJ_STAGE_EULER, 0, 0}, {HJ_STAGE_EULER, HJ_STAGE_RK2_FULL, 0},
+                                         {HJ_STAGE_EULER, HJ_STAGE_RK3_HALF, HJ_STAGE_RK3_FULL}};
+        for (int64_t l = 0; l < launches; ++l) {
+            rc = dispatch_substep(g, tab, scheme, ham, stages[order - 1][l % order], restrict_sign, params,
+                                  (const hjb_entry*)table + l * B, B, s);
+            if (rc) return rc;
+        }
+    }
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t n = (int64_t)dts[(size_t)b].size();
+        if (t_host) t_host[b] = tend[(size_t)b];
+        if (steps_host) steps_host[b] = n;
+        if (result_in_host) result_in_host[b] = n == 0 ? 0 : 1 + (int32_t)((n - 1) & 1);
+    }
+    return HJ_OK;
+}
+
+int hjb_nan_flags(int dtype, const hjb_entry* entries, int64_t B, int64_t n, int32_t* flags, void* stream) {
+    if (dtype != HJ_F64 && dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", dtype);
+    if (B < 0 || n < 0) return fail(HJ_EINVAL, "B and n must not be negative");
+    if (B == 0) return HJ_OK;
+    if (!entries || !flags) return fail(HJ_EINVAL, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    HIP_TRY(hipMemsetAsync(flags, 0, sizeof(int32_t) * (size_t)B, s));
+    if (n == 0) return HJ_OK;
+    const unsigned bx = (unsigned)std::min<long long>((n + 255) / 256, 64);
+    for (int64_t off = 0; off < B; off += MAX_Y) {
+        const int64_t nb = std::min<int64_t>(MAX_Y, B - off);
+        if (dtype == HJ_F64)
+            hipLaunchKernelGGL((batch_nan_kernel<double>), dim3(bx, (unsigned)nb), dim3(256), 0, s, entries + off, (long long)n, (int*)flags + off);
+        else
+            hipLaunchKernelGGL((batch_nan_kernel<float>), dim3(bx, (unsigned)nb), dim3(256), 0, s, entries + off, (long long)n, (int*)flags + off);
+        HIP_TRY(hipGetLastError());
+    }
+    g_kernel = dtype == HJ_F64 ? "batch_nan_kernel<double>" : "batch_nan_kernel<float>";
+    return HJ_OK;
+}
+
+const char* hjb_last_error(void) { return g_err; }
+const char* hjb_last_kernel(void) { return g_kernel; }
+
+}  // extern "C"

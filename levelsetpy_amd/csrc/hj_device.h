@@ -148,6 +148,14 @@ template <typename T> inline void fill_stencil_constants(double dx, T* K) {
     K[6] = (T)(45 * c); K[7] = (T)(-9 * c); K[8] = (T)c;
     K[9] = (T)(15 * c); K[10] = (T)(-6 * c); K[11] = (T)(-20 * c);
 }
+// costate scale the scheme's stencil leaves out (scaling note at the Hamiltonians below).  Host side, here beside the stencil constants
+// because every library that launches a substep kernel fills it (libhj_mi355x.so, libhj_batch.so)
+template <typename T> inline T scheme_scale(int scheme, double dx) {
+    if (scheme == HJ_WENO5_ASSHIPPED) return (T)((1.0 / dx) * (1.0 / 60.0));
+    if (scheme == HJ_WENO5) return (T)((1.0 / dx) * (1.0 / 12.0));
+    if (lean_eno(scheme)) return (T)((1.0 / dx) * 0.5);     // lean ENO2 / ENO3: costates on undivided differences, p = q/(2dx)
+    return T(1);                      // ENO2 / ENO3 on the reference's divided-difference tables: true costates
+}
 
 template <typename T>
 __device__ __forceinline__ void dd_tables(const T* v, const T* K, DD<T>& t) {

@@ -278,14 +278,6 @@ template <typename T, int ND> void fill_grid(const hj_ctx* c, GridArgs<T, ND>& G
     G.total = c->total;
 }
 
-// costate scale the scheme's stencil leaves out (hj_device.h, scaling note)
-template <typename T> T scheme_scale(int scheme, double dx) {
-    if (scheme == HJ_WENO5_ASSHIPPED) return (T)((1.0 / dx) * (1.0 / 60.0));
-    if (scheme == HJ_WENO5) return (T)((1.0 / dx) * (1.0 / 12.0));
-    if (lean_eno(scheme)) return (T)((1.0 / dx) * 0.5);     // lean ENO2 / ENO3: costates on undivided differences, p = q/(2dx)
-    return T(1);                      // ENO2 / ENO3 on the reference's divided-difference tables: true costates
-}
-
 struct SubstepCall {
     int scheme, ham, stage, restrict_sign;
     const double* par;
