@@ -5,7 +5,7 @@ hot path, behind the reference's own names and callback protocol:
         ->  upwindFirstENO2 / ENO3 / WENO5  +  artificialDissipationGLF  +  addGhost*
 
 All arithmetic on the path runs in hand-written HIP kernels (csrc/, C ABI in
-include/hj_mi355x.h, bound with ctypes).  There is no CPU fallback.
+include/hj_mi355x.h, bound with ctypes).  The package has no CPU fallback.
 """
 from .utilities import *            # noqa: F401,F403
 from .boundary import addGhostExtrapolate, addGhostPeriodic, addGhostAllDims   # noqa: F401

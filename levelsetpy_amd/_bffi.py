@@ -1,23 +1,18 @@
 """ctypes binding of libhj_batch.so (include/hj_batch.h): many problems on one grid, one launch per RK stage.
 
-A library of its own beside libhj_mi355x.so (_ffi.py), libhj_query.so (_qffi.py), libhj_surface.so (_sffi.py),
-libhj_ttr.so (_tffi.py) and libhj_rollout.so (_rffi.py): stateless entry points, the grid descriptor of _qffi and a HIP
-stream per call.  As there, a missing library is an error -- there is no CPU fallback.
+Stateless entry points, the grid descriptor of include/hj_query.h and a HIP stream per call.  Loaded by _ffi.bind: a
+missing library is an error.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import _ffi, _qffi
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HJ_BATCH_LIB") or os.path.join(HERE, "csrc", "libhj_batch.so")
-
 PAR_SLOTS = 8                                      # HJB_PAR_SLOTS
 ARR_NONE, ARR_MIN, ARR_MAX, ARR_MAX_NEG = 0, 1, 2, 3   # HJB_ARR_*
 SCHEMES = _qffi.POINT_SCHEMES                      # the schemes batch_substep_kernel is instantiated for
-HAM_DIMS = {_ffi.HAM_DUBINS_REL: 3, _ffi.HAM_DOUBLE_INTEGRATOR: 2, _ffi.HAM_DOUBLE_PENDULUM: 4}
+HAM_DIMS = _ffi.HAM_DIMS
 HAM_NAMES = {_ffi.HAM_DUBINS_REL: "HamDubinsRel", _ffi.HAM_DOUBLE_INTEGRATOR: "HamDoubleIntegrator",
              _ffi.HAM_DOUBLE_PENDULUM: "HamDoublePendulum"}
 
@@ -54,41 +49,7 @@ SIGNATURES = {
     "hjb_last_kernel": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (loudly) if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-        # torch first, as _ffi.lib(): the process must share the HIP runtime its wheel bundles
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    """Non-zero return code -> ValueError (Unsupported for HJ_EUNSUPPORTED), as _ffi.check."""
-    if rc != 0:
-        msg = lib().hjb_last_error()
-        text = (msg or b"hj_batch error").decode("utf-8", "replace") + " (code %d)" % rc
-        raise (_ffi.Unsupported if rc == -3 else ValueError)(text)
-
-
-def last_kernel():
-    return (lib().hjb_last_kernel() or b"").decode()
+LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_BATCH_LIB", "libhj_batch.so", "hjb", "hj_batch error", SIGNATURES)
 
 
 def kernel_name(dtype_name, ham, scheme):

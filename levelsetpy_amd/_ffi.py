@@ -1,13 +1,13 @@
 """ctypes binding of libhj_mi355x.so (include/hj_mi355x.h).
 
 The product path is HIP only: if the shared library is missing or cannot be
-loaded, every compute entry point raises -- there is no CPU fallback.
+loaded, every compute entry point raises.  bind() below is the one loader: the bindings of
+the stateless libraries (_qffi, _sffi, _tffi, _rffi, _bffi) go through it too.
 """
 import ctypes as C
 import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HJ_LIB") or os.path.join(HERE, "csrc", "libhj_mi355x.so")   # HJ_LIB: tuning builds
 
 # enums of include/hj_mi355x.h
 BC_EXTRAPOLATE, BC_PERIODIC = 0, 1
@@ -17,6 +17,7 @@ POST_NONE, POST_MIN_PREV, POST_MAX_PREV = 0, 1, 2
 ENO2, ENO3, WENO5, WENO5_ASSHIPPED = 0, 1, 2, 3
 HAM_DUBINS_REL, HAM_DOUBLE_INTEGRATOR, HAM_DOUBLE_PENDULUM = 0, 1, 2
 HAM_USER_BASE = 100
+HAM_DIMS = {HAM_DUBINS_REL: 3, HAM_DOUBLE_INTEGRATOR: 2, HAM_DOUBLE_PENDULUM: 4}      # state dimension of the built-in systems
 F64, F32 = 0, 1
 STAGE_YDOT, STAGE_EULER, STAGE_RK3_HALF, STAGE_RK3_FULL, STAGE_RK2_FULL = 0, 1, 2, 3, 4
 OP_MIN, OP_MAX, OP_MAX_NEG = 0, 1, 2
@@ -103,43 +104,57 @@ SIGNATURES = {
 
 HAM_RANGE = 1          # hj_ham_register2 flag: alpha reads the costate range (dmin / dmax)
 
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (loudly) if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-        # torch first: its wheel bundles the HIP/HSA runtime the process must share.  Loaded the other way
-        # round, the library would bring in /opt/rocm's copy and torch a second one, and the later of the
-        # two runtimes to initialise finds "no ROCm-capable device" (seen with build() followed by smoke()).
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
 
 class Unsupported(ValueError):
     """HJ_EUNSUPPORTED: the library has no kernel for this combination (callers with another path may take it)."""
 
 
-def check(rc):
-    """Non-zero return code -> ValueError, as the reference's error() (matlab_utils.py:134-137)."""
-    if rc != 0:
-        msg = lib().hj_last_error()
-        text = (msg or b"hj_mi355x error").decode("utf-8", "replace") + " (code %d)" % rc
-        raise (Unsupported if rc == -3 else ValueError)(text)
+def bind(env_var, file_name, prefix, fallback_text, signatures):
+    """The loader of one shared library of levelsetpy_amd/csrc: -> (path, lib, check, last_kernel).
+
+      path           the environment variable's value, or the library beside this package's sources
+      lib()          the loaded library, its functions typed by `signatures`; RuntimeError (loudly) if it is not built
+      check(rc)      non-zero return code -> ValueError with <prefix>_last_error() (Unsupported for HJ_EUNSUPPORTED),
+                     as the reference's error() (matlab_utils.py:134-137)
+      last_kernel()  <prefix>_last_kernel() of the calling thread as text (the stateless libraries)
+    """
+    path = os.environ.get(env_var) or os.path.join(HERE, "csrc", file_name)
+    loaded = []
+
+    def lib():
+        if not loaded:
+            if not os.path.exists(path):
+                raise RuntimeError(
+                    "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
+                    "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % path)
+            # torch first: its wheel bundles the HIP/HSA runtime the process must share.  Loaded the other way
+            # round, the library would bring in /opt/rocm's copy and torch a second one, and the later of the
+            # two runtimes to initialise finds "no ROCm-capable device" (seen with build() followed by smoke()).
+            try:
+                import torch  # noqa: F401
+            except ImportError:
+                pass
+            L = C.CDLL(path)
+            for name, (res, args) in signatures.items():
+                fn = getattr(L, name)
+                fn.restype = res
+                fn.argtypes = args
+            loaded.append(L)
+        return loaded[0]
+
+    def check(rc):
+        if rc != 0:
+            msg = getattr(lib(), prefix + "_last_error")()
+            text = (msg or fallback_text.encode()).decode("utf-8", "replace") + " (code %d)" % rc
+            raise (Unsupported if rc == -3 else ValueError)(text)
+
+    def last_kernel():
+        return (getattr(lib(), prefix + "_last_kernel")() or b"").decode()
+
+    return path, lib, check, last_kernel
+
+
+LIB_PATH, lib, check, _ = bind("HJ_LIB", "libhj_mi355x.so", "hj", "hj_mi355x error", SIGNATURES)   # HJ_LIB: tuning builds
 
 
 def darr(values):

@@ -1,10 +1,12 @@
-"""Marshalling shared by the front ends of the stateless libraries (query.py, surface.py): what array type a result takes,
-how NumPy arrays, HostViews and tensors become contiguous device tensors, raw pointers and streams for ctypes."""
+"""Marshalling shared by the front ends of the stateless libraries (query.py, surface.py, ttr.py, rollout.py, batch.py): what
+array type a result takes, how NumPy arrays, HostViews and tensors become contiguous device tensors, raw pointers and streams
+for ctypes, and how a grid becomes the hjq_grid descriptor."""
 import ctypes as C
 
 import numpy as np
 
-from .context import is_tensor, require_gpu, _raw_stream_getter
+from . import _qffi
+from .context import array_dtype_name as dtype_name, grid_bc, is_tensor, require_gpu, _raw_stream_getter   # noqa: F401
 from .lazy import HostView, DeviceArray
 from .utilities import error
 
@@ -64,3 +66,14 @@ def fields(t, N):
     if len(shape) == len(N) + 1 and shape[1:] == tuple(N) and shape[0] >= 1:
         return shape[0], total
     error('data parameter does not agree in array size with grid')
+
+
+def descriptor(g, dtype_name):
+    """(hjq_grid of grid g for data of `dtype_name` ('float64' / 'float32', see dtype_name(t)), g's shape as a tuple)."""
+    N = [int(v) for v in np.asarray(g.N).ravel()]
+    dx = [float(v) for v in np.asarray(g.dx).ravel()]
+    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
+    bc, tz = grid_bc(g)
+    if g.dim > _qffi.MAX_DIM:
+        error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
+    return _qffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)

@@ -1,15 +1,11 @@
 """ctypes binding of libhj_query.so (include/hj_query.h): value-function queries at states.
 
-A library of its own beside libhj_mi355x.so (_ffi.py): stateless entry points, a plain grid descriptor and a
-HIP stream per call.  As there, a missing library is an error -- there is no CPU fallback.
+Stateless entry points, a plain grid descriptor (hjq_grid, which the other stateless libraries share) and a HIP
+stream per call.  Loaded by _ffi.bind: a missing library is an error.
 """
 import ctypes as C
-import os
 
 from . import _ffi
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HJ_QUERY_LIB") or os.path.join(HERE, "csrc", "libhj_query.so")
 
 MAX_DIM = 4
 OP_MIN, OP_MAX = 0, 1
@@ -35,41 +31,7 @@ SIGNATURES = {
     "hjq_last_kernel": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (loudly) if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-        # torch first, as _ffi.lib(): the process must share the HIP runtime its wheel bundles
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    """Non-zero return code -> ValueError (Unsupported for HJ_EUNSUPPORTED), as _ffi.check."""
-    if rc != 0:
-        msg = lib().hjq_last_error()
-        text = (msg or b"hj_query error").decode("utf-8", "replace") + " (code %d)" % rc
-        raise (_ffi.Unsupported if rc == -3 else ValueError)(text)
-
-
-def last_kernel():
-    return (lib().hjq_last_kernel() or b"").decode()
+LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_QUERY_LIB", "libhj_query.so", "hjq", "hj_query error", SIGNATURES)
 
 
 def grid_descriptor(ndim, N, xmin, xlast, dx, bc, tz, dtype_name):

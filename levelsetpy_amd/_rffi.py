@@ -1,21 +1,16 @@
 """ctypes binding of libhj_rollout.so (include/hj_rollout.h): many optimal trajectories in one launch.
 
-A library of its own beside libhj_mi355x.so (_ffi.py), libhj_query.so (_qffi.py), libhj_surface.so (_sffi.py) and
-libhj_ttr.so (_tffi.py): one stateless entry point, the grid descriptor of _qffi and a HIP stream per call.  As there, a
-missing library is an error -- there is no CPU fallback.
+One stateless entry point, the grid descriptor of include/hj_query.h and a HIP stream per call.  Loaded by _ffi.bind: a
+missing library is an error.
 """
 import ctypes as C
-import os
 
 from . import _ffi, _qffi
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HJ_ROLLOUT_LIB") or os.path.join(HERE, "csrc", "libhj_rollout.so")
 
 MODE_MIN, MODE_MAX = 0, 1                          # HJR_MODE_*
 REACHED, EXHAUSTED, LEFT_GRID = 0, 1, 2            # HJR_* status of a trajectory
 SCHEMES = _qffi.POINT_SCHEMES                      # the schemes hjr_rollout instantiates
-PLANT_DIMS = {_ffi.HAM_DUBINS_REL: 3, _ffi.HAM_DOUBLE_INTEGRATOR: 2, _ffi.HAM_DOUBLE_PENDULUM: 4}
+PLANT_DIMS = _ffi.HAM_DIMS
 
 
 class Plant(C.Structure):
@@ -33,41 +28,7 @@ SIGNATURES = {
     "hjr_last_kernel": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (loudly) if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-        # torch first, as _ffi.lib(): the process must share the HIP runtime its wheel bundles
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    """Non-zero return code -> ValueError (Unsupported for HJ_EUNSUPPORTED), as _ffi.check."""
-    if rc != 0:
-        msg = lib().hjr_last_error()
-        text = (msg or b"hj_rollout error").decode("utf-8", "replace") + " (code %d)" % rc
-        raise (_ffi.Unsupported if rc == -3 else ValueError)(text)
-
-
-def last_kernel():
-    return (lib().hjr_last_kernel() or b"").decode()
+LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_ROLLOUT_LIB", "libhj_rollout.so", "hjr", "hj_rollout error", SIGNATURES)
 
 
 def plant_descriptor(ham_id, u_mode, d_mode, params):

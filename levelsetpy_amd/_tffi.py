@@ -1,16 +1,10 @@
 """ctypes binding of libhj_ttr.so (include/hj_ttr.h): time-to-reach functions.
 
-A library of its own beside libhj_mi355x.so (_ffi.py), libhj_query.so (_qffi.py) and libhj_surface.so (_sffi.py):
-stateless entry points, plain pointers and a HIP stream per call.  As there, a missing library is an error -- there is
-no CPU fallback.
+Stateless entry points, plain pointers and a HIP stream per call.  Loaded by _ffi.bind: a missing library is an error.
 """
 import ctypes as C
-import os
 
 from . import _ffi
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("HJ_TTR_LIB") or os.path.join(HERE, "csrc", "libhj_ttr.so")
 
 FIRST, NO_INTERP = 1, 2              # mode bits (HJT_FIRST, HJT_NO_INTERP)
 
@@ -25,38 +19,4 @@ SIGNATURES = {
     "hjt_last_kernel": (C.c_char_p, []),
 }
 
-_lib = None
-
-
-def lib():
-    """The loaded library; raises RuntimeError (loudly) if it is not built."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                "levelsetpy_amd: %s is missing -- build it with `python -c 'import __graft_entry__ as g; "
-                "g.build()'` (or `make -C levelsetpy_amd/csrc`). There is no CPU fallback." % LIB_PATH)
-        # torch first, as _ffi.lib(): the process must share the HIP runtime its wheel bundles
-        try:
-            import torch  # noqa: F401
-        except ImportError:
-            pass
-        L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(L, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = L
-    return _lib
-
-
-def check(rc):
-    """Non-zero return code -> ValueError (Unsupported for HJ_EUNSUPPORTED), as _ffi.check."""
-    if rc != 0:
-        msg = lib().hjt_last_error()
-        text = (msg or b"hj_ttr error").decode("utf-8", "replace") + " (code %d)" % rc
-        raise (_ffi.Unsupported if rc == -3 else ValueError)(text)
-
-
-def last_kernel():
-    return (lib().hjt_last_kernel() or b"").decode()
+LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_TTR_LIB", "libhj_ttr.so", "hjt", "hj_ttr error", SIGNATURES)

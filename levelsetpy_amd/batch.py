@@ -41,7 +41,7 @@ from .hji_solver import HJIPDE_solve
 from .lazy import HostView, DeviceArray
 from .spatial import scheme_id_of, upwindFirstWENO5
 from .utilities import Bundle, error, info, isfield, realmax
-from ._marshal import unlazy as _unlazy, stream as _stream, ptr as _ptr
+from ._marshal import unlazy as _unlazy, stream as _stream, ptr as _ptr, descriptor as _descriptor
 
 __all__ = ["HJIPDE_solve_batch", "plan_interval", "plan_schedule"]
 
@@ -353,7 +353,6 @@ def _nan_problems(torch, device, ptrs, active, n, dtype_id):
 
 
 def _device_solve(setup, data0s, tau, compMethod, extraArgs, kinds, tensors, quiet):
-    from .query import _descriptor
     torch = require_gpu()
     g, ham, scheme = setup.grid, setup.ham, setup.scheme
     src = _unlazy(data0s)

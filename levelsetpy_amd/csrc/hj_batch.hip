@@ -12,34 +12,17 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <limits>
 #include <vector>
+#include "hj_tool_host.h"
 #include "hj_split.h"
 #include "../../include/hj_batch.h"
 
 namespace hjb {
 
 using namespace hj;
-
-static thread_local char g_err[512] = "";
-static thread_local const char* g_kernel = "";
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-    } while (0)
+using namespace hj_tool;
 
 constexpr long long MAX_Y = 65535;      // gridDim.y of one launch
 
@@ -186,10 +169,6 @@ __global__ __launch_bounds__(256) void batch_nan_kernel(const hjb_entry* tab, lo
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static int ham_ndim(int ham) {
-    return ham == HJ_HAM_DUBINS_REL ? 3 : (ham == HJ_HAM_DOUBLE_INTEGRATOR ? 2 : (ham == HJ_HAM_DOUBLE_PENDULUM ? 4 : 0));
-}
-
 // the checks every entry point makes on (grid, tables, system); total = the number of cells
 static int check_setup(const hjq_grid* g, const hjb_tables* tab, int ham, long long& total) {
     if (!g || !tab) return fail(HJ_EINVAL, "null grid descriptor or tables");
@@ -241,16 +220,17 @@ static int launch_substep(const hjq_grid* g, const hjb_tables* tab, int stage, i
     for (int s = 0; s < 4; ++s) A.aux[s] = (const T*)tab->aux[s];
     A.stage = stage;
     A.restrict_sign = restrict_sign;
-    const long long bx = (A.G.total + 255) / 256;
-    if (bx > 0x7fffffffll) return fail(HJ_EINVAL, "grid too large for one thread per cell");
+    unsigned bx;
+    int rc = blocks_for(A.G.total, "grid too large for one thread per cell", bx);
+    if (rc) return rc;
     for (int64_t off = 0; off < B; off += MAX_Y) {
         const int64_t nb = std::min<int64_t>(MAX_Y, B - off);
         A.par = params + off * HJB_PAR_SLOTS;
         A.tab = entries + off;
-        hipLaunchKernelGGL((batch_substep_kernel<T, HAM, SCHEME>), dim3((unsigned)bx, (unsigned)nb), dim3(256), 0, stream, A);
+        hipLaunchKernelGGL((batch_substep_kernel<T, HAM, SCHEME>), dim3(bx, (unsigned)nb), dim3(256), 0, stream, A);
         HIP_TRY(hipGetLastError());
     }
-    g_kernel = name;
+    launched(name);
     return HJ_OK;
 }
 
@@ -277,12 +257,6 @@ static int dispatch_substep(const hjq_grid* g, const hjb_tables* tab, int scheme
 #undef HJB_GO
 }
 
-static int check_scheme(int scheme) {
-    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
-        return fail(HJ_EUNSUPPORTED, "scheme %d has no batched kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
-    return HJ_OK;
-}
-
 template <typename T, typename HAM>
 static int launch_bound(const hjq_grid* g, const hjb_tables* tab, const double* params, int64_t B, unsigned long long* keys,
                         hipStream_t stream) {
@@ -297,7 +271,7 @@ static int launch_bound(const hjq_grid* g, const hjb_tables* tab, const double* 
                            params + off * HJB_PAR_SLOTS, keys + off * HJ_MAX_DIM);
         HIP_TRY(hipGetLastError());
     }
-    g_kernel = "batch_bound_kernel";
+    launched("batch_bound_kernel");
     return HJ_OK;
 }
 
@@ -386,7 +360,7 @@ int hjb_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, i
     long long total;
     int rc = check_setup(g, tab, ham, total);
     if (rc) return rc;
-    if ((rc = check_scheme(scheme))) return rc;
+    if ((rc = check_point_scheme(scheme, "batched"))) return rc;
     if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
     if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
     if (B == 0) return HJ_OK;
@@ -416,7 +390,7 @@ int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
     long long total;
     int rc = check_setup(g, tab, ham, total);
     if (rc) return rc;
-    if ((rc = check_scheme(scheme))) return rc;
+    if ((rc = check_point_scheme(scheme, "batched"))) return rc;
     if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
     if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
     if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
@@ -510,11 +484,10 @@ int hjb_nan_flags(int dtype, const hjb_entry* entries, int64_t B, int64_t n, int
             hipLaunchKernelGGL((batch_nan_kernel<float>), dim3(bx, (unsigned)nb), dim3(256), 0, s, entries + off, (long long)n, (int*)flags + off);
         HIP_TRY(hipGetLastError());
     }
-    g_kernel = dtype == HJ_F64 ? "batch_nan_kernel<double>" : "batch_nan_kernel<float>";
+    launched(dtype == HJ_F64 ? "batch_nan_kernel<double>" : "batch_nan_kernel<float>");
     return HJ_OK;
 }
 
-const char* hjb_last_error(void) { return g_err; }
-const char* hjb_last_kernel(void) { return g_kernel; }
+HJ_TOOL_LAST_SYMBOLS(hjb)
 
 }  // extern "C"

@@ -7,29 +7,13 @@
 // The interpolation arithmetic is hji_solver._eval_point's, operation by operation (contraction off: `v += wt * val`
 // must stay a multiply and an add), so the fp64 results equal the host loop's bit for bit.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
 #include <cmath>
+#include "hj_tool_host.h"
 #include "hj_query_dev.h"
 
 namespace hjq {
 
-static thread_local char g_err[512] = "";
-static thread_local const char* g_kernel = "";
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-    } while (0)
+using namespace hj_tool;
 
 template <typename T>
 __device__ __forceinline__ void put(void* out, long long i, double v, int out_f64) {
@@ -218,31 +202,6 @@ __global__ __launch_bounds__(256) void project_minmax_kernel(const T* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
-    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
-    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
-    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
-    G.ndim = g->ndim;
-    total = 1;
-    for (int d = 0; d < MAXD; ++d) {
-        G.n[d] = 1; G.per[d] = 0; G.stride[d] = 0; G.xmin[d] = 0; G.xlast[d] = 0; G.dx[d] = 1;
-    }
-    for (int d = g->ndim - 1; d >= 0; --d) {
-        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
-            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
-        G.n[d] = (int)g->N[d];
-        G.per[d] = g->bc[d] == HJ_BC_PERIODIC;
-        G.stride[d] = total;
-        G.xmin[d] = g->xmin[d];
-        G.xlast[d] = g->xlast[d];
-        G.dx[d] = g->dx[d];
-        total *= g->N[d];
-    }
-    return HJ_OK;
-}
-
 static int check_points(const hjq_grid* g, const QGrid& G, long long total, const void* data, int64_t nfields, int64_t field_stride,
                  const double* xs, int64_t nstates, bool costate) {
     if (!data || !xs) return fail(HJ_EINVAL, "null argument");
@@ -256,24 +215,17 @@ static int check_points(const hjq_grid* g, const QGrid& G, long long total, cons
     return HJ_OK;
 }
 
-static int blocks_for(long long threads, unsigned& blocks) {
-    const long long b = (threads + 255) / 256;
-    if (b > 0x7fffffffll) return fail(HJ_EINVAL, "too many (field, state) pairs for one launch");
-    blocks = (unsigned)b;
-    return HJ_OK;
-}
+static const char TOO_MANY[] = "too many (field, state) pairs for one launch";
 
 template <typename T>
 static int interp_launch(const QGrid& G, const void* data, int64_t nfields, int64_t field_stride, const double* xs, int64_t M,
                   void* out, int out_f64, hipStream_t stream, const char* name) {
     unsigned blocks;
-    int rc = blocks_for((long long)nfields * M, blocks);
+    int rc = blocks_for((long long)nfields * M, TOO_MANY, blocks);
     if (rc) return rc;
     hipLaunchKernelGGL((interp_points_kernel<T>), dim3(blocks), dim3(256), 0, stream, (const T*)data, (long long)field_stride,
                        (long long)nfields, xs, (long long)M, G, out, out_f64);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 template <typename T, int SCHEME>
@@ -285,24 +237,20 @@ static int costate_launch(const hjq_grid* g, const QGrid& G, const void* data, i
         hj::fill_stencil_constants<T>(G.dx[d], S.K[d]);
     }
     unsigned blocks;
-    int rc = blocks_for((long long)nfields * M * (1ll << G.ndim), blocks);
+    int rc = blocks_for((long long)nfields * M * (1ll << G.ndim), TOO_MANY, blocks);
     if (rc) return rc;
     hipLaunchKernelGGL((costate_points_kernel<T, SCHEME>), dim3(blocks), dim3(256), 0, stream, (const T*)data,
                        (long long)field_stride, (long long)nfields, xs, (long long)M, G, S, O);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 template <typename T, bool WAVE>
 static int project_launch(const void* data, void* out, const ProjArgs& A, hipStream_t stream, const char* name) {
     unsigned blocks;
-    int rc = blocks_for(A.nfields * A.nout * (WAVE ? 64 : 1), blocks);
+    int rc = blocks_for(A.nfields * A.nout * (WAVE ? 64 : 1), TOO_MANY, blocks);
     if (rc) return rc;
     hipLaunchKernelGGL((project_minmax_kernel<T, WAVE>), dim3(blocks), dim3(256), 0, stream, (const T*)data, (T*)out, A);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 }  // namespace hjq
@@ -331,8 +279,7 @@ int hjq_costate_points(const hjq_grid* g, int scheme, const void* data, int64_t 
     int rc = make_grid(g, G, total);
     if (rc) return rc;
     if (!costate) return fail(HJ_EINVAL, "null argument");
-    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
-        return fail(HJ_EUNSUPPORTED, "scheme %d has no point kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
+    if ((rc = check_point_scheme(scheme, "point"))) return rc;
     if ((rc = check_points(g, G, total, data, nfields, field_stride, xs, nstates, true))) return rc;
     const CostateOut O{costate, derivL, derivR, value, out_f64};
     hipStream_t s = (hipStream_t)stream;
@@ -386,7 +333,6 @@ int hjq_project_minmax(const hjq_grid* g, const void* data, int64_t nfields, int
                 : project_launch<float, false>(data, out, A, s, "project_minmax_kernel<float, false>");
 }
 
-const char* hjq_last_error(void) { return g_err; }
-const char* hjq_last_kernel(void) { return g_kernel; }
+HJ_TOOL_LAST_SYMBOLS(hjq)
 
 }  // extern "C"

@@ -1,10 +1,11 @@
 // Device code shared by the point kernels of libhj_query.so (hj_query.hip) and libhj_rollout.so (hj_rollout.hip): the grid as a
 // kernel sees it, the cell search, the corner weights, the stencil gather and the ordered sum over a state's corner lanes.
 // One source, so a value or a costate interpolated inside a rollout has the bits interp_points_kernel and
-// costate_points_kernel give for the same state.
+// costate_points_kernel give for the same state.  At the end, the host function that fills the grid from the descriptor.
 #ifndef HJ_QUERY_DEV_H
 #define HJ_QUERY_DEV_H
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include "hj_device.h"
 #include "../../include/hj_query.h"
 
@@ -130,6 +131,39 @@ __device__ __forceinline__ double group_sum(double term, int used, int lanes) {
         if (u) v = v + p;
     }
     return v;
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+// The descriptor as the kernels see it, with the checks both libraries make on it; total = the number of nodes.  Refusals go to
+// the including library's own error record: hj_tool_host.h comes before this header.
+#ifndef HJ_TOOL_HOST_H
+#error "include hj_tool_host.h before hj_query_dev.h"
+#endif
+using hj_tool::fail;
+
+static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
+    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
+    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    G.ndim = g->ndim;
+    total = 1;
+    for (int d = 0; d < MAXD; ++d) {
+        G.n[d] = 1; G.per[d] = 0; G.stride[d] = 0; G.xmin[d] = 0; G.xlast[d] = 0; G.dx[d] = 1;
+    }
+    for (int d = g->ndim - 1; d >= 0; --d) {
+        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
+            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
+        G.n[d] = (int)g->N[d];
+        G.per[d] = g->bc[d] == HJ_BC_PERIODIC;
+        G.stride[d] = total;
+        G.xmin[d] = g->xmin[d];
+        G.xlast[d] = g->xlast[d];
+        G.dx[d] = g->dx[d];
+        total *= g->N[d];
+    }
+    return HJ_OK;
 }
 
 }  // namespace hjq

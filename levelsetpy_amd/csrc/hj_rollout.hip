@@ -10,9 +10,8 @@
 // group_sum runs with all lanes of its group active.  State, weights, controls and dynamics are fp64 with contraction off;
 // the stencil arithmetic is T, as in the costate kernel.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
 #include <cmath>
+#include "hj_tool_host.h"
 #include "hj_query_dev.h"
 #include "../../include/hj_rollout.h"
 
@@ -21,23 +20,8 @@ namespace hjr {
 using hjq::MAXD;
 using hjq::QGrid;
 using hjq::QStencil;
-
-static thread_local char g_err[512] = "";
-static thread_local const char* g_kernel = "";
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-    } while (0)
+using hjq::make_grid;
+using namespace hj_tool;
 
 // +1 for s >= 0, -1 for s < 0, NaN for NaN: an exact zero is deterministic, a NaN costate poisons the state
 __device__ __forceinline__ double sgn(double s) { return s >= 0.0 ? 1.0 : (s < 0.0 ? -1.0 : __builtin_nan("")); }
@@ -294,32 +278,6 @@ __global__ __launch_bounds__(256) void rollout_kernel(const T* __restrict__ data
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-// the descriptor as the kernels see it (the checks of hj_query.hip's make_grid)
-static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
-    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
-    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
-    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
-    G.ndim = g->ndim;
-    total = 1;
-    for (int d = 0; d < MAXD; ++d) {
-        G.n[d] = 1; G.per[d] = 0; G.stride[d] = 0; G.xmin[d] = 0; G.xlast[d] = 0; G.dx[d] = 1;
-    }
-    for (int d = g->ndim - 1; d >= 0; --d) {
-        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
-            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
-        G.n[d] = (int)g->N[d];
-        G.per[d] = g->bc[d] == HJ_BC_PERIODIC;
-        G.stride[d] = total;
-        G.xmin[d] = g->xmin[d];
-        G.xlast[d] = g->xlast[d];
-        G.dx[d] = g->dx[d];
-        total *= g->N[d];
-    }
-    return HJ_OK;
-}
-
 template <typename T, int SCHEME, int PLANT>
 static int launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
                   int64_t M, int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O, hipStream_t stream,
@@ -329,13 +287,12 @@ static int launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t n
         S.km[d] = (d < G.ndim && g->toward_zero[d]) ? T(-1) : T(1);
         hj::fill_stencil_constants<T>(G.dx[d], S.K[d]);
     }
-    const long long b = ((long long)M * (1ll << G.ndim) + 255) / 256;
-    if (b > 0x7fffffffll) return fail(HJ_EINVAL, "too many trajectories for one launch");
-    hipLaunchKernelGGL((rollout_kernel<T, SCHEME, PLANT>), dim3((unsigned)b), dim3(256), 0, stream, (const T*)data,
+    unsigned blocks;
+    int rc = blocks_for((long long)M * (1ll << G.ndim), "too many trajectories for one launch", blocks);
+    if (rc) return rc;
+    hipLaunchKernelGGL((rollout_kernel<T, SCHEME, PLANT>), dim3(blocks), dim3(256), 0, stream, (const T*)data,
                        (long long)field_stride, (int)ntimes, x0, (long long)M, G, S, sub_samples, dt_small, P, O);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 }  // namespace hjr
@@ -357,15 +314,9 @@ int hjr_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes,
     if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
     if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
     if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
-    if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
-        return fail(HJ_EUNSUPPORTED, "scheme %d has no rollout kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme);
-    int nd;
-    switch (plant->id) {
-        case HJ_HAM_DUBINS_REL: nd = 3; break;
-        case HJ_HAM_DOUBLE_INTEGRATOR: nd = 2; break;
-        case HJ_HAM_DOUBLE_PENDULUM: nd = 4; break;
-        default: return fail(HJ_EUNSUPPORTED, "plant %d has no rollout kernel", (int)plant->id);
-    }
+    if ((rc = check_point_scheme(scheme, "rollout"))) return rc;
+    const int nd = ham_ndim(plant->id);
+    if (nd == 0) return fail(HJ_EUNSUPPORTED, "plant %d has no rollout kernel", (int)plant->id);
     if (nd != G.ndim) return fail(HJ_EINVAL, "plant %d has %d states, the grid %d dimensions", (int)plant->id, nd, G.ndim);
     if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
         return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
@@ -396,7 +347,6 @@ int hjr_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes,
 #undef HJR_GO
 }
 
-const char* hjr_last_error(void) { return g_err; }
-const char* hjr_last_kernel(void) { return g_kernel; }
+HJ_TOOL_LAST_SYMBOLS(hjr)
 
 }  // extern "C"

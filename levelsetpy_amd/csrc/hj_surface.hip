@@ -10,30 +10,13 @@
 //                          is base(lower node) + popcount(mask(lower node) & below(edge class))
 // Coordinates keep the product and the sum apart (contraction off), as tests/surface_ref.py computes them.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
 #include <cmath>
-#include <string>
+#include "hj_tool_host.h"
 #include "../../include/hj_surface.h"
 
 namespace hjs {
 
-static thread_local char g_err[512] = "";
-static thread_local std::string g_kernel;
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-    } while (0)
+using namespace hj_tool;
 
 constexpr int TPB = 256;                 // threads per workgroup
 constexpr int ITEMS = 4;                 // nodes per thread in classify_kernel
@@ -452,7 +435,8 @@ static int count_launch(const SGrid& G, const void* data, int64_t nfields, int64
     hipLaunchKernelGGL(scan_blocks_kernel, dim3((unsigned)nfields), dim3(SCAN_TPB), 0, stream, ws, (long long)nfields, G.nodes,
                        G.ntiles, (long long*)counts);
     HIP_TRY(hipGetLastError());
-    g_kernel = std::string(name) + ";scan_blocks_kernel";
+    launched(name);
+    launched_also("scan_blocks_kernel");
     return HJ_OK;
 }
 
@@ -461,7 +445,7 @@ static int emit_launch(const SGrid& G, const void* data, int64_t nfields, int64_
                        const int64_t* counts, double* verts, int32_t* faces, hipStream_t stream, const char* name) {
     const unsigned blocks = (unsigned)(G.ntiles * ITEMS);
     long long vat = 0, fat = 0;
-    g_kernel.clear();
+    launched_none();
     for (int64_t f = 0; f < nfields; ++f) {
         const long long nv = counts[2 * f], nf = counts[2 * f + 1];
         if (nv == 0 && nf == 0) continue;
@@ -469,7 +453,7 @@ static int emit_launch(const SGrid& G, const void* data, int64_t nfields, int64_
         hipLaunchKernelGGL((emit_kernel<T, D>), dim3(blocks), dim3(TPB), 0, stream, (const T*)data + f * field_stride, G, level, W, nv,
                            nf, verts + vat * D, faces + fat * D);
         HIP_TRY(hipGetLastError());
-        g_kernel += g_kernel.empty() ? name : std::string(";") + name;
+        launched_also(name);
         vat += nv;
         fat += nf;
     }
@@ -538,7 +522,6 @@ int hjs_emit(const hjq_grid* g, const void* data, int64_t nfields, int64_t field
 #undef HJS_EMIT
 }
 
-const char* hjs_last_error(void) { return g_err; }
-const char* hjs_last_kernel(void) { return g_kernel.c_str(); }
+HJ_TOOL_LAST_SYMBOLS(hjs)
 
 }  // extern "C"

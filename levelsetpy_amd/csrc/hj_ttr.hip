@@ -10,28 +10,12 @@
 // nodes BLOCK apart and issues the loads of DEPTH slices before it consumes the first (NODES * DEPTH loads outstanding).
 // The recurrence is written one operation per statement with contraction off: the results are NumPy's, bit for bit.
 #include <hip/hip_runtime.h>
-#include <cstdarg>
-#include <cstdio>
+#include "hj_tool_host.h"
 #include "../../include/hj_ttr.h"
 
 namespace hjt {
 
-static thread_local char g_err[512] = "";
-static thread_local const char* g_kernel = "";
-
-static int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(HJ_EHIP, "%s: %s", #expr, hipGetErrorString(e_));             \
-    } while (0)
+using namespace hj_tool;
 
 constexpr int BLOCK = 256;
 constexpr int NODES = 2;              // nodes per thread and pass of the grid-stride loop, BLOCK apart
@@ -166,7 +150,8 @@ __global__ __launch_bounds__(BLOCK) void ttr_from_stack_kernel(const T* __restri
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static unsigned blocks_for(long long n) {
+// capped, unlike hj_tool::blocks_for: the kernels walk larger arrays in a grid-stride loop
+static unsigned stream_blocks(long long n) {
     const long long per = (long long)BLOCK * NODES;
     const long long b = (n + per - 1) / per;
     return (unsigned)(b < MAX_BLOCKS ? b : MAX_BLOCKS);
@@ -181,30 +166,24 @@ static int check_common(int dtype, int64_t n, int mode) {
 
 template <typename T>
 static int init_launch(const void* y, int64_t n, double t, double level, double* ttr, void* last_y, hipStream_t stream, const char* name) {
-    hipLaunchKernelGGL((ttr_init_kernel<T>), dim3(blocks_for(n)), dim3(BLOCK), 0, stream, (const T*)y, (long long)n, t, level, ttr, (T*)last_y);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    hipLaunchKernelGGL((ttr_init_kernel<T>), dim3(stream_blocks(n)), dim3(BLOCK), 0, stream, (const T*)y, (long long)n, t, level, ttr, (T*)last_y);
+    return launch_done(name);
 }
 
 template <typename T>
 static int update_launch(const void* y, int64_t n, double t, double t_last, double level, int mode, double* ttr, void* last_y,
                          hipStream_t stream, const char* name) {
-    hipLaunchKernelGGL((ttr_update_kernel<T>), dim3(blocks_for(n)), dim3(BLOCK), 0, stream, (const T*)y, (long long)n, t, t_last, level,
+    hipLaunchKernelGGL((ttr_update_kernel<T>), dim3(stream_blocks(n)), dim3(BLOCK), 0, stream, (const T*)y, (long long)n, t, t_last, level,
                        mode, ttr, (T*)last_y);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 template <typename T>
 static int stack_launch(const void* data, int64_t T_, int64_t field_stride, int64_t n, const double* tau, double level, int mode,
                         double* ttr, hipStream_t stream, const char* name) {
-    hipLaunchKernelGGL((ttr_from_stack_kernel<T>), dim3(blocks_for(n)), dim3(BLOCK), 0, stream, (const T*)data, (long long)T_,
+    hipLaunchKernelGGL((ttr_from_stack_kernel<T>), dim3(stream_blocks(n)), dim3(BLOCK), 0, stream, (const T*)data, (long long)T_,
                        (long long)field_stride, (long long)n, tau, level, mode, ttr);
-    HIP_TRY(hipGetLastError());
-    g_kernel = name;
-    return HJ_OK;
+    return launch_done(name);
 }
 
 }  // namespace hjt
@@ -247,7 +226,6 @@ int hjt_ttr_from_stack(int dtype, const void* data, int64_t T, int64_t field_str
     return stack_launch<float>(data, T, field_stride, n, tau_dev, level, mode, ttr, (hipStream_t)stream, "ttr_from_stack_kernel<float>");
 }
 
-const char* hjt_last_error(void) { return g_err; }
-const char* hjt_last_kernel(void) { return g_kernel; }
+HJ_TOOL_LAST_SYMBOLS(hjt)
 
 }  // extern "C"

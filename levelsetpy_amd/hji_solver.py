@@ -83,7 +83,8 @@ def _eval_point(g, data, x):
     if x.size != g.dim:
         error('stopInit must be a vector of length g.dim!')
     if is_tensor(data) and data.is_cuda and g.dim <= 4 and tuple(data.shape) == tuple(int(n) for n in np.asarray(g.N).ravel()):
-        from .query import interp_states, _device_data, _device_states
+        from .query import interp_states
+        from ._marshal import device_data as _device_data, device_states as _device_states
         t = _device_data(data)
         return float(interp_states(g, t, _device_states(x.reshape(1, -1), t.device), out_f64=True)[0, 0])
     bc, _ = grid_bc(g)

@@ -25,7 +25,8 @@ import numpy as np
 from .context import is_tensor
 from .gradients import computeGradients
 from .hji_solver import _eval_point
-from .query import interp_states, costate_states, _device_data, _device_states, _point_scheme
+from .query import interp_states, costate_states, point_scheme
+from ._marshal import device_data as _device_data, device_states as _device_states
 from .spatial import upwindFirstWENO5
 from .utilities import isfield, error
 
@@ -84,7 +85,7 @@ def computeOptTraj(g, data, tau, dynSys, extraArgs=None):
         BRS_at_t = data[tEarliest]                                           # :91
         # the costate at the state (:119): the 2^dim corner stencils only, one launch per sub-sample (eval_costate's
         # kernel); derivative functions it does not cover go through computeGradients as before
-        sid = _point_scheme(derivFunc)
+        sid = point_scheme(derivFunc)
         if sid is not None:
             onDevice = _device_data(BRS_at_t)                                # a NumPy table: this set goes over once per step
         else:

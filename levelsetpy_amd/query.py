@@ -25,33 +25,17 @@ from .lazy import HostView, DeviceArray
 from .utilities import Bundle, error, warn
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, from_numpy as _from_numpy,      # noqa: F401
                        device_data as _device_data, device_states as _device_states, stream as _stream, ptr as _ptr,
-                       fields as _fields)
+                       fields as _fields, descriptor as _descriptor, dtype_name as _dtype_name)
 
 __all__ = ["eval_u", "eval_costate", "proj", "augmentPeriodicData"]
 
 
 # ------------------------------------------------------------------------------------------ marshalling
-def _grid_numbers(g):
-    N = [int(v) for v in np.asarray(g.N).ravel()]
-    dx = [float(v) for v in np.asarray(g.dx).ravel()]
-    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
-    bc, tz = grid_bc(g)
-    return N, dx, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], bc, tz
-
-
-def _descriptor(g, dtype_name):
-    N, dx, x0, x1, bc, tz = _grid_numbers(g)
-    if g.dim > _qffi.MAX_DIM:
-        error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
-    return _qffi.grid_descriptor(g.dim, N, x0, x1, dx, bc, tz, dtype_name), tuple(N)
-
-
 def interp_states(g, data, xs, out_f64=False):
     """V at states for one array or a stack on grid g: device tensors in, a (F, M) tensor out (F = 1 for one array).
     `xs` is an (M, dim) fp64 device tensor.  out_f64: the unrounded fp64 sum whatever the data's dtype."""
     torch = require_gpu()
-    dname = "float32" if data.dtype == torch.float32 else "float64"
-    desc, N = _descriptor(g, dname)
+    desc, N = _descriptor(g, _dtype_name(data))
     F, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
         error('states must be an (M, %d) array' % g.dim)
@@ -66,8 +50,7 @@ def interp_states(g, data, xs, out_f64=False):
 def costate_states(g, data, xs, scheme, out_f64=False, want_lr=False, want_value=False):
     """grad V at states: (F, M, dim) costates [, derivL, derivR (same shape), V (F, M)] from hjq_costate_points."""
     torch = require_gpu()
-    dname = "float32" if data.dtype == torch.float32 else "float64"
-    desc, N = _descriptor(g, dname)
+    desc, N = _descriptor(g, _dtype_name(data))
     F, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
         error('states must be an (M, %d) array' % g.dim)
@@ -94,7 +77,7 @@ def _give(t, proto, squeeze0=False):
     return t.detach().cpu().numpy()
 
 
-def _states_2d(g, xs):
+def states_2d(g, xs):
     """States as rows: a vector is one state; a matrix whose column count is not g.dim is transposed (evaluate_u.py:83).
     Works on a copy -- the caller's array is never modified (the reference wraps it in place)."""
     xs = _unlazy(xs)
@@ -131,7 +114,7 @@ def _eval_single(g, data, xs):
     if nd not in (gd, gd + 1):
         error('Dimensions of input data and grid don\'t match!')
     t = _device_data(data)
-    x = _device_states(_states_2d(g, xs), t.device)
+    x = _device_states(states_2d(g, xs), t.device)
     out = interp_states(g, t, x)
     if nd == gd + 1 and _is_single_state(g, xs):
         return _give(out[:, 0], data)                   # option 2: one value per array
@@ -185,7 +168,7 @@ def _stack(vals, proto, flat):
 
 
 # ------------------------------------------------------------------------------------------ eval_costate
-def _point_scheme(derivFunc):
+def point_scheme(derivFunc):
     """Scheme id for hjq_costate_points, or None when the derivative function has no point kernel: a foreign
     function, or the intended WENO5 (its epsilon is a reduction over the whole grid)."""
     from .spatial import scheme_id_of
@@ -218,10 +201,10 @@ def eval_costate(g, data, xs, derivFunc=None, dims=None):
     nd = _ndim(data)
     if nd not in (g.dim, g.dim + 1):
         error('Dimensions of input data and grid don\'t match!')
-    sid = _point_scheme(derivFunc)
+    sid = point_scheme(derivFunc)
     if sid is not None:
         t = _device_data(data)
-        x = _device_states(_states_2d(g, xs), t.device)
+        x = _device_states(states_2d(g, xs), t.device)
         cs = costate_states(g, t, x, sid)[0]
     else:
         cs = _costate_fallback(g, data, xs, derivFunc, dims)
@@ -242,7 +225,7 @@ def _costate_fallback(g, data, xs, derivFunc, dims, out_f64=False):
             continue
         t = _device_data(derivC[d])
         if x is None:
-            x = _device_states(_states_2d(g, xs), t.device)
+            x = _device_states(states_2d(g, xs), t.device)
         cols.append(interp_states(g, t, x, out_f64))
     first = next(c for c in cols if c is not None)
     cols = [torch.full_like(first, float('nan')) if c is None else c for c in cols]
@@ -346,8 +329,7 @@ def proj(g, data, dimsToRemove, xs=None, NOut=None, process=True):
     gOut = _kept_grid(g, keep, Nout, process)
     torch = require_gpu()
     t = _device_data(data)
-    dname = "float32" if t.dtype == torch.float32 else "float64"
-    desc, N = _descriptor(g, dname)
+    desc, N = _descriptor(g, _dtype_name(t))
     F, stride = _fields(t, N)
     resample = Nout != Nkeep
     if isinstance(xs, str):

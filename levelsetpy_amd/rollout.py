@@ -31,11 +31,12 @@ from . import _ffi, _rffi
 from .context import grid_bc, is_tensor, require_gpu
 from .dynamics import native_plant
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind
-from .query import _descriptor, _point_scheme, _states_2d
+from .query import point_scheme, states_2d
 from .spatial import upwindFirstWENO5
 from .utilities import Bundle, error, info, isfield
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, device_data as _device_data,
-                       device_states as _device_states, stream as _stream, ptr as _ptr, fields as _fields)
+                       device_states as _device_states, stream as _stream, ptr as _ptr, fields as _fields,
+                       descriptor as _descriptor, dtype_name as _dtype_name)
 
 __all__ = ["computeOptTrajs", "REACHED", "EXHAUSTED", "LEFT_GRID"]
 
@@ -61,7 +62,7 @@ def _why_host(dynSys, derivFunc, g):
         return None, "%s has no native plant" % type(dynSys).__name__
     if _rffi.PLANT_DIMS.get(nat[0]) != g.dim:
         return None, "%s has no native plant on a %d-D grid" % (type(dynSys).__name__, g.dim)
-    if _point_scheme(derivFunc) is None:
+    if point_scheme(derivFunc) is None:
         return None, "derivFunc %s has no point kernel" % getattr(derivFunc, "__name__", derivFunc)
     return nat, None
 
@@ -70,8 +71,7 @@ def rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, want_te=Fals
     """hjr_rollout on device tensors: `data` a contiguous (T,) + g.shape stack, `xs` an (M, dim) fp64 tensor, `plant` an
     _rffi.Plant.  -> (traj (M, dim, T) fp64, length (M,) int32, tEarliest (M, T) int32 or None, status (M,) int32)."""
     torch = require_gpu()
-    dname = "float32" if data.dtype == torch.float32 else "float64"
-    desc, N = _descriptor(g, dname)
+    desc, N = _descriptor(g, _dtype_name(data))
     T, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim:
         error('states must be an (M, %d) array' % g.dim)
@@ -141,7 +141,7 @@ def computeOptTrajs(g, data, tau, dynSys, x0s, extraArgs=None):
     if subSamples < 1:
         error('subSamples must be positive')
     tensors = _wants_tensor(data) or _wants_tensor(x0s)
-    x0 = _states_2d(g, x0s)
+    x0 = states_2d(g, x0s)
     nat, why = _why_host(dynSys, derivFunc, g)
     if why is None:
         if uMode not in _MODES or (dMode is not None and dMode not in _MODES):
@@ -150,7 +150,7 @@ def computeOptTrajs(g, data, tau, dynSys, x0s, extraArgs=None):
         xs = _device_states(x0, t.device)
         plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
         dtSmall = (tau[1] - tau[0]) / subSamples                 # exactly as computeOptTraj forms it
-        trajs, lengths, te, status = rollout_states(g, t, xs, _point_scheme(derivFunc), subSamples, dtSmall, plant, want_te)
+        trajs, lengths, te, status = rollout_states(g, t, xs, point_scheme(derivFunc), subSamples, dtSmall, plant, want_te)
         _last_path = _rffi.last_kernel()
         if not tensors:
             trajs, lengths, status = (a.cpu().numpy() for a in (trajs, lengths, status))

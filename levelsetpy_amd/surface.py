@@ -19,7 +19,7 @@ import numpy as np
 from . import _sffi
 from .context import is_tensor, require_gpu
 from .lazy import HostView
-from ._marshal import device_data, fields, ptr, stream, unlazy, wants_tensor
+from ._marshal import device_data, dtype_name, fields, ptr, stream, unlazy, wants_tensor
 from .utilities import Bundle, error
 
 __all__ = ["extract_level_set", "level_set_measure", "implicit_mesh"]
@@ -89,8 +89,7 @@ def extract_level_set(g, data, level=0.0):
         error('extract_level_set works on 2-D and 3-D grids (this one has %d dimensions): take a slice or a '
               'projection with proj(g, data, dimsToRemove, xs) first' % g.dim)
     t = device_data(data)
-    dname = "float32" if str(t.dtype).endswith("float32") else "float64"
-    desc, N = descriptor(g, dname)
+    desc, N = descriptor(g, dtype_name(t))
     if tuple(t.shape) == tuple(N) + (1,):
         t = t.reshape(N)
     out = [_bundle(pair, data) for pair in extract_fields(desc, N, t, level)]
@@ -147,8 +146,7 @@ def implicit_mesh(surface, level=None, spacing=(1., 1., 1.), gd='ascent', edge_c
         level = 0.5 * (float(t.min()) + float(t.max()))
     N = tuple(int(n) for n in t.shape)
     dx = [float(s) for s in spacing]
-    dname = "float32" if str(t.dtype).endswith("float32") else "float64"
-    desc = _sffi.grid_descriptor(3, N, [0.0] * 3, [(n - 1) * h for n, h in zip(N, dx)], dx, [0] * 3, [0] * 3, dname)
+    desc = _sffi.grid_descriptor(3, N, [0.0] * 3, [(n - 1) * h for n, h in zip(N, dx)], dx, [0] * 3, [0] * 3, dtype_name(t))
     verts, faces = extract_fields(desc, N, t, level)[0]
     verts, faces = verts.cpu().numpy(), faces.cpu().numpy()
     if gd == 'descent':

@@ -2,7 +2,8 @@
 
   * the schedule planner against the oracle's odeCFL3 driven by HJIPDE_solve's time loop, times compared with ==, and
     hjb_plan (the same loop in C) against the planner;
-  * _bffi.SIGNATURES against the header and the built library's export table;
+  * the structs and enums of _bffi against the header, the census of the built library (the binding itself against the header
+    and the export table: tests/test_tool_libs_host.py);
   * the eligibility rule: every disqualifier selects the host loop, with its reason.
 """
 import ctypes as C
@@ -98,25 +99,6 @@ def test_c_planner_equals_the_python_planner():
 def header_text():
     txt = open(os.path.join(ROOT, "include", "hj_batch.h")).read()
     return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
-def test_signatures_name_exactly_the_declared_functions():
-    syms = sorted(set(re.findall(r"\b(hjb_[a-z0-9_]+)\s*\(", header_text())))
-    assert set(syms) == set(_bffi.SIGNATURES)
-    for need in ("hjb_step_bounds", "hjb_substep", "hjb_integrate", "hjb_last_error", "hjb_last_kernel"):
-        assert need in syms
-    out = subprocess.check_output(["nm", "-D", _bffi.LIB_PATH]).decode()
-    exported = set(re.findall(r" T (hjb_[a-z0-9_]+)", out))
-    assert exported == set(syms), (sorted(exported), syms)
-    lib = _bffi.lib()
-    for s in syms:
-        assert hasattr(lib, s)
-    # argument counts of the ctypes signatures against the declarations
-    for name, (_, args) in _bffi.SIGNATURES.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, header_text())
-        decl = m.group(1).strip()
-        n = 0 if decl in ("", "void") else decl.count(",") + 1
-        assert n == len(args), (name, n, len(args))
 
 
 def test_census_of_the_batch_library():

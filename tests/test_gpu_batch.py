@@ -27,7 +27,7 @@ torch = pytest.importorskip("torch")
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import levelsetpy_amd as L  # noqa: E402
-from levelsetpy_amd import _bffi, _ffi, batch, query  # noqa: E402
+from levelsetpy_amd import _bffi, _ffi, _marshal, batch  # noqa: E402
 from levelsetpy_amd.context import DeviceGrid  # noqa: E402
 from levelsetpy_amd.term import native_plan  # noqa: E402
 from oracle import hj_oracle as O  # noqa: E402
@@ -257,7 +257,7 @@ def params_dev(c):
 
 
 def substep(c, dtype, scheme, stage, ent, B=None, restrict=0, par=None):
-    desc, _ = query._descriptor(c.g, dtype)
+    desc, _ = _marshal.descriptor(c.g, dtype)
     tab = batch.tables(c.g, torch, torch.device("cuda", torch.cuda.current_device()), dtype)
     e = batch.upload_entries(ent, torch, "cuda")
     par = params_dev(c) if par is None else par
@@ -301,7 +301,7 @@ def test_integrate_orders_equal_hj_rk_integrate(order, dtype):
     c = case("integrator")
     dev = torch.device("cuda", torch.cuda.current_device())
     ham = c.systems[0].native()[0]
-    desc, _ = query._descriptor(c.g, dtype)
+    desc, _ = _marshal.descriptor(c.g, dtype)
     tab = batch.tables(c.g, torch, dev, dtype)
     par = params_dev(c)
     sbs = batch.step_bounds(c.g, tab, desc, ham, par, c.B, torch, dev)
@@ -347,7 +347,7 @@ def test_finished_problems_are_left_alone():
     c = case("dubins")
     dev = torch.device("cuda", torch.cuda.current_device())
     ham = c.systems[0].native()[0]
-    desc, N = query._descriptor(c.g, "float64")
+    desc, N = _marshal.descriptor(c.g, "float64")
     n = int(np.prod(N))
     tab = batch.tables(c.g, torch, dev)
     par = params_dev(c)[:2].contiguous()
@@ -482,7 +482,7 @@ def test_errors_name_the_problems():
     with pytest.raises(ValueError, match="target function"):
         L.HJIPDE_solve_batch(c.data0, c.tau, c.sds(), "minVWithL", L.Bundle(dict(quiet=True)))
     # the entry points refuse what they cannot run, and say so
-    desc, _ = query._descriptor(c.g, "float64")
+    desc, _ = _marshal.descriptor(c.g, "float64")
     tab = batch.tables(c.g, torch, torch.device("cuda", torch.cuda.current_device()))
     lib = _bffi.lib()
     ent = batch.upload_entries(entries(1), torch, "cuda")

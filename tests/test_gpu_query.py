@@ -30,7 +30,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import levelsetpy_amd as L  # noqa: E402
 from levelsetpy_amd import eval_u, eval_costate, proj  # noqa: E402  (the feature: missing before it)
-from levelsetpy_amd import _ffi, _qffi, query  # noqa: E402
+from levelsetpy_amd import _ffi, _marshal, _qffi, query  # noqa: E402
 from levelsetpy_amd.hji_solver import _eval_point  # noqa: E402
 from levelsetpy_amd.opt_traj import find_earliest_BRS_ind  # noqa: E402
 
@@ -461,7 +461,7 @@ def test_kernels_stay_inside_their_arrays(nd, dtype):
     lib = _qffi.lib()
     pd = (nd - 1,)
     g, og, _, xs, _ = case(nd, pd)
-    desc, N = query._descriptor(g, dtype)
+    desc, N = _marshal.descriptor(g, dtype)
     stack = torch.stack([dev(smooth(g, 3), dtype), dev(smooth(g, 4), dtype)])
     M = 130
     x_t = dev(xs[:M])
@@ -515,7 +515,7 @@ def test_kernels_stay_inside_their_arrays(nd, dtype):
 def test_entry_points_refuse_bad_arguments():
     lib = _qffi.lib()
     g, og, data, xs, _ = case(3, ())
-    desc, N = query._descriptor(g, "float64")
+    desc, N = _marshal.descriptor(g, "float64")
     d_t, x_t, o = dev(data), dev(xs[:4]), torch.empty(12, dtype=torch.float64, device="cuda")
     p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
     assert lib.hjq_costate_points(C.byref(desc), _ffi.WENO5, p(d_t), 1, d_t.numel(), p(x_t), 4, p(o), None, None, None, 0, None) == -3

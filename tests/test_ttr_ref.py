@@ -1,5 +1,5 @@
-"""The NumPy restatement of the time-to-reach recurrence (tests/ttr_ref.py) on closed forms, the binding against the header,
-and the golden pin of the initialisation branch (tests/golden/ttr.npz, generated from the reference's postTimeStepTTR by
+"""The NumPy restatement of the time-to-reach recurrence (tests/ttr_ref.py) on closed forms and the golden pin of the
+initialisation branch (tests/golden/ttr.npz, generated from the reference's postTimeStepTTR by
 tests/golden/make_golden_ttr.py).  No GPU: tests/test_gpu_ttr.py holds the kernels to this restatement bit for bit.
 
 Bound of (a): phi is linear in t, so the interpolated crossing time is psi / 0.8 exactly; the formula
@@ -8,14 +8,12 @@ of the data itself), each by at most half an ulp of a quantity no larger than ta
 """
 import json
 import os
-import re
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 import ttr_ref as R  # noqa: E402
@@ -91,21 +89,6 @@ def test_td2ttr_equals_its_own_step_by_step_fold(dtype):
                     b = R.fold(data, tau, level, R.mode_bits(crossing, interpolate))
                     assert a.dtype == b.dtype == np.float64
                     assert np.array_equal(a, b, equal_nan=True), (len(tau), level, crossing, interpolate)
-
-
-# ------------------------------------------------------------------------------------------ (e) binding against the header
-def test_binding_names_exactly_the_functions_of_the_header():
-    from levelsetpy_amd import _tffi
-    text = open(os.path.join(ROOT, "include", "hj_ttr.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    declared = set(re.findall(r"\b(hjt_\w+)\s*\(", text))
-    assert declared and declared == set(_tffi.SIGNATURES), (sorted(declared), sorted(_tffi.SIGNATURES))
-    for name in declared:                              # and every argument is accounted for
-        args = re.search(r"\b%s\s*\(([^)]*)\)" % name, text).group(1).strip()
-        count = 0 if args in ("", "void") else len(args.split(","))
-        assert count == len(_tffi.SIGNATURES[name][1]), name
-    assert (_tffi.FIRST, _tffi.NO_INTERP) == (R.FIRST, R.NO_INTERP)
-    assert re.search(r"HJT_FIRST\s*=\s*1\b", text) and re.search(r"HJT_NO_INTERP\s*=\s*2\b", text)
 
 
 # ------------------------------------------------------------------------------------------ (f) golden pin

@@ -1,0 +1,217 @@
+"""The argument checks of the five stateless libraries (libhj_query / surface / ttr / rollout / batch .so) as data: calls that
+are refused, or accepted as "nothing to do", before the first HIP call -- so they run on a machine without a GPU.
+
+Every case is (library, id, function, arguments, return code, word of <prefix>_last_error()).  An argument is an int, a float,
+None (a null pointer: every data pointer is null, so no case can reach a launch), FAKE (a non-null address where a check wants
+one: it is only compared with null, never read) or a Grid / Plant / Tables spec below, passed by address.
+tests/test_tool_libs_host.py asserts the cases through ctypes; tools/tool_lib_refusals.py dumps code and whole message of every
+call (to compare two builds of the libraries) and writes the same calls as a stand-alone C++ program (for the host sanitizers)."""
+import ctypes as C
+import math
+
+OK, EINVAL, EUNSUPPORTED = 0, -1, -3
+ENO2, WENO5 = 0, 2
+DUBINS, INTEGRATOR, USER = 0, 1, 100
+NAN = float("nan")
+FAKE = "fake"                     # (void*)0x1000
+
+LIBS = {"query": "hjq", "surface": "hjs", "ttr": "hjt", "rollout": "hjr", "batch": "hjb"}
+
+
+class Grid:
+    """hjq_grid by value: n nodes per axis from 0 with spacing 0.1, extrapolated; `put` overwrites (field, axis 0) entries."""
+    def __init__(self, ndim, n=8, dtype=0, **put):
+        self.ndim, self.dtype = ndim, dtype
+        self.N, self.xmin, self.xlast = [n] * 4, [0.0] * 4, [0.1 * (n - 1)] * 4
+        self.dx, self.bc, self.toward_zero = [0.1] * 4, [0] * 4, [0] * 4
+        for k, v in put.items():
+            getattr(self, k)[0] = v
+
+
+class Plant:
+    """hjr_plant: both modes min, every parameter 1."""
+    def __init__(self, id):
+        self.id = id
+
+
+class Tables:
+    """hjb_tables with every coordinate and aux table at FAKE."""
+
+
+def grid_variants(ndim, too_few):
+    """(id, Grid or None, word of the refusal the table of descriptor cases expects from query / rollout / surface)."""
+    return [("null", None, "null"), ("ndim0", Grid(0), "ndim"), ("ndim5", Grid(5), "ndim"), ("dtype7", Grid(ndim, dtype=7), "dtype"),
+            ("N0", Grid(ndim, N=0), "N[0]")] + [("N%d" % n, Grid(ndim, N=n), "N[0]") for n in too_few] + [
+            ("bc9", Grid(ndim, bc=9), "boundary"), ("dx0", Grid(ndim, dx=0.0), "dx"), ("dxnan", Grid(ndim, dx=NAN), "dx")]
+
+
+def cases():
+    out = []
+
+    def add(lib, cid, fn, args, rc, word=""):
+        out.append((lib, cid, LIBS[lib] + "_" + fn, args, rc, word))
+
+    # ---- query: (a) V at states, (b) costates, (c) projection
+    def query(g, scheme=ENO2, costate=None):
+        return [("interp_points", [g, None, 1, 0, None, 1, None, 0, None]),
+                ("costate_points", [g, scheme, None, 1, 0, None, 1, costate, None, None, None, 0, None]),
+                ("project_minmax", [g, None, 1, 0, 1, 0, None, None])]
+    for cid, g, word in grid_variants(2, ()):
+        for fn, args in query(g):
+            add("query", "%s-%s" % (fn, cid), fn, args, EINVAL, word)
+    for fn, args in query(Grid(2)):
+        add("query", "%s-nulldata" % fn, fn, args, EINVAL, "null")
+    for sch in (WENO5, 9):
+        add("query", "costate_points-scheme%d" % sch, *query(Grid(2), sch, FAKE)[1], EUNSUPPORTED, "scheme")   # its output is tested first
+
+    # ---- surface: the boundary kinds are not read, so bc 9 reaches the null-argument check
+    def surface(g):
+        return [("workspace_size", [g, 1, None]), ("count", [g, None, 1, 0, 0.0, None, 0, None, None]),
+                ("emit", [g, None, 1, 0, 0.0, None, 0, None, None, None, None])]
+    for cid, g, word in grid_variants(2, (1,)):
+        for fn, args in surface(g):
+            add("surface", "%s-%s" % (fn, cid), fn, args, EINVAL, "null" if cid == "bc9" else word)
+    for nd in (1, 4):
+        for fn, args in surface(Grid(nd)):
+            add("surface", "%s-ndim%d" % (fn, nd), fn, args, EUNSUPPORTED, "2-D and 3-D")
+    for fn, args in surface(Grid(3)):
+        add("surface", "%s-nulldata" % fn, fn, args, EINVAL, "null")
+    # no vertex and no face anywhere: nothing is launched and nothing is read (the addresses are only compared with null)
+    add("surface", "emit-nothing", "emit", [Grid(2), FAKE, 1, 0, 0.0, FAKE, 1 << 40, [0, 0], None, None, None], OK)
+
+    # ---- ttr: no descriptor; dtype, mode, n
+    def ttr(dtype=0, n=1, mode=0):
+        return [("ttr_init", [dtype, None, n, 0.0, 0.0, None, None, None]),
+                ("ttr_update", [dtype, None, n, 1.0, 0.0, 0.0, mode, None, None, None]),
+                ("ttr_from_stack", [dtype, None, 2, max(n, 0), n, None, 0.0, mode, None, None])]
+    for cid, kw, rc, word in (("dtype7", dict(dtype=7), EUNSUPPORTED, "dtype"), ("mode4", dict(mode=4), EINVAL, "mode"),
+                              ("n-1", dict(n=-1), EINVAL, "negative"), ("n0", dict(n=0), OK, ""), ("nulldata", {}, EINVAL, "null")):
+        for fn, args in ttr(**kw):
+            if cid != "mode4" or fn != "ttr_init":              # hjt_ttr_init takes no mode
+                add("ttr", "%s-%s" % (fn, cid), fn, args, rc, word)
+
+    # ---- rollout: the double integrator on a 2-D grid
+    def rollout(g, scheme=ENO2, plant=Plant(INTEGRATOR), nstates=1):
+        return ["rollout", [g, scheme, None, 2, 64, None, nstates, 4, 0.01, plant, None, None, None, None, None]]
+    for cid, g, word in grid_variants(2, ()):
+        add("rollout", "rollout-%s" % cid, *rollout(g), EINVAL, word)
+    for sch in (WENO5, 9):
+        add("rollout", "rollout-scheme%d" % sch, *rollout(Grid(2), sch), EUNSUPPORTED, "scheme")
+    add("rollout", "rollout-nullplant", *rollout(Grid(2), plant=None), EINVAL, "null plant")
+    add("rollout", "rollout-plant3d", *rollout(Grid(2), plant=Plant(DUBINS)), EINVAL, "3 states")
+    add("rollout", "rollout-userplant", *rollout(Grid(2), plant=Plant(USER)), EUNSUPPORTED, "plant 100")
+    add("rollout", "rollout-N2", *rollout(Grid(2, N=2)), EINVAL, "too small")
+    add("rollout", "rollout-nulldata", *rollout(Grid(2)), EINVAL, "null argument")
+    add("rollout", "rollout-nostates", *rollout(Grid(2), nstates=0), OK)
+
+    # ---- batch: the relative Dubins system on a 3-D grid; its own check reports a grid of another dimension
+    def batch(g, tab=Tables(), scheme=ENO2, ham=DUBINS):
+        return [("step_bounds", [g, tab, ham, None, 1, None, None, None, None]),
+                ("substep", [g, tab, scheme, ham, 1, 0, None, None, 1, None]),
+                ("integrate", [g, tab, scheme, ham, 3, 0, 0, None, None, None, 1, 0.0, 1.0, 0.8, 1e300, 1e-4, None, 0, None, None,
+                               None, None])]
+    for cid, g, word in grid_variants(3, (2,)):
+        for fn, args in batch(g):
+            add("batch", "%s-%s" % (fn, cid), fn, args, EINVAL, "dimensions" if cid in ("ndim0", "ndim5") else word)
+    for fn, args in batch(Grid(3), tab=None):
+        add("batch", "%s-nulltables" % fn, fn, args, EINVAL, "null")
+    for fn, args in batch(Grid(3), ham=INTEGRATOR):
+        add("batch", "%s-ham2d" % fn, fn, args, EINVAL, "2-D grids")
+    for fn, args in batch(Grid(3), ham=USER):
+        add("batch", "%s-userham" % fn, fn, args, EUNSUPPORTED, "Hamiltonian 100")
+    for sch in (WENO5, 9):
+        for fn, args in batch(Grid(3), scheme=sch)[1:]:
+            add("batch", "%s-scheme%d" % (fn, sch), fn, args, EUNSUPPORTED, "scheme")
+    for fn, args in batch(Grid(3)):
+        add("batch", "%s-nulldata" % fn, fn, args, EINVAL, "null argument")
+    add("batch", "nan_flags-dtype7", "nan_flags", [7, None, 1, 1, None, None], EINVAL, "dtype")
+    return out
+
+
+CASES = cases()
+
+
+# ------------------------------------------------------------------------------------------ through ctypes
+def modules():
+    from levelsetpy_amd import _bffi, _qffi, _rffi, _sffi, _tffi
+    return {"query": _qffi, "surface": _sffi, "ttr": _tffi, "rollout": _rffi, "batch": _bffi}
+
+
+def _ctypes_arg(a, keep):
+    from levelsetpy_amd import _bffi, _qffi, _rffi
+    if a is FAKE:
+        return 0x1000
+    if isinstance(a, list):
+        keep.append((C.c_int64 * len(a))(*a))
+        return keep[-1]
+    if isinstance(a, Grid):
+        g = _qffi.Grid()
+        g.ndim, g.dtype = a.ndim, a.dtype
+        for k in ("N", "xmin", "xlast", "dx", "bc", "toward_zero"):
+            for d in range(4):
+                getattr(g, k)[d] = getattr(a, k)[d]
+        keep.append(g)
+    elif isinstance(a, Plant):
+        keep.append(_rffi.plant_descriptor(a.id, 0, 0, [1.0] * 4))
+    elif isinstance(a, Tables):
+        t = _bffi.Tables()
+        for d in range(4):
+            t.coord[d] = t.aux[d] = 0x1000
+        keep.append(t)
+    else:
+        return a
+    return C.byref(keep[-1])
+
+
+def run(case, mods=None):
+    """-> (return code, <prefix>_last_error() text, <prefix>_last_kernel() text) of one case."""
+    lib_name, _, fn, args, _, _ = case
+    lib = (mods or modules())[lib_name].lib()
+    keep = []
+    rc = getattr(lib, fn)(*[_ctypes_arg(a, keep) for a in args])
+    pre = LIBS[lib_name]
+    return rc, getattr(lib, pre + "_last_error")().decode(), getattr(lib, pre + "_last_kernel")().decode()
+
+
+def line(case, rc, err, kernel):
+    return "%s %s rc=%d error=[%s] kernel=[%s]" % (case[0], case[1], rc, err, kernel)
+
+
+# ------------------------------------------------------------------------------------------ as a C++ program
+def _cxx_num(v):
+    if isinstance(v, float):
+        return "NAN" if math.isnan(v) else repr(v)
+    return "%dll" % v if abs(v) > 2 ** 31 else str(v)
+
+
+def cxx_program(lib_name):
+    """The cases of one library as a program that prints line() of each: link it with that library's .hip file."""
+    pre = LIBS[lib_name]
+    body = []
+    for k, case in enumerate(c for c in CASES if c[0] == lib_name):
+        decl, call = [], []
+        for j, a in enumerate(case[3]):
+            v = "a%d_%d" % (k, j)
+            if a is None:
+                call.append("nullptr")
+            elif a is FAKE:
+                call.append("(void*)0x1000")
+            elif isinstance(a, list):
+                decl.append("int64_t %s[] = {%s};" % (v, ", ".join(map(str, a))))
+                call.append(v)
+            elif isinstance(a, Grid):
+                rows = ", ".join("{%s}" % ", ".join(_cxx_num(x) for x in getattr(a, f)) for f in ("N", "xmin", "xlast", "dx", "bc", "toward_zero"))
+                decl.append("hjq_grid %s = {%d, %d, %s};" % (v, a.ndim, a.dtype, rows))
+                call.append("&" + v)
+            elif isinstance(a, Plant):
+                decl.append("hjr_plant %s = {%d, 0, 0, 0, {1.0, 1.0, 1.0, 1.0}};" % (v, a.id))
+                call.append("&" + v)
+            elif isinstance(a, Tables):
+                decl.append("hjb_tables %s = {{P, P, P, P}, {P, P, P, P}};" % v)
+                call.append("&" + v)
+            else:
+                call.append(_cxx_num(a))
+        body.append("    { %s\n      const int rc = %s(%s);\n      printf(\"%s %s rc=%%d error=[%%s] kernel=[%%s]\\n\", rc, %s_last_error(), %s_last_kernel()); }"
+                    % (" ".join(decl), case[2], ", ".join(call), case[0], case[1], pre, pre))
+    return ("#include <cmath>\n#include <cstdio>\n#include \"hj_%s.h\"\n\nint main() {\n    void* const P = (void*)0x1000;\n    (void)P;\n%s\n    return 0;\n}\n"
+            % (lib_name, "\n".join(body)))

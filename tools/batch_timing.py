@@ -48,7 +48,7 @@ def main():
     import torch
     assert torch.cuda.is_available(), "tools/batch_timing.py needs an MI355X: there is nothing to measure without one"
     import levelsetpy_amd as L
-    from levelsetpy_amd import _bffi, _ffi, batch, query
+    from levelsetpy_amd import _bffi, _ffi, _marshal, batch
 
     n = args.n
     gmin = np.array([[-.75, -1.25, -np.pi]]).T
@@ -81,7 +81,7 @@ def main():
             return [L.HJIPDE_solve(data0[b], tau, sds[b], 'minVOverTime', L.Bundle(dict(quiet=True, keepLast=True)))[0] for b in range(B)]
 
         # hjb_integrate alone, on buffers prepared once
-        desc, _ = query._descriptor(g, "float64")
+        desc, _ = _marshal.descriptor(g, "float64")
         tab = batch.tables(g, torch, dev)
         st, why = batch.classify(data0, sds, 'minVOverTime', ea)
         assert why is None, why
