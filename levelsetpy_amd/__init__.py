@@ -36,5 +36,8 @@ from .surface import extract_level_set, level_set_measure, implicit_mesh       #
 from .ttr import postTimeStepTTR, TD2TTR                                        # noqa: F401
 from .rollout import computeOptTrajs                                            # noqa: F401
 from .batch import HJIPDE_solve_batch                                           # noqa: F401
+from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCenter,   # noqa: F401
+                     shapeHyperplane, shapeHyperplaneByPoints, shapeUnion, shapeIntersection,
+                     shapeDifference, shapeComplement)
 
 __version__ = "0.1.0"
