@@ -39,5 +39,6 @@ from .batch import HJIPDE_solve_batch                                           
 from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCenter,   # noqa: F401
                      shapeHyperplane, shapeHyperplaneByPoints, shapeUnion, shapeIntersection,
                      shapeDifference, shapeComplement)
+from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
 
 __version__ = "0.1.0"

@@ -30,24 +30,7 @@ __global__ __launch_bounds__(256) void interp_points_kernel(const T* __restrict_
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (t >= nfields * M) return;
     const long long f = t / M, m = t - f * M;
-    int lo[MAXD];
-    double w[MAXD];
-    double v;
-    if (!locate(G, xs + m * G.ndim, lo, w)) {
-        v = __builtin_nan("");
-    } else {
-        const T* __restrict__ field = data + f * field_stride;
-        v = 0.0;
-        for (int c = 0; c < (1 << G.ndim); ++c) {
-            long long off;
-            const double wt = corner(G, lo, w, c, off);
-            if (wt != 0.0) {
-                const double val = (double)field[off];
-                const double p = wt * val;
-                v = v + p;
-            }
-        }
-    }
+    const double v = interp_value<T>(G, data + f * field_stride, xs + m * G.ndim);
     put<T>(out, t, v, out_f64);
 }
 

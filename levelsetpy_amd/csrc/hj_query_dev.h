@@ -1,4 +1,5 @@
-// Device code shared by the point kernels of libhj_query.so (hj_query.hip) and libhj_rollout.so (hj_rollout.hip): the grid as a
+// Device code shared by the point kernels of libhj_query.so (hj_query.hip), libhj_rollout.so (hj_rollout.hip) and
+// libhj_decomp.so (hj_decomp.hip): the grid as a
 // kernel sees it, the cell search, the corner weights, the stencil gather and the ordered sum over a state's corner lanes.
 // One source, so a value or a costate interpolated inside a rollout has the bits interp_points_kernel and
 // costate_points_kernel give for the same state.  At the end, the host function that fills the grid from the descriptor.
@@ -79,6 +80,28 @@ __device__ __forceinline__ double corner(const QGrid& G, const int* lo, const do
         wt *= up ? w[d] : (1.0 - w[d]);
     }
     return wt;
+}
+
+// V(x) of one field, the interpolant of include/hj_query.h in fp64: corners in ascending number, those of weight exactly 0
+// skipped, a multiply and an add per corner; NaN outside an extrapolated axis.  interp_points_kernel and the kernels of
+// libhj_decomp.so call this one function.
+template <typename T>
+__device__ __forceinline__ double interp_value(const QGrid& G, const T* __restrict__ field, const double* __restrict__ x) {
+#pragma clang fp contract(off)
+    int lo[MAXD];
+    double w[MAXD];
+    if (!locate(G, x, lo, w)) return __builtin_nan("");
+    double v = 0.0;
+    for (int c = 0; c < (1 << G.ndim); ++c) {
+        long long off;
+        const double wt = corner(G, lo, w, c, off);
+        if (wt != 0.0) {
+            const double val = (double)field[off];
+            const double p = wt * val;
+            v = v + p;
+        }
+    }
+    return v;
 }
 
 template <typename T> __device__ __forceinline__ bool finite(T v) { return v - v == T(0); }
