@@ -40,5 +40,6 @@ from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCe
                      shapeHyperplane, shapeHyperplaneByPoints, shapeUnion, shapeIntersection,
                      shapeDifference, shapeComplement)
 from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
+from .eikonal import signedDistance, addCRadius                                  # noqa: F401
 
 __version__ = "0.1.0"
