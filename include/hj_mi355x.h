@@ -433,6 +433,9 @@ unsigned long long hj_ctx_state_generation(hj_ctx* ctx);
  * launch (bench.py --gpus N --plan-only prints it for every rank before the node exists).  It runs the launch code of hj_rk_substep up to
  * the point where the kernel would be enqueued -- configuration choice by scheme / grid size, tile search, chunking against num_cus
  * compute units (0: 256, MI355X) -- with the occupancy taken from the kernel's launch bound instead of the runtime's query.
+ * So the kernel, the tile and the cap on a chunk are those of a live launch; the NUMBER of chunks (and with it planes per chunk and
+ * workgroups) is an estimate wherever the 4 GiB cap leaves it free: a live context chooses it from the runtime's occupancy, which is lower
+ * than the launch bound where the compiler needed more registers (fp32 ENO3 pair kernel, 8200 x 512 x 512: 4 chunks live, 3 planned).
  * halo_lo / halo_hi: the grid is a slab with pad planes on that side (hj_ctx_set_slab).  Built-in Hamiltonians only.
  * out_host[12] = {threads per workgroup, workgroups, tiles per plane, chunks, planes per chunk, tile extents on axes 1..3 (0 beyond the
  * dimension), LDS bytes per workgroup, workgroups per CU, slab flag, 0}; kernel_name_host receives the kernel's name (as hj_last_kernel).

@@ -594,7 +594,13 @@ XGMI_LINK_GBS = 153.0        # per link and neighbour, peak (the pool's figure f
 
 def plan_substep(N, bc, dtype, scheme, ham, stage, p0, p1, halo_lo=False, halo_hi=False, num_cus=256):
     """The launch plan of one substep over planes [p0, p1) -- kernel, workgroups, tiles, chunks -- from the C library's own launch
-    code run WITHOUT a device (hj_plan_substep).  Returns a dict."""
+    code run WITHOUT a device (hj_plan_substep).  Returns a dict.
+
+    The kernel, the tile and the cap on a chunk's length are what a live launch takes.  "chunks" / "chunk_planes" / "workgroups" are an
+    ESTIMATE wherever the chunk count is free (more than one count fits under the 4 GiB span): it is chosen from the workgroups a CU holds,
+    which the plan takes from the kernel's launch bound and a live context asks the runtime; where the compiler needed more registers than
+    the bound promises, the device makes another count (seen: the fp32 ENO3 pair kernel on 8200 x 512 x 512 runs 4 chunks of 2050 planes,
+    the plan says 3 of 2734).  With HJ_TARGET_BLOCKS=1, or where the cap decides, plan and launch agree."""
     import ctypes as C
     out = (C.c_int64 * 12)()
     name = C.create_string_buffer(64)

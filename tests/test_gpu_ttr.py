@@ -10,7 +10,8 @@ Sizes: n in {1, 7, 957, 1024, 1025} -- one node, less than a wavefront, the odd 
 passes of a workgroup's 512 nodes with a tail of one -- and PAST = 2048 blocks x 256 threads x 2 nodes + 77, at which the
 grid-stride loop takes a second pass.  T in {1, 2, 3, 5, 9, 17}: no update at all, and depths on both sides of the kernel's
 unroll by four (remainder loop only, one unrolled group, groups plus remainder).  field_stride in {n, n + 1, n + 3}: slices of
-alternating alignment.  64-bit indexing is verified by reading, not by a run: no test here holds 2^31 elements.
+alternating alignment.  64-bit indexing is run elsewhere: tests/test_gpu_large_arrays.py
+(test_tools_td2ttr_stack_past_2e31_elements) folds a stack of 17 x 2^27 elements, whose last slice starts at element 2^31.
 
 Kernel -> test that launches it (each test asserts the name through hjt_last_kernel; test_census_of_the_ttr_library checks
 the table against `nm -D libhj_ttr.so`):
