@@ -16,7 +16,7 @@ from .spatial import (upwindFirstENO2, upwindFirstENO3, upwindFirstENO3a, upwind
                       set_weno5_mode, get_weno5_mode, set_eno_mode, get_eno_mode)
 from .dissipation import (artificialDissipationGLF, artificialDissipationLLF,      # noqa: F401
                           artificialDissipationLLLF)
-from .dynamics import DubinsVehicleRel, DoubleIntegrator, DoublePendulum4D      # noqa: F401
+from .dynamics import DubinsVehicleRel, DoubleIntegrator, DoublePendulum4D, Plane5D, DubinsPair6D      # noqa: F401
 from .user_ham import register_native_hamiltonian, NativeRegistration, RegisteredSystem, kernel_cache_stats   # noqa: F401
 from .trace_ham import trace_callbacks, TraceError                              # noqa: F401
 from .term import termLaxFriedrichs, termRestrictUpdate, explain_plan           # noqa: F401
@@ -41,5 +41,6 @@ from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCe
                      shapeDifference, shapeComplement)
 from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
 from .eikonal import signedDistance, addCRadius                                  # noqa: F401
+from . import hidim                                                              # noqa: F401
 
 __version__ = "0.1.0"

@@ -282,37 +282,6 @@ static double key_to_double(unsigned long long k) {
     return v;
 }
 
-// the time a step of `order` from t with deltaT = dt reaches: the expressions of hj_rk_step (ode_cfl_1/2/3.py)
-static double step_time(int order, double t0, double dt) {
-    if (order == 1) return t0 + dt;
-    const double t1 = t0 + dt, t2 = t1 + dt;
-    if (order == 2) return 0.5 * (t0 + t2);
-    const double tHalf = 0.25 * (3 * t0 + t2);
-    const double tThreeHalf = tHalf + dt;
-    return (1.0 / 3.0) * (t0 + 2 * tThreeHalf);
-}
-
-// one problem's steps over [t0, tf]: dts gets deltaT of every step (may be null), t the time reached
-static int plan_problem(int order, double sb, double t0, double tf, double factor_cfl, double max_step, double stop_tol,
-                        std::vector<double>* dts, double& t, int64_t b) {
-    // the loop of odeCFLn (ode_cfl_3.py:125): while tf - t >= small*|tf|, small = 100*eps (:81); stop_tol >= 0: HJIPDE_solve's
-    const double small = 100.0 * 2.220446049250313e-16;
-    t = t0;
-    int64_t steps = 0;
-    auto more = [&]() { return stop_tol < 0 ? (tf - t >= small * std::fabs(tf)) : (t < tf - stop_tol); };
-    if (!(sb > 0.0)) return fail(HJ_EINVAL, "problem %lld: the step bound must be positive (got %g)", (long long)b, sb);
-    while (more()) {
-        // deltaT = min(factorCFL*stepBound, tspan[1]-t, maxStep)  (ode_cfl_3.py:142)
-        const double dt = std::min(std::min(factor_cfl * sb, tf - t), max_step);
-        const double tn = step_time(order, t, dt);
-        if (!(tn > t)) return fail(HJ_ESTATE, "problem %lld: time step underflow at t=%g (dt=%g)", (long long)b, t, dt);
-        if (++steps > (1ll << 24)) return fail(HJ_ESTATE, "problem %lld: more than 2^24 steps in one interval", (long long)b);
-        if (dts) dts->push_back(dt);
-        t = tn;
-    }
-    return HJ_OK;
-}
-
 }  // namespace hjb
 
 using namespace hjb;

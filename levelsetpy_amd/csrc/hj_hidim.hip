@@ -1,0 +1,627 @@
+// libhj_hidim.so (include/hj_hidim.h): Hamilton-Jacobi substeps on 5-D and 6-D grids, for gfx950.
+//   hidim_substep_kernel<T, HAM, SCHEME>  batch_substep_kernel (hj_batch.hip) without the problem axis: one thread per cell, every stencil load
+//                                         issued unconditionally, 256 threads per workgroup.  Everything rides in the kernel arguments.
+//   hidim_upwind_kernel<T, ND, SCHEME>    derivL / derivR of the axes of a mask from one gather per cell, and their 4 reductions per axis
+//   hidim_bound_kernel<T, HAM>            the per-axis maxima of alpha at zero costate
+// The per-cell functions (decode, gather_stencils, upwind_cd, upwind, rk_stage_out, post_step) are the solver's own source (hj_device.h,
+// hj_split.h), instantiated at ND = 5 and 6 and compiled with the solver's flags.  HJ_MAX_DIM stays 4: HamTables cannot hold the coordinates
+// of axes 4 and 5, so the two systems here read a table struct of their own (HiTables), and the one solver function that takes a HamTables,
+// lf_ydot, has its dissipation sum restated below (hidim_ydot).  The library links nothing of libhj_mi355x.so.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+#include "hj_tool_host.h"
+#include "hj_split.h"
+#include "../../include/hj_hidim.h"
+
+namespace hjh {
+
+using namespace hj;
+using namespace hj_tool;
+
+template <typename T> struct HiTables {
+    const T* coord[HJH_MAX_DIM];       // grid.vs[d]
+    const T* aux[4];                   // cos / sin tables (include/hj_hidim.h)
+    T par[HJH_PAR_SLOTS];
+};
+
+// ---- the systems.  Interface and scaling as hj_device.h's: cell() folds the costate scales sc[d] into the cell's coefficients, eval() takes
+// the UNSCALED costates q (p_d = sc[d] q_d), returns H(x, p) and alpha_s[d] = sc[d] alpha_d.  NP (ENO2 / ENO3, sc = 1): the expression of
+// include/hj_hidim.h operation by operation, each a statement of its own, contraction off.
+template <typename T> struct HamPlane5D {
+    static constexpr int ND = 5;
+    static constexpr int ID = HJH_HAM_PLANE5D;
+    struct Cell { T vc, vs, om, am, al, s; };      // sc0 (x3 cos x2), sc1 (x3 sin x2), sc2 x4, sc3 a_max, sc4 alpha_max, the sign
+    __device__ static __forceinline__ Cell cell(const HiTables<T>& P, const int* idx, const T* sc) {
+#pragma clang fp contract(off)
+        const T c = P.aux[0][idx[2]], s = P.aux[1][idx[2]];
+        const T v = P.coord[3][idx[3]], om = P.coord[4][idx[4]];
+        const T vc = v * c;
+        const T vs = v * s;
+        Cell k;
+        k.vc = sc[0] * vc;
+        k.vs = sc[1] * vs;
+        k.om = sc[2] * om;
+        k.am = sc[3] * P.par[0];
+        k.al = sc[4] * P.par[1];
+        k.s = P.par[2];
+        return k;
+    }
+    template <bool NP>
+    __device__ static __forceinline__ void eval(const Cell& k, const T* q, T& H, T* alpha) {
+        if constexpr (NP) {
+#pragma clang fp contract(off)
+            const T t0 = q[0] * k.vc;
+            const T t1 = q[1] * k.vs;
+            const T t2 = q[2] * k.om;
+            const T a3 = k.am * t_abs(q[3]);
+            const T t3 = k.s * a3;
+            const T a4 = k.al * t_abs(q[4]);
+            const T t4 = k.s * a4;
+            T h = t0 + t1;
+            h = h + t2;
+            h = h + t3;
+            h = h + t4;
+            H = h;
+        } else {
+            H = q[0] * k.vc + q[1] * k.vs + q[2] * k.om + k.s * (k.am * t_abs(q[3])) + k.s * (k.al * t_abs(q[4]));
+        }
+        alpha[0] = t_abs(k.vc);
+        alpha[1] = t_abs(k.vs);
+        alpha[2] = t_abs(k.om);
+        alpha[3] = k.am;
+        alpha[4] = k.al;
+    }
+};
+
+template <typename T> struct HamDubinsPair6D {
+    static constexpr int ND = 6;
+    static constexpr int ID = HJH_HAM_DUBINS_PAIR6D;
+    struct Cell { T a0, a1, we, a3, a4, wp; };     // sc0 v_e cos x2, sc1 v_e sin x2, sc2 w_e, sc3 v_p cos x5, sc4 v_p sin x5, sc5 w_p
+    __device__ static __forceinline__ Cell cell(const HiTables<T>& P, const int* idx, const T* sc) {
+#pragma clang fp contract(off)
+        const T ce = P.aux[0][idx[2]], se = P.aux[1][idx[2]];
+        const T cp = P.aux[2][idx[5]], sp = P.aux[3][idx[5]];
+        const T a0 = P.par[0] * ce;
+        const T a1 = P.par[0] * se;
+        const T a3 = P.par[1] * cp;
+        const T a4 = P.par[1] * sp;
+        Cell k;
+        k.a0 = sc[0] * a0;
+        k.a1 = sc[1] * a1;
+        k.we = sc[2] * P.par[2];
+        k.a3 = sc[3] * a3;
+        k.a4 = sc[4] * a4;
+        k.wp = sc[5] * P.par[3];
+        return k;
+    }
+    template <bool NP>
+    __device__ static __forceinline__ void eval(const Cell& k, const T* q, T& H, T* alpha) {
+        if constexpr (NP) {
+#pragma clang fp contract(off)
+            const T t0 = q[0] * k.a0;
+            const T t1 = q[1] * k.a1;
+            const T t3 = q[3] * k.a3;
+            const T t4 = q[4] * k.a4;
+            const T t2 = k.we * t_abs(q[2]);
+            const T t5 = k.wp * t_abs(q[5]);
+            T h = t0 + t1;
+            h = h + t3;
+            h = h + t4;
+            h = h + t2;
+            h = h - t5;
+            H = -h;
+        } else {
+            H = -(q[0] * k.a0 + q[1] * k.a1 + q[3] * k.a3 + q[4] * k.a4 + k.we * t_abs(q[2]) - k.wp * t_abs(q[5]));
+        }
+        alpha[0] = t_abs(k.a0);
+        alpha[1] = t_abs(k.a1);
+        alpha[2] = k.we;
+        alpha[3] = t_abs(k.a3);
+        alpha[4] = t_abs(k.a4);
+        alpha[5] = k.wp;
+    }
+};
+
+// lf_ydot (hj_device.h) for a system that reads HiTables: ydot = -(H - sum_d hd_d alpha_d), the sum in axis order, NP as there
+template <bool NP, typename HAM, typename T>
+__device__ __forceinline__ T hidim_ydot(const typename HAM::Cell& c, const T* pc, const T* hd, T* alpha) {
+    T H;
+    HAM::template eval<NP>(c, pc, H, alpha);
+    if constexpr (NP) {
+#pragma clang fp contract(off)
+        T diss = T(0);
+#pragma unroll
+        for (int d = 0; d < HAM::ND; ++d) diss = diss + hd[d] * alpha[d];
+        return -(H - diss);
+    } else {
+        T diss = T(0);
+#pragma unroll
+        for (int d = 0; d < HAM::ND; ++d) diss += hd[d] * alpha[d];
+        return -(H - diss);
+    }
+}
+
+// min / max against an array: batch_substep_kernel's expression, NaN propagating as NumPy's minimum / maximum
+template <typename T>
+__device__ __forceinline__ T array_op(int op, T a, T b) {
+    T r;
+    if (a != a) r = a;
+    else if (b != b) r = b;
+    else if (op == HJH_ARR_MIN) r = a < b ? a : b;
+    else if (op == HJH_ARR_MAX) r = a > b ? a : b;
+    else r = a > -b ? a : -b;
+    return r;
+}
+
+template <typename T, int ND> struct SubstepArgs {
+    GridArgs<T, ND> G;
+    T sc[ND];                          // costate scale of the scheme (hj_device.h)
+    HiTables<T> P;
+    const T* src;
+    const T* y0;
+    T* dst;
+    const T* post_a;
+    const T* post_b;
+    T dt;
+    int stage, restrict_sign, post_prev, op_a, op_b;
+};
+
+template <typename T, typename HAM, int SCHEME>
+__global__ __launch_bounds__(256) void hidim_substep_kernel(const SubstepArgs<T, HAM::ND> A) {
+    constexpr int ND = HAM::ND;
+    constexpr bool NP = np_order(SCHEME);
+    static_assert(SCHEME != HJ_WENO5, "the intended WENO5 needs an epsilon reduction over the grid");
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    if (t >= A.G.total) return;
+    const int stage = A.stage;
+    WenoK<T> wk;
+    wk.c13 = T(0); wk.c4 = T(0);
+    T ca = T(0), cb = T(1);
+    if (stage == HJ_STAGE_RK3_HALF) { ca = T(0.75); cb = T(0.25); }
+    else if (stage == HJ_STAGE_RK3_FULL) { ca = T(1.0 / 3.0); cb = T(2.0 / 3.0); }
+    else if (stage == HJ_STAGE_RK2_FULL) { ca = T(0.5); cb = T(0.5); }
+    const bool use_y0 = stage >= HJ_STAGE_RK3_HALF;
+    int idx[ND];
+    decode<T, ND>(A.G, t, idx);
+    const T* pc0 = A.src + t;
+    T v[ND][7];
+    const T centre = pc0[0];
+    const T y0v = use_y0 ? A.y0[t] : T(0);
+    const typename HAM::Cell hc = HAM::cell(A.P, idx, A.sc);
+    gather_stencils<T, ND>(A.G, pc0, idx, centre, v);
+    T pc[ND], hd[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], T(0), wk, pc[d], hd[d]);
+    T alpha[ND];
+    T ydot = hidim_ydot<NP, HAM>(hc, pc, hd, alpha);
+    // termRestrictUpdate clamp, written like direct_substep_kernel's (a NaN stays a NaN)
+    if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
+    else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
+    T o;
+    if (stage == HJ_STAGE_YDOT) o = ydot;
+    else {
+        o = rk_stage_out<NP>(stage, ca, cb, A.dt, y0v, centre, ydot);
+        if (A.post_prev) o = post_step(A.post_prev, o, use_y0 ? y0v : centre);
+        if (A.op_a) o = array_op(A.op_a, o, A.post_a[t]);
+        if (A.op_b) o = array_op(A.op_b, o, A.post_b[t]);
+    }
+    A.dst[t] = o;
+}
+
+// ENO2 / ENO3 one-sided derivatives with every operation rounded on its own: upwind_cd's exact branch (hj_device.h) stops at the centred
+// costate and the half jump, and L, R cannot be had back from those without a rounding.  Same tables (dd_tables), same selectors, same
+// order of operations; what the substep kernel differentiates is what this returns.
+template <int SCHEME, typename T>
+__device__ __forceinline__ void upwind_lr_exact(const T* v, const T* K, T& L, T& R) {
+#pragma clang fp contract(off)
+    DD<T> t;
+    dd_tables(v, K, t);
+    const T dx = K[3], dx2 = K[4], tdx2 = K[5];
+    const bool sL0 = t_abs(t.D2[1]) < t_abs(t.D2[2]), sL1 = t_abs(t.D2[2]) < t_abs(t.D2[3]);
+    if constexpr (SCHEME == HJ_ENO2) {
+        const T eL = dx * (sL0 ? t.D2[1] : t.D2[2]);
+        const T eR = dx * (sL1 ? t.D2[2] : t.D2[3]);
+        L = t.D1[2] + eL;
+        R = t.D1[3] - eR;
+    } else {
+        const bool sT0 = t_abs(t.D3[0]) < t_abs(t.D3[1]), sT1 = t_abs(t.D3[1]) < t_abs(t.D3[2]);
+        const bool sT2 = t_abs(t.D3[2]) < t_abs(t.D3[3]);
+        const bool lRR = !sL0 && !sT1;
+        const T l2 = dx * (lRR ? t.D2[2] : t.D2[1]);
+        const T l3a = tdx2 * ((sL0 && sT0) ? t.D3[0] : t.D3[1]);
+        const T l3b = dx2 * t.D3[2];
+        const T lb = t.D1[2] + l2;
+        L = lRR ? (lb - l3b) : (lb + l3a);
+        const bool rRR = !sL1 && !sT2;
+        const T r2 = dx * (rRR ? t.D2[3] : t.D2[2]);
+        const T r3a = dx2 * ((sL1 && sT1) ? t.D3[1] : t.D3[2]);
+        const T r3b = tdx2 * t.D3[3];
+        const T rb = t.D1[3] - r2;
+        R = rRR ? (rb + r3b) : (rb - r3a);
+    }
+}
+
+template <typename T, int ND> struct UpwindArgs {
+    GridArgs<T, ND> G;
+    const T* src;
+    T* dL[ND];
+    T* dR[ND];
+    unsigned long long* keys;          // 4 * HJH_MAX_DIM keys, or null
+    unsigned mask;
+};
+
+template <typename T, int ND, int SCHEME>
+__global__ __launch_bounds__(256) void hidim_upwind_kernel(const UpwindArgs<T, ND> A) {
+    static_assert(SCHEME != HJ_WENO5, "the intended WENO5 needs an epsilon reduction over the grid");
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const bool live = t < A.G.total;
+    __shared__ double red[4][4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    T v[ND][7];
+    if (live) {
+        int idx[ND];
+        decode<T, ND>(A.G, t, idx);
+        const T* pc0 = A.src + t;
+        gather_stencils<T, ND>(A.G, pc0, idx, pc0[0], v);
+    }
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        if (!((A.mask >> d) & 1u)) continue;           // uniform
+        double m[4] = {-1e300, -1e300, -1e300, -1e300};
+        if (live) {
+            T L, R;
+            if constexpr (np_order(SCHEME)) upwind_lr_exact<SCHEME, T>(v[d], A.G.K[d], L, R);
+            else upwind<SCHEME, T>(v[d], A.G.K[d], T(0), L, R);
+            A.dL[d][t] = L;
+            A.dR[d][t] = R;
+            m[0] = -(double)L; m[1] = (double)L; m[2] = -(double)R; m[3] = (double)R;
+        }
+        if (A.keys) {                                  // uniform
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double w = wave_max(m[k]);
+                if (lane == 0) red[wv][k] = w;
+            }
+            __syncthreads();
+            if (threadIdx.x < 4) {
+                const int k = threadIdx.x;
+                const double w = fmax(fmax(red[0][k], red[1][k]), fmax(red[2][k], red[3][k]));
+                if (w > -1e299) key_max(A.keys + 4 * d + k, w);
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// max over the grid of alpha_d at zero costate: batch_bound_kernel's evaluation (unit scales), one workgroup maximum per axis folded into
+// keys[d] (order-preserving keys, zero at launch)
+template <typename T, typename HAM>
+__global__ __launch_bounds__(256) void hidim_bound_kernel(const GridArgs<T, HAM::ND> G, const HiTables<T> P, unsigned long long* keys) {
+    constexpr int ND = HAM::ND;
+    double m[ND];
+    T one[ND], p[ND];
+#pragma unroll
+    for (int d = 0; d < ND; ++d) { m[d] = -1e300; one[d] = T(1); p[d] = T(0); }
+    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < G.total; t += (long long)gridDim.x * blockDim.x) {
+        int idx[ND];
+        decode<T, ND>(G, t, idx);
+        T H, a[ND];
+        HAM::template eval<false>(HAM::cell(P, idx, one), p, H, a);
+#pragma unroll
+        for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
+    }
+    __shared__ double red[4][ND];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+        const double w = wave_max(m[d]);
+        if (lane == 0) red[wv][d] = w;
+    }
+    __syncthreads();
+    if (threadIdx.x < ND) {
+        const int d = threadIdx.x;
+        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
+        if (w > -1e299) key_max(keys + d, w);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------- host side
+static int hidim_ham_ndim(int ham) { return ham == HJH_HAM_PLANE5D ? 5 : (ham == HJH_HAM_DUBINS_PAIR6D ? 6 : 0); }
+
+static int check_grid(const hjh_grid* g, long long& total) {
+    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    if (g->ndim < HJH_MIN_DIM || g->ndim > HJH_MAX_DIM)
+        return fail(HJ_EINVAL, "grid.ndim must be %d..%d here (got %d; 1..%d: the solver of hj_mi355x.h)", (int)HJH_MIN_DIM, (int)HJH_MAX_DIM,
+                    (int)g->ndim, HJ_MAX_DIM);
+    total = 1;
+    for (int d = 0; d < g->ndim; ++d) {
+        if (g->N[d] < HJ_STENCIL || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range (need %d .. 2^30)", d, (long long)g->N[d], HJ_STENCIL);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d])) return fail(HJ_EINVAL, "axis %d: dx must be positive and finite", d);
+        total *= g->N[d];
+        if (total > (1ll << 38)) return fail(HJ_EINVAL, "grid too large");
+    }
+    return HJ_OK;
+}
+
+// the checks every entry point that evaluates a system makes on (grid, tables, system, parameters)
+static int check_setup(const hjh_grid* g, const hjh_tables* tab, int ham, const double* params_host, long long& total) {
+    int rc = check_grid(g, total);
+    if (rc) return rc;
+    if (!tab) return fail(HJ_EINVAL, "null tables");
+    const int nd = hidim_ham_ndim(ham);
+    if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no kernel here (HJH_HAM_PLANE5D, HJH_HAM_DUBINS_PAIR6D)", ham);
+    if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
+    for (int d = 0; d < nd; ++d)
+        if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
+    const int naux = ham == HJH_HAM_PLANE5D ? 2 : 4;
+    for (int s = 0; s < naux; ++s)
+        if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
+    if (!params_host) return fail(HJ_EINVAL, "null parameters");
+    return HJ_OK;
+}
+
+// what a stage needs besides the setup; shared by hjh_substep and hjh_integrate
+static int check_ops(int restrict_sign, int post_prev, int op_a, const void* post_a, int op_b, const void* post_b) {
+    if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
+    if (op_a < HJH_ARR_NONE || op_a > HJH_ARR_MAX_NEG || op_b < HJH_ARR_NONE || op_b > HJH_ARR_MAX_NEG) return fail(HJ_EINVAL, "unknown array operator");
+    if ((op_a && !post_a) || (op_b && !post_b)) return fail(HJ_EINVAL, "an array operator without its array");
+    return HJ_OK;
+}
+
+// fill_grid of the solver (hj_host.h) from the descriptor: a single domain, no slab halos
+template <typename T, int ND> static void fill_grid(const hjh_grid* g, GridArgs<T, ND>& G) {
+    long long s = 1;
+    for (int d = ND - 1; d >= 0; --d) {
+        G.n[d] = (int)g->N[d];
+        G.bc[d] = g->bc[d];
+        G.km[d] = g->toward_zero[d] ? T(-1) : T(1);
+        G.inv_dx[d] = (T)(1.0 / g->dx[d]);
+        fill_stencil_constants<T>(g->dx[d], G.K[d]);
+        G.stride[d] = s;
+        s *= g->N[d];
+    }
+    G.halo_lo = 0;
+    G.halo_hi = 0;
+    G.total = s;
+}
+
+template <typename T> static void fill_tables(const hjh_tables* tab, const double* params_host, HiTables<T>& P) {
+    for (int d = 0; d < HJH_MAX_DIM; ++d) P.coord[d] = (const T*)tab->coord[d];
+    for (int s = 0; s < 4; ++s) P.aux[s] = (const T*)tab->aux[s];
+    for (int s = 0; s < HJH_PAR_SLOTS; ++s) P.par[s] = (T)params_host[s];
+}
+
+// one stage's pointers and scalars
+struct Stage {
+    const void* src;
+    const void* y0;
+    void* dst;
+    double dt;
+    int stage, post_prev, op_a, op_b;
+    const void* post_a;
+    const void* post_b;
+};
+
+template <typename T, typename HAM, int SCHEME>
+static int launch_substep(const hjh_grid* g, const hjh_tables* tab, int restrict_sign, const double* params_host, const Stage* st, int nst,
+                          hipStream_t stream, const char* name) {
+    constexpr int ND = HAM::ND;
+    SubstepArgs<T, ND> A;
+    memset(&A, 0, sizeof(A));
+    fill_grid<T, ND>(g, A.G);
+    for (int d = 0; d < ND; ++d) A.sc[d] = scheme_scale<T>(SCHEME, g->dx[d]);
+    fill_tables<T>(tab, params_host, A.P);
+    A.restrict_sign = restrict_sign;
+    unsigned bx;
+    int rc = blocks_for(A.G.total, "grid too large for one thread per cell", bx);
+    if (rc) return rc;
+    for (int k = 0; k < nst; ++k) {
+        const Stage& s = st[k];
+        A.src = (const T*)s.src; A.y0 = (const T*)s.y0; A.dst = (T*)s.dst;
+        A.post_a = (const T*)s.post_a; A.post_b = (const T*)s.post_b;
+        A.dt = (T)s.dt;
+        A.stage = s.stage; A.post_prev = s.post_prev; A.op_a = s.op_a; A.op_b = s.op_b;
+        hipLaunchKernelGGL((hidim_substep_kernel<T, HAM, SCHEME>), dim3(bx), dim3(256), 0, stream, A);
+        HIP_TRY(hipGetLastError());
+    }
+    launched(name);
+    return HJ_OK;
+}
+
+static int dispatch_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, int restrict_sign, const double* params_host,
+                            const Stage* st, int nst, hipStream_t stream) {
+#define HJH_GO(T, HAM, SCH) \
+    return launch_substep<T, HAM<T>, SCH>(g, tab, restrict_sign, params_host, st, nst, stream, "hidim_substep_kernel<" #T ", " #HAM ", " #SCH ">")
+#define HJH_HAMS(T, SCH)                                              \
+    do {                                                              \
+        if (ham == HJH_HAM_PLANE5D) HJH_GO(T, HamPlane5D, SCH);       \
+        HJH_GO(T, HamDubinsPair6D, SCH);                              \
+    } while (0)
+    static_assert(HJ_ENO2 == 0 && HJ_ENO3 == 1 && HJ_WENO5_ASSHIPPED == 3, "scheme ids name the kernels");
+    if (g->dtype == HJ_F64) {
+        if (scheme == HJ_ENO2) HJH_HAMS(double, 0);
+        if (scheme == HJ_ENO3) HJH_HAMS(double, 1);
+        HJH_HAMS(double, 3);
+    }
+    if (scheme == HJ_ENO2) HJH_HAMS(float, 0);
+    if (scheme == HJ_ENO3) HJH_HAMS(float, 1);
+    HJH_HAMS(float, 3);
+#undef HJH_HAMS
+#undef HJH_GO
+}
+
+template <typename T, int ND, int SCHEME>
+static int launch_upwind(const hjh_grid* g, const void* src, unsigned mask, void* const* dL, void* const* dR, unsigned long long* keys,
+                         hipStream_t stream, const char* name) {
+    UpwindArgs<T, ND> A;
+    memset(&A, 0, sizeof(A));
+    fill_grid<T, ND>(g, A.G);
+    A.src = (const T*)src;
+    for (int d = 0; d < ND; ++d)
+        if ((mask >> d) & 1u) { A.dL[d] = (T*)dL[d]; A.dR[d] = (T*)dR[d]; }
+    A.keys = keys;
+    A.mask = mask;
+    unsigned bx;
+    int rc = blocks_for(A.G.total, "grid too large for one thread per cell", bx);
+    if (rc) return rc;
+    if (keys) HIP_TRY(hipMemsetAsync(keys, 0, sizeof(unsigned long long) * 4 * HJH_MAX_DIM, stream));
+    hipLaunchKernelGGL((hidim_upwind_kernel<T, ND, SCHEME>), dim3(bx), dim3(256), 0, stream, A);
+    return launch_done(name);
+}
+
+static double key_to_double(unsigned long long k) {
+    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+    double v;
+    memcpy(&v, &b, 8);
+    return v;
+}
+
+}  // namespace hjh
+
+using namespace hjh;
+
+extern "C" {
+
+int hjh_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, int stage, int restrict_sign, const double* params_host,
+                const void* src, const void* y0, void* dst, double dt, int post_prev, int op_a, const void* post_a, int op_b,
+                const void* post_b, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, params_host, total);
+    if (rc) return rc;
+    if ((rc = check_point_scheme(scheme, "5-D / 6-D substep"))) return rc;
+    if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
+    if ((rc = check_ops(restrict_sign, post_prev, op_a, post_a, op_b, post_b))) return rc;
+    if (!src || !dst) return fail(HJ_EINVAL, "null argument");
+    if (src == dst) return fail(HJ_EINVAL, "dst must not alias src");
+    if (stage >= HJ_STAGE_RK3_HALF && !y0) return fail(HJ_EINVAL, "stage %d reads y0, which is null", stage);
+    const Stage st = {src, y0, dst, dt, stage, post_prev, op_a, op_b, post_a, post_b};
+    return dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, &st, 1, (hipStream_t)stream);
+}
+
+int hjh_step_bound(const hjh_grid* g, const hjh_tables* tab, int ham, const double* params_host, void* keys, double* sb_host,
+                   double* amax_host, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, params_host, total);
+    if (rc) return rc;
+    if (!keys || !sb_host) return fail(HJ_EINVAL, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* k = (unsigned long long*)keys;
+    HIP_TRY(hipMemsetAsync(k, 0, sizeof(unsigned long long) * HJH_MAX_DIM, s));
+    const unsigned bx = (unsigned)std::min<long long>((total + 255) / 256, 1024);
+#define HJH_B(T, HAM)                                                                                          \
+    do {                                                                                                       \
+        GridArgs<T, HAM<T>::ND> G;                                                                             \
+        memset(&G, 0, sizeof(G));                                                                              \
+        fill_grid<T, HAM<T>::ND>(g, G);                                                                        \
+        HiTables<T> P;                                                                                         \
+        fill_tables<T>(tab, params_host, P);                                                                   \
+        hipLaunchKernelGGL((hidim_bound_kernel<T, HAM<T>>), dim3(bx), dim3(256), 0, s, G, P, k);               \
+        HIP_TRY(hipGetLastError());                                                                            \
+        launched("hidim_bound_kernel<" #T ", " #HAM ">");                                                      \
+    } while (0)
+    if (g->dtype == HJ_F64) { if (ham == HJH_HAM_PLANE5D) HJH_B(double, HamPlane5D); else HJH_B(double, HamDubinsPair6D); }
+    else { if (ham == HJH_HAM_PLANE5D) HJH_B(float, HamPlane5D); else HJH_B(float, HamDubinsPair6D); }
+#undef HJH_B
+    unsigned long long h[HJH_MAX_DIM];
+    HIP_TRY(hipMemcpyAsync(h, k, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    // stepBound = 1 / sum_d max alpha_d / dx_d, summed in axis order (hjb_step_bounds)
+    double inv = 0.0;
+    for (int d = 0; d < g->ndim; ++d) {
+        const double a = key_to_double(h[d]);
+        if (amax_host) amax_host[d] = a;
+        inv += a / g->dx[d];
+    }
+    for (int d = g->ndim; d < HJH_MAX_DIM && amax_host; ++d) amax_host[d] = 0.0;
+    *sb_host = 1.0 / inv;
+    return HJ_OK;
+}
+
+int hjh_integrate(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, int order, int restrict_sign, int post_prev,
+                  const double* params_host, double sb, const void* y_in, void* buf_a, void* buf_b, void* work, int op_a,
+                  const void* post_a, int op_b, const void* post_b, double t0, double tf, double factor_cfl, double max_step,
+                  double stop_tol, double* t_host, int64_t* steps_host, int32_t* result_in_host, void* stream) {
+    long long total;
+    int rc = check_setup(g, tab, ham, params_host, total);
+    if (rc) return rc;
+    if ((rc = check_point_scheme(scheme, "5-D / 6-D substep"))) return rc;
+    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    if ((rc = check_ops(restrict_sign, post_prev, op_a, post_a, op_b, post_b))) return rc;
+    if (!y_in || !buf_a || !buf_b) return fail(HJ_EINVAL, "null buffer");
+    if (order >= 2 && !work) return fail(HJ_EINVAL, "work buffer required for order >= 2");
+    if (buf_a == buf_b || buf_a == y_in || buf_b == y_in || work == y_in || work == buf_a || work == buf_b)
+        return fail(HJ_EINVAL, "buffers must be distinct");
+    // the schedule: the time arithmetic of hjb_plan (hj_tool_host.h), known before the first launch because alpha ignores the data
+    std::vector<double> dts;
+    double tend;
+    if ((rc = plan_problem(order, sb, t0, tf, factor_cfl, max_step, stop_tol, &dts, tend, 0))) return rc;
+    const int64_t n = (int64_t)dts.size();
+    std::vector<Stage> st;
+    st.reserve((size_t)(n * order));
+    void* outs[2] = {buf_a, buf_b};
+    const void* cur = y_in;
+    for (int64_t k = 0; k < n; ++k) {
+        void* nxt = outs[k & 1];
+        const double dt = dts[(size_t)k];
+        // RK3: the first stage buffer doubles as the output; RK2: `work` is the first stage buffer (hj_rk_integrate)
+        if (order == 1) st.push_back(Stage{cur, nullptr, nxt, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
+        else if (order == 2) {
+            st.push_back(Stage{cur, nullptr, work, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
+            st.push_back(Stage{work, cur, nxt, dt, HJ_STAGE_RK2_FULL, 0, 0, 0, nullptr, nullptr});
+        } else {
+            st.push_back(Stage{cur, nullptr, nxt, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
+            st.push_back(Stage{nxt, cur, work, dt, HJ_STAGE_RK3_HALF, 0, 0, 0, nullptr, nullptr});
+            st.push_back(Stage{work, cur, nxt, dt, HJ_STAGE_RK3_FULL, 0, 0, 0, nullptr, nullptr});
+        }
+        Stage& last = st.back();
+        last.post_prev = post_prev;
+        last.op_a = op_a; last.post_a = op_a ? post_a : nullptr;
+        last.op_b = op_b; last.post_b = op_b ? post_b : nullptr;
+        cur = nxt;
+    }
+    if (n > 0 && (rc = dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, st.data(), (int)st.size(), (hipStream_t)stream))) return rc;
+    if (t_host) *t_host = tend;
+    if (steps_host) *steps_host = n;
+    if (result_in_host) *result_in_host = n == 0 ? 0 : 1 + (int32_t)((n - 1) & 1);
+    return HJ_OK;
+}
+
+int hjh_upwind(const hjh_grid* g, int scheme, const void* src, unsigned axis_mask, void* const* derivL_host, void* const* derivR_host,
+               void* keys, void* stream) {
+    long long total;
+    int rc = check_grid(g, total);
+    if (rc) return rc;
+    if ((rc = check_point_scheme(scheme, "5-D / 6-D derivative"))) return rc;
+    if (axis_mask == 0 || (axis_mask >> g->ndim)) return fail(HJ_EINVAL, "axis_mask 0x%x names no axis or one beyond the grid's %d", axis_mask, (int)g->ndim);
+    if (!src || !derivL_host || !derivR_host) return fail(HJ_EINVAL, "null argument");
+    for (int d = 0; d < g->ndim; ++d)
+        if (((axis_mask >> d) & 1u) && (!derivL_host[d] || !derivR_host[d])) return fail(HJ_EINVAL, "null output array of axis %d", d);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long* k = (unsigned long long*)keys;
+#define HJH_U(T, ND, SCH) \
+    return launch_upwind<T, ND, SCH>(g, src, axis_mask, derivL_host, derivR_host, k, s, "hidim_upwind_kernel<" #T ", " #ND ", " #SCH ">")
+#define HJH_DIMS(T, SCH)                        \
+    do {                                        \
+        if (g->ndim == 5) HJH_U(T, 5, SCH);     \
+        HJH_U(T, 6, SCH);                       \
+    } while (0)
+    if (g->dtype == HJ_F64) {
+        if (scheme == HJ_ENO2) HJH_DIMS(double, 0);
+        if (scheme == HJ_ENO3) HJH_DIMS(double, 1);
+        HJH_DIMS(double, 3);
+    }
+    if (scheme == HJ_ENO2) HJH_DIMS(float, 0);
+    if (scheme == HJ_ENO3) HJH_DIMS(float, 1);
+    HJH_DIMS(float, 3);
+#undef HJH_DIMS
+#undef HJH_U
+}
+
+HJ_TOOL_LAST_SYMBOLS(hjh)
+
+}  // extern "C"

@@ -35,6 +35,8 @@ def glf_device(t, data, derivL, derivR, schemeData, ham=None):
     from .spatial import cached_minmax
     grid = schemeData.grid
     dim = grid.dim
+    if dim > 4:
+        return None                    # 5-D / 6-D: the array expressions of artificialDissipationGLF (hidim.py)
     if not all(is_tensor(a) and a.is_cuda for a in list(derivL) + list(derivR)) or (ham is not None and not is_tensor(ham)):
         return None
     dg = device_grid(grid, array_dtype_name(derivL[0]))

@@ -1,6 +1,7 @@
 """Problem callbacks with a native (fused-kernel) implementation:
 DubinsVehicleRel (reference DynamicalSystems/dubins_relative.py:12), DoubleIntegrator
-(double_integrator.py:9) and the build-defined DoublePendulum4D (BASELINE config C5).
+(double_integrator.py:9), the build-defined DoublePendulum4D (BASELINE config C5), and the 5-D / 6-D systems
+Plane5D and DubinsPair6D, whose kernels live in libhj_hidim.so (include/hj_hidim.h, hidim.py).
 
 Each class keeps the reference's callback protocol -- `.hamiltonian(t, data, derivs, sd)` and
 `.dissipation(t, data, derivMin, derivMax, sd, dim)` work on NumPy arrays or torch tensors, for
@@ -15,10 +16,10 @@ Hamiltonian is the optimum of.  One state at a time, in fp64, one operation per 
 """
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _hffi
 from .context import is_tensor
 
-__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "native_of", "native_again", "native_plant"]
+__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "Plane5D", "DubinsPair6D", "native_of", "native_again", "native_plant"]
 
 
 def native_again(system):
@@ -297,6 +298,126 @@ class DoublePendulum4D(object):
         return self.x
 
 
+class Plane5D(object):
+    """A planar vehicle with speed and turn rate as states: (x, y, theta, v, omega) with xdot = v cos theta,
+    ydot = v sin theta, thetadot = omega, vdot = a, omegadot = alpha, |a| <= a_max, |alpha| <= alpha_max.  u_mode 'min':
+    the controls minimise (s = -1), 'max': they maximise (s = +1):
+        H = p0 (x3 cos x2) + p1 (x3 sin x2) + p2 x4 + s (a_max |p3|) + s (alpha_max |p4|)      summed left to right
+        alpha = { |x3 cos x2|, |x3 sin x2|, |x4|, a_max, alpha_max }
+    hidim_substep_kernel<T, HamPlane5D, SCHEME> (csrc/hj_hidim.hip) restates these expressions operation by operation."""
+
+    def __init__(self, grid, a_max=1.0, alpha_max=1.0, u_mode='min'):
+        self.grid = grid
+        self.a_max = a_max
+        self.alpha_max = alpha_max
+        self.u_mode = _mode(u_mode)
+
+    def _s(self):
+        return -1.0 if self.u_mode == 'min' else 1.0
+
+    def native(self):
+        if self.grid.dim != 5 or not (np.isscalar(self.a_max) and np.isscalar(self.alpha_max)) or self.u_mode not in ('min', 'max'):
+            return None
+        return _hffi.HAM_PLANE5D, [float(self.a_max), float(self.alpha_max), self._s(), 0.0]
+
+    def hamiltonian(self, t, data, value_derivs, finite_diff_bundle=None):
+        p = value_derivs
+        x2, x3, x4 = (_xs(self.grid, i, p[0]) for i in (2, 3, 4))
+        s = self._s()
+        return (p[0] * (x3 * _cos(x2)) + p[1] * (x3 * _sin(x2)) + p[2] * x4 + s * (self.a_max * _abs(p[3]))
+                + s * (self.alpha_max * _abs(p[4])))
+
+    def dissipation(self, t, data, derivMin, derivMax, schemeData, dim):
+        assert 0 <= dim < 5, "Plane5D has dimensions 0 to 4."
+        if dim == 0:
+            return _abs(_xs(self.grid, 3, data) * _cos(_xs(self.grid, 2, data)))
+        if dim == 1:
+            return _abs(_xs(self.grid, 3, data) * _sin(_xs(self.grid, 2, data)))
+        if dim == 2:
+            return _abs(_xs(self.grid, 4, data))
+        return self.a_max if dim == 3 else self.alpha_max
+
+    # ---- the dynSys protocol: u = (a, alpha), no disturbance
+    x = None
+
+    def dynamics(self, t, x, u, d=None):
+        x = _state(x)
+        th, v, om = float(x[2]), float(x[3]), float(x[4])
+        return np.array([v * float(np.cos(th)), v * float(np.sin(th)), om, float(u[0]), float(u[1])])
+
+    def get_opt_u(self, t, deriv, uMode, x):
+        a = float(self.a_max) * _sgn(deriv[3])
+        al = float(self.alpha_max) * _sgn(deriv[4])
+        return (a, al) if _mode(uMode, self.u_mode) == 'max' else (-a, -al)
+
+    def get_opt_v(self, t, deriv, dMode, x):
+        return None
+
+    def update_state(self, u, dt, x, d=None):
+        self.x = _rk4(lambda z: self.dynamics(None, z, u), x, dt)
+        return self.x
+
+
+class DubinsPair6D(object):
+    """Two Dubins vehicles in ABSOLUTE coordinates: evader (x0, x1, x2), pursuer (x3, x4, x5), speeds v_e / v_p, turn rates
+    |u| <= w_e / |d| <= w_p.  The convention of the reference's Dubins game (dubins_relative.py:63-111): the evader
+    maximises, the pursuer minimises, H is the negated optimum:
+        H = -( p0 (v_e cos x2) + p1 (v_e sin x2) + p3 (v_p cos x5) + p4 (v_p sin x5) + w_e |p2| - w_p |p5| )   left to right
+        alpha = { |v_e cos x2|, |v_e sin x2|, w_e, |v_p cos x5|, |v_p sin x5|, w_p }
+    hidim_substep_kernel<T, HamDubinsPair6D, SCHEME> (csrc/hj_hidim.hip) restates these expressions operation by operation."""
+
+    def __init__(self, grid, v_e=5, v_p=5, w_e=5, w_p=5):
+        self.grid = grid
+        self.v_e, self.v_p, self.w_e, self.w_p = v_e, v_p, w_e, w_p
+
+    def native(self):
+        if self.grid.dim != 6 or not all(np.isscalar(v) for v in (self.v_e, self.v_p, self.w_e, self.w_p)):
+            return None
+        return _hffi.HAM_DUBINS_PAIR6D, [float(self.v_e), float(self.v_p), float(self.w_e), float(self.w_p)]
+
+    def hamiltonian(self, t, data, value_derivs, finite_diff_bundle=None):
+        p = value_derivs
+        x2, x5 = _xs(self.grid, 2, p[0]), _xs(self.grid, 5, p[0])
+        return -(p[0] * (self.v_e * _cos(x2)) + p[1] * (self.v_e * _sin(x2)) + p[3] * (self.v_p * _cos(x5))
+                 + p[4] * (self.v_p * _sin(x5)) + self.w_e * _abs(p[2]) - self.w_p * _abs(p[5]))
+
+    def dissipation(self, t, data, derivMin, derivMax, schemeData, dim):
+        assert 0 <= dim < 6, "DubinsPair6D has dimensions 0 to 5."
+        if dim == 0:
+            return _abs(self.v_e * _cos(_xs(self.grid, 2, data)))
+        if dim == 1:
+            return _abs(self.v_e * _sin(_xs(self.grid, 2, data)))
+        if dim == 3:
+            return _abs(self.v_p * _cos(_xs(self.grid, 5, data)))
+        if dim == 4:
+            return _abs(self.v_p * _sin(_xs(self.grid, 5, data)))
+        return self.w_e if dim == 2 else self.w_p
+
+    # ---- the dynSys protocol: u the evader's turn rate, d the pursuer's
+    x = None
+
+    def dynamics(self, t, x, u, d):
+        x = _state(x)
+        ve, vp = float(self.v_e), float(self.v_p)
+        return np.array([ve * float(np.cos(x[2])), ve * float(np.sin(x[2])), float(u),
+                         vp * float(np.cos(x[5])), vp * float(np.sin(x[5])), float(d)])
+
+    def get_opt_u(self, t, deriv, uMode, x):
+        """uMode None: 'max', the evader of the class's own Hamiltonian."""
+        a = float(self.w_e) * _sgn(deriv[2])
+        return a if _mode(uMode, 'max') == 'max' else -a
+
+    def get_opt_v(self, t, deriv, dMode, x):
+        """dMode None: 'min', the pursuer of the class's own Hamiltonian."""
+        b = float(self.w_p) * _sgn(deriv[5])
+        return b if _mode(dMode, 'min') == 'max' else -b
+
+    def update_state(self, u, dt, x, d=None):
+        d = 0.0 if d is None else d
+        self.x = _rk4(lambda z: self.dynamics(None, z, u, d), x, dt)
+        return self.x
+
+
 def native_of(hamFunc, partialFunc):
     """(system, ham_id, params) when hamFunc/partialFunc are the bound methods of ONE of the
     systems above (so the fused kernel computes exactly what the callbacks would), else None.
@@ -312,7 +433,7 @@ def native_of(hamFunc, partialFunc):
         if getattr(hamFunc, "__func__", None) is not att.ham_func or getattr(partialFunc, "__func__", None) is not att.diss_func:
             return None
         return sys_h, att.reg.ham_id, att.params(sys_h)
-    owner = next((k for k in (DubinsVehicleRel, DoubleIntegrator, DoublePendulum4D) if isinstance(sys_h, k)), None)
+    owner = next((k for k in (DubinsVehicleRel, DoubleIntegrator, DoublePendulum4D, Plane5D, DubinsPair6D) if isinstance(sys_h, k)), None)
     if owner is None:
         return None
     if getattr(hamFunc, "__func__", None) is not owner.hamiltonian:

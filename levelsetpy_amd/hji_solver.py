@@ -133,6 +133,9 @@ def _trim(g, a):
 
 
 def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
+    if int(schemeData.grid.dim) > 4:   # 5-D / 6-D grids: libhj_hidim.so (hidim.py); 7-D and beyond are refused there
+        from . import hidim
+        return hidim.solve(data0, tau, schemeData, compMethod, extraArgs)
     extraArgs = extraArgs if extraArgs is not None else Bundle({})
     extraOuts = Bundle({})
     quiet = bool(_get(extraArgs, 'quiet', False))

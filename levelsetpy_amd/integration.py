@@ -164,6 +164,9 @@ def _integrate(order, schemeFunc, tspan, y0, options, schemeData):
         raise ValueError('vector level sets (list y0) are not supported (broken in the reference: '
                          'ode_cfl_3.py:147-149)')
     dev = _device_plan(schemeFunc, schemeData, y0)
+    if dev is not None and dev[0][0].dim > 4:
+        _check_shape(schemeFunc, y0)
+        dev = None                     # 5-D / 6-D: the generic loop below, its schemeFunc calls run hidim_substep_kernel (hidim.py)
     if dev is not None:
         _check_shape(schemeFunc, y0)
         return _integrate_device(order, dev, tspan, y0, options, schemeData, schemeFunc)
@@ -317,7 +320,7 @@ def integrate_span_device(schemeFunc, schemeData, y, t0, tf, options, stop_tol, 
     min/max-over-time operator of :571-575 fused into the last RK stage): steps while t < tf - stop_tol.
     `y` is a device tensor; returns (t, new device tensor), or None if the problem cannot run fused."""
     dev = _device_plan(schemeFunc, schemeData, y)
-    if dev is None:
+    if dev is None or dev[0][0].dim > 4:
         return None
     plan, rs = dev
     grid, sid, ham, par = plan
@@ -352,6 +355,8 @@ def _any_device_grid(schemeData, like):
         if sd is None:
             return None
         if isfield(sd, 'grid'):
+            if sd.grid.dim > 4:
+                return None            # 5-D / 6-D grids have no hj_ctx: the stage expressions run as array expressions
             try:
                 return device_grid(sd.grid, array_dtype_name(like))
             except (ValueError, RuntimeError):

@@ -67,6 +67,9 @@ def scheme_id_of(fn):
 def _upwind(scheme_name, grid, data, dim):
     if dim < 0 or dim >= grid.dim:
         error('Illegal dim parameter')
+    if grid.dim > 4:                   # 5-D / 6-D: hidim_upwind_kernel (libhj_hidim.so)
+        from . import hidim
+        return hidim.upwind_one(scheme_name, grid, data, dim)
     dg = device_grid(grid, array_dtype_name(data))
     if tuple(data.shape) != dg.shape:
         error('data parameter does not agree in array size with grid')
@@ -90,6 +93,9 @@ def upwind_all_dims(fn, grid, data):
     sid = scheme_id_of(fn)
     if sid is None or not is_tensor(data):
         return None
+    if grid.dim > 4:                   # 5-D / 6-D: one launch of hidim_upwind_kernel (libhj_hidim.so)
+        from . import hidim
+        return hidim.upwind_all(sid, grid, data)
     dg = device_grid(grid, array_dtype_name(data))
     if tuple(data.shape) != dg.shape:
         error('data parameter does not agree in array size with grid')
@@ -120,6 +126,8 @@ def _candidates(grid, data, dim, order, approx4=False, want_dd=False):
     the padded array's divided differences (compatibility path: array ops on the device).  With want_dd the
     divided-difference tables come back too, stripped as the reference returns them (ENO3aHelper.py:99-112:
     D1 with N+1 entries along dim, D2 with N+2, D3 with N+3)."""
+    if grid.dim > 4:
+        error('generateAll has no implementation on grids of 5 or 6 dimensions')
     dg = device_grid(grid, "float64")
     g = grid.bdry[dim](dg.to_device(data), dim, order, grid.bdryData[dim])
     dx = dg.dx[dim]

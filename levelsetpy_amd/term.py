@@ -123,6 +123,12 @@ def explain_plan(schemeData):
     if sd.dissFunc not in (artificialDissipationGLF, artificialDissipationLLF, artificialDissipationLLLF):
         return dict(path='split', reason='dissFunc is not one of this package\'s artificialDissipation* functions')
     plan = _plan_of(sd)
+    if int(sd.grid.dim) > 4:
+        # 5-D / 6-D grids (hidim.py): the two systems of libhj_hidim.so run fused, everything else through hjh_upwind and array expressions
+        if plan is not None:
+            return dict(path='built-in', ham_id=plan[2], params=list(plan[3]), library='libhj_hidim.so')
+        return dict(path='split', reason='on a grid of %d dimensions only Plane5D / DubinsPair6D with artificialDissipationGLF run fused; the '
+                                         'tracer stops at 4-D' % int(sd.grid.dim), library='libhj_hidim.so')
     if plan is not None and not plan.traced:
         return dict(path='registered' if plan[2] >= _ffi.HAM_USER_BASE else 'built-in', ham_id=plan[2], params=list(plan[3]))
     if not _trace.enabled():
@@ -180,6 +186,8 @@ def _classify(sd, fn):
     if sid is None or sd.dissFunc not in (artificialDissipationGLF, artificialDissipationLLF, artificialDissipationLLLF):
         return None
     nat = native_of(sd.hamFunc, sd.partialFunc)
+    if int(sd.grid.dim) > 4 and sd.dissFunc is not artificialDissipationGLF:
+        return None                    # 5-D / 6-D: the fused kernel is the global Lax-Friedrichs term; the local ones run as array expressions
     traced = False
     try:
         from .context import grid_bc
@@ -285,6 +293,9 @@ def _drop_traced(reg, sd):
 
 def _fused_term(plan, t, y, restrict_sign):
     grid, sid, ham, par = plan
+    if grid.dim > 4:                   # 5-D / 6-D: hidim_substep_kernel (libhj_hidim.so)
+        from . import hidim
+        return hidim.fused_term(plan, t, y, restrict_sign)
     dg = device_grid(grid, array_dtype_name(y))
     if int(np.prod(y.shape)) != dg.numel:
         raise ValueError('y does not agree in size with grid')
