@@ -5,7 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _qffi
+from . import _hffi, _qffi
 from .context import array_dtype_name as dtype_name, grid_bc, is_tensor, require_gpu, _raw_stream_getter   # noqa: F401
 from .lazy import HostView, DeviceArray
 from .utilities import error
@@ -77,3 +77,20 @@ def descriptor(g, dtype_name):
     if g.dim > _qffi.MAX_DIM:
         error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
     return _qffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)
+
+
+def descriptor_hi(g, dtype_name):
+    """descriptor's sibling for the queries of libhj_hiquery.so: (hjh_grid of a 5-D or 6-D grid g, g's shape as a tuple)."""
+    if not _hffi.MIN_DIM <= g.dim <= _hffi.MAX_DIM:
+        error('grid.dim must be %d..%d for the 5-D / 6-D queries (got %d): grids of more than %d dimensions have no device implementation'
+              % (_hffi.MIN_DIM, _hffi.MAX_DIM, g.dim, _hffi.MAX_DIM))
+    N = [int(v) for v in np.asarray(g.N).ravel()]
+    dx = [float(v) for v in np.asarray(g.dx).ravel()]
+    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
+    bc, tz = grid_bc(g)
+    return _hffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)
+
+
+def is_hi(g):
+    """Whether grid g's queries run in libhj_hiquery.so (more than _qffi.MAX_DIM axes) and not in libhj_query.so / libhj_rollout.so."""
+    return g.dim > _qffi.MAX_DIM

@@ -248,6 +248,47 @@ __device__ __forceinline__ void upwind(const T* v, const T* K, T eps, T& L, T& R
     }
 }
 
+// ENO2 / ENO3 one-sided derivatives with every operation rounded on its own: upwind_cd's exact branch (below) stops at the centred
+// costate and the half jump, and L, R cannot be had back from those without a rounding.  Same tables (dd_tables), same selectors, same
+// order of operations; what the 5-D / 6-D substep kernel (hj_hidim.hip) differentiates is what this returns.
+template <int SCHEME, typename T>
+__device__ __forceinline__ void upwind_lr_exact(const T* v, const T* K, T& L, T& R) {
+#pragma clang fp contract(off)
+    DD<T> t;
+    dd_tables(v, K, t);
+    const T dx = K[3], dx2 = K[4], tdx2 = K[5];
+    const bool sL0 = t_abs(t.D2[1]) < t_abs(t.D2[2]), sL1 = t_abs(t.D2[2]) < t_abs(t.D2[3]);
+    if constexpr (SCHEME == HJ_ENO2) {
+        const T eL = dx * (sL0 ? t.D2[1] : t.D2[2]);
+        const T eR = dx * (sL1 ? t.D2[2] : t.D2[3]);
+        L = t.D1[2] + eL;
+        R = t.D1[3] - eR;
+    } else {
+        const bool sT0 = t_abs(t.D3[0]) < t_abs(t.D3[1]), sT1 = t_abs(t.D3[1]) < t_abs(t.D3[2]);
+        const bool sT2 = t_abs(t.D3[2]) < t_abs(t.D3[3]);
+        const bool lRR = !sL0 && !sT1;
+        const T l2 = dx * (lRR ? t.D2[2] : t.D2[1]);
+        const T l3a = tdx2 * ((sL0 && sT0) ? t.D3[0] : t.D3[1]);
+        const T l3b = dx2 * t.D3[2];
+        const T lb = t.D1[2] + l2;
+        L = lRR ? (lb - l3b) : (lb + l3a);
+        const bool rRR = !sL1 && !sT2;
+        const T r2 = dx * (rRR ? t.D2[3] : t.D2[2]);
+        const T r3a = dx2 * ((sL1 && sT1) ? t.D3[1] : t.D3[2]);
+        const T r3b = tdx2 * t.D3[3];
+        const T rb = t.D1[3] - r2;
+        R = rRR ? (rb + r3b) : (rb - r3a);
+    }
+}
+
+// derivL / derivR of the 5-D / 6-D libraries (hidim_upwind_kernel, and the point kernels of hj_hiquery.hip that must give its bits):
+// the exact form for ENO2 / ENO3, upwind<> for the as-shipped WENO5
+template <int SCHEME, typename T>
+__device__ __forceinline__ void upwind_lr_hidim(const T* v, const T* K, T& L, T& R) {
+    if constexpr (np_order(SCHEME)) upwind_lr_exact<SCHEME, T>(v, K, L, R);
+    else upwind<SCHEME, T>(v, K, T(0), L, R);
+}
+
 // Centred costate pc = (L+R)/2 and half jump hd = (R-L)/2: all the Lax-Friedrichs term needs
 // (term_lax_friedrich.py:108, artificial_diss_glf.py:91,100).  The as-shipped WENO5 is linear in
 // phi, so both are short fixed stencils on the undivided differences u_j = v[j+1]-v[j]:

@@ -211,39 +211,7 @@ __global__ __launch_bounds__(256) void hidim_substep_kernel(const SubstepArgs<T,
     A.dst[t] = o;
 }
 
-// ENO2 / ENO3 one-sided derivatives with every operation rounded on its own: upwind_cd's exact branch (hj_device.h) stops at the centred
-// costate and the half jump, and L, R cannot be had back from those without a rounding.  Same tables (dd_tables), same selectors, same
-// order of operations; what the substep kernel differentiates is what this returns.
-template <int SCHEME, typename T>
-__device__ __forceinline__ void upwind_lr_exact(const T* v, const T* K, T& L, T& R) {
-#pragma clang fp contract(off)
-    DD<T> t;
-    dd_tables(v, K, t);
-    const T dx = K[3], dx2 = K[4], tdx2 = K[5];
-    const bool sL0 = t_abs(t.D2[1]) < t_abs(t.D2[2]), sL1 = t_abs(t.D2[2]) < t_abs(t.D2[3]);
-    if constexpr (SCHEME == HJ_ENO2) {
-        const T eL = dx * (sL0 ? t.D2[1] : t.D2[2]);
-        const T eR = dx * (sL1 ? t.D2[2] : t.D2[3]);
-        L = t.D1[2] + eL;
-        R = t.D1[3] - eR;
-    } else {
-        const bool sT0 = t_abs(t.D3[0]) < t_abs(t.D3[1]), sT1 = t_abs(t.D3[1]) < t_abs(t.D3[2]);
-        const bool sT2 = t_abs(t.D3[2]) < t_abs(t.D3[3]);
-        const bool lRR = !sL0 && !sT1;
-        const T l2 = dx * (lRR ? t.D2[2] : t.D2[1]);
-        const T l3a = tdx2 * ((sL0 && sT0) ? t.D3[0] : t.D3[1]);
-        const T l3b = dx2 * t.D3[2];
-        const T lb = t.D1[2] + l2;
-        L = lRR ? (lb - l3b) : (lb + l3a);
-        const bool rRR = !sL1 && !sT2;
-        const T r2 = dx * (rRR ? t.D2[3] : t.D2[2]);
-        const T r3a = dx2 * ((sL1 && sT1) ? t.D3[1] : t.D3[2]);
-        const T r3b = tdx2 * t.D3[3];
-        const T rb = t.D1[3] - r2;
-        R = rRR ? (rb + r3b) : (rb - r3a);
-    }
-}
-
+// (the one-sided derivatives of hidim_upwind_kernel: hj_device.h's upwind_lr_hidim -- the exact form for ENO2 / ENO3 -- shared with hj_hiquery.hip)
 template <typename T, int ND> struct UpwindArgs {
     GridArgs<T, ND> G;
     const T* src;
@@ -273,8 +241,7 @@ __global__ __launch_bounds__(256) void hidim_upwind_kernel(const UpwindArgs<T, N
         double m[4] = {-1e300, -1e300, -1e300, -1e300};
         if (live) {
             T L, R;
-            if constexpr (np_order(SCHEME)) upwind_lr_exact<SCHEME, T>(v[d], A.G.K[d], L, R);
-            else upwind<SCHEME, T>(v[d], A.G.K[d], T(0), L, R);
+            upwind_lr_hidim<SCHEME, T>(v[d], A.G.K[d], L, R);
             A.dL[d][t] = L;
             A.dR[d][t] = R;
             m[0] = -(double)L; m[1] = (double)L; m[2] = -(double)R; m[3] = (double)R;

@@ -120,37 +120,7 @@ __global__ __launch_bounds__(256) void costate_points_kernel(const T* __restrict
     }
 }
 
-// ---- (c) min / max over a subset of axes
-struct ProjArgs {
-    int nkeep, nrem;
-    int keep_n[MAXD], rem_n[MAXD];                  // sizes, in axis order (removed axes right-aligned, see the kernel)
-    long long keep_s[MAXD], rem_s[MAXD];            // strides in the input
-    long long nout;                                 // product of keep_n
-    long long field_stride, nfields;
-    int op;
-};
-
-// running min / max that remembers a NaN (np.amin / np.amax: any NaN in the set gives NaN)
-template <typename T> struct Red {
-    T v;
-    int nan;
-    __device__ __forceinline__ void take(T x, int op) {
-        if (x != x) nan = 1;
-        else if (op == HJQ_MIN ? x < v : x > v) v = x;
-    }
-};
-
-template <typename T>
-__device__ __forceinline__ long long proj_base(const ProjArgs& A, long long o) {
-    long long base = 0;
-    for (int k = A.nkeep - 1; k >= 0; --k) {
-        const long long q = o / A.keep_n[k];
-        base += (o - q * A.keep_n[k]) * A.keep_s[k];
-        o = q;
-    }
-    return base;
-}
-
+// ---- (c) min / max over a subset of axes (ProjArgs, Red, proj_base: hj_query_dev.h)
 // WAVE = false: the last axis is kept -- one thread per output node, neighbouring threads read neighbouring elements.
 // WAVE = true:  the last axis is removed -- one wavefront per output node; its lanes stride the last axis (neighbouring
 //               lanes read neighbouring elements) inside loops over the other removed axes.
@@ -185,21 +155,7 @@ __global__ __launch_bounds__(256) void project_minmax_kernel(const T* __restrict
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static int check_points(const hjq_grid* g, const QGrid& G, long long total, const void* data, int64_t nfields, int64_t field_stride,
-                 const double* xs, int64_t nstates, bool costate) {
-    if (!data || !xs) return fail(HJ_EINVAL, "null argument");
-    if (nfields < 1 || nstates < 1) return fail(HJ_EINVAL, "nfields and nstates must be positive");
-    if (nfields > 1 && field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
-    for (int d = 0; d < G.ndim; ++d) {
-        // an extrapolated axis interpolates between nodes i and i+1 <= N-1; the stencils reach HJ_STENCIL nodes (hj_upwind's limit)
-        const int need = costate ? HJ_STENCIL : (G.per[d] ? 1 : 2);
-        if (G.n[d] < need) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], need);
-    }
-    return HJ_OK;
-}
-
-static const char TOO_MANY[] = "too many (field, state) pairs for one launch";
-
+// (check_points, TOO_MANY: hj_query_dev.h)
 template <typename T>
 static int interp_launch(const QGrid& G, const void* data, int64_t nfields, int64_t field_stride, const double* xs, int64_t M,
                   void* out, int out_f64, hipStream_t stream, const char* name) {

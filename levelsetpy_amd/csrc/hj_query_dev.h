@@ -1,5 +1,5 @@
 // Device code shared by the point kernels of libhj_query.so (hj_query.hip), libhj_rollout.so (hj_rollout.hip) and
-// libhj_decomp.so (hj_decomp.hip): the grid as a
+// libhj_decomp.so (hj_decomp.hip), and at six axes by those of libhj_hiquery.so (hj_hiquery.hip): the grid as a
 // kernel sees it, the cell search, the corner weights, the stencil gather and the ordered sum over a state's corner lanes.
 // One source, so a value or a costate interpolated inside a rollout has the bits interp_points_kernel and
 // costate_points_kernel give for the same state.  At the end, the host function that fills the grid from the descriptor.
@@ -12,7 +12,16 @@
 
 namespace hjq {
 
-constexpr int MAXD = HJ_MAX_DIM;
+// The axes the structs below have room for, and the dimensions make_grid accepts.  hj_hiquery.hip defines both before it includes
+// this header (6, and 5..6); every other library compiles the defaults.
+#ifndef HJ_QUERY_MAXD
+#define HJ_QUERY_MAXD HJ_MAX_DIM
+#endif
+#ifndef HJ_QUERY_MIND
+#define HJ_QUERY_MIND 1
+#endif
+constexpr int MAXD = HJ_QUERY_MAXD;
+constexpr int MIND = HJ_QUERY_MIND;
 
 // grid as the kernels see it (kernel argument: lives in SGPRs)
 struct QGrid {
@@ -156,6 +165,38 @@ __device__ __forceinline__ double group_sum(double term, int used, int lanes) {
     return v;
 }
 
+// ---- min / max over a subset of axes: the arguments, the reduction and the decode of project_minmax_kernel (hj_query.hip) and
+// hi_project_minmax_kernel (hj_hiquery.hip)
+struct ProjArgs {
+    int nkeep, nrem;
+    int keep_n[MAXD], rem_n[MAXD];                  // sizes, in axis order (removed axes right-aligned, see the kernel)
+    long long keep_s[MAXD], rem_s[MAXD];            // strides in the input
+    long long nout;                                 // product of keep_n
+    long long field_stride, nfields;
+    int op;
+};
+
+// running min / max that remembers a NaN (np.amin / np.amax: any NaN in the set gives NaN)
+template <typename T> struct Red {
+    T v;
+    int nan;
+    __device__ __forceinline__ void take(T x, int op) {
+        if (x != x) nan = 1;
+        else if (op == HJQ_MIN ? x < v : x > v) v = x;
+    }
+};
+
+template <typename T>
+__device__ __forceinline__ long long proj_base(const ProjArgs& A, long long o) {
+    long long base = 0;
+    for (int k = A.nkeep - 1; k >= 0; --k) {
+        const long long q = o / A.keep_n[k];
+        base += (o - q * A.keep_n[k]) * A.keep_s[k];
+        o = q;
+    }
+    return base;
+}
+
 // ---------------------------------------------------------------------------------------------- host side
 // The descriptor as the kernels see it, with the checks both libraries make on it; total = the number of nodes.  Refusals go to
 // the including library's own error record: hj_tool_host.h comes before this header.
@@ -164,9 +205,11 @@ __device__ __forceinline__ double group_sum(double term, int used, int lanes) {
 #endif
 using hj_tool::fail;
 
-static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
+// GD: hjq_grid, or hjh_grid (include/hj_hidim.h) where MAXD is 6 -- the same fields with room for six axes.
+template <typename GD>
+static int make_grid(const GD* g, QGrid& G, long long& total) {
     if (!g) return fail(HJ_EINVAL, "null grid descriptor");
-    if (g->ndim < 1 || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside 1..%d", (int)g->ndim, MAXD);
+    if (g->ndim < MIND || g->ndim > MAXD) return fail(HJ_EINVAL, "ndim %d outside %d..%d", (int)g->ndim, MIND, MAXD);
     if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
     G.ndim = g->ndim;
     total = 1;
@@ -188,6 +231,23 @@ static int make_grid(const hjq_grid* g, QGrid& G, long long& total) {
     }
     return HJ_OK;
 }
+
+// the checks of the point entry points on their arrays
+template <typename GD>
+static int check_points(const GD* g, const QGrid& G, long long total, const void* data, int64_t nfields, int64_t field_stride,
+                 const double* xs, int64_t nstates, bool costate) {
+    if (!data || !xs) return fail(HJ_EINVAL, "null argument");
+    if (nfields < 1 || nstates < 1) return fail(HJ_EINVAL, "nfields and nstates must be positive");
+    if (nfields > 1 && field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    for (int d = 0; d < G.ndim; ++d) {
+        // an extrapolated axis interpolates between nodes i and i+1 <= N-1; the stencils reach HJ_STENCIL nodes (hj_upwind's limit)
+        const int need = costate ? HJ_STENCIL : (G.per[d] ? 1 : 2);
+        if (G.n[d] < need) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], need);
+    }
+    return HJ_OK;
+}
+
+static const char TOO_MANY[] = "too many (field, state) pairs for one launch";
 
 }  // namespace hjq
 #endif

@@ -1,0 +1,194 @@
+// Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip) and libhj_hiquery.so (hj_hiquery.hip): what does
+// not depend on the plant -- sgn, the RK4 step, and a trajectory from its first state to its last (the bisection over the stored
+// sets, the costate, the sub-steps).  One source, so a 5-D / 6-D trajectory is stepped by the statements a 2-D .. 4-D one is.
+// A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).
+// Include after hj_query_dev.h.
+#ifndef HJ_ROLLOUT_DEV_H
+#define HJ_ROLLOUT_DEV_H
+#include "hj_query_dev.h"
+#include "../../include/hj_rollout.h"
+
+namespace hjr {
+
+using hjq::MAXD;
+using hjq::QGrid;
+using hjq::QStencil;
+
+// +1 for s >= 0, -1 for s < 0, NaN for NaN: an exact zero is deterministic, a NaN costate poisons the state
+__device__ __forceinline__ double sgn(double s) { return s >= 0.0 ? 1.0 : (s < 0.0 ? -1.0 : __builtin_nan("")); }
+
+// ---- the plants: controls(costate p, state x) -> (c0, c1), f(x; c0, c1) -> xdot.  One operation per statement.
+template <int ID> struct Plant;
+
+// one classical RK4 step with the controls held, in the expression order of the Python systems' update_state
+template <typename PL>
+__device__ __forceinline__ void rk4(const hjr_plant& P, double* x, double dt, double c0, double c1) {
+#pragma clang fp contract(off)
+    constexpr int N = PL::ND;
+    double k1[N], k2[N], k3[N], k4[N], xa[N];
+    const double h = 0.5 * dt;
+    PL::f(P, x, c0, c1, k1);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = h * k1[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k2);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = h * k2[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k3);
+#pragma unroll
+    for (int d = 0; d < N; ++d) { const double t = dt * k3[d]; xa[d] = x[d] + t; }
+    PL::f(P, xa, c0, c1, k4);
+    const double sixth = dt / 6.0;
+#pragma unroll
+    for (int d = 0; d < N; ++d) {
+        const double a = 2.0 * k2[d];
+        double s = k1[d] + a;
+        const double b = 2.0 * k3[d];
+        s = s + b;
+        s = s + k4[d];
+        s = sixth * s;
+        x[d] = x[d] + s;
+    }
+}
+
+struct RolloutOut {
+    double* traj;
+    int* length;
+    int* t_earliest;
+    int* status;
+};
+
+// The one-sided derivatives of a corner's stencil.  UpwindSolver: hj_device.h's upwind<>, what computeGradients runs up to 4-D;
+// hj_hiquery.hip has the 5-D / 6-D one.
+struct UpwindSolver {
+    template <int SCHEME, typename T>
+    __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind<SCHEME, T>(v, K, T(0), L, R); }
+};
+
+// The body of a rollout kernel: the thread's trajectory (2^ND lanes per trajectory, this thread one corner of its cell).
+// Control flow is uniform inside a group and predicated across groups: see hj_rollout.hip.
+template <typename T, int SCHEME, typename PL, typename UP>
+__device__ __forceinline__ void rollout_body(const T* __restrict__ data, long long field_stride, int ntimes,
+                                             const double* __restrict__ x0, long long M, const QGrid& G, const QStencil<T>& S,
+                                             int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O) {
+    constexpr int ND = PL::ND;                     // == G.ndim (checked by the host)
+    constexpr int lanes = 1 << ND;                 // 4 .. 64: divides the wavefront, groups never straddle one
+    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    const long long m = t / lanes;
+    const int c = (int)(t - m * lanes);
+    if (m >= M) return;                            // whole groups leave together
+    const double nan = __builtin_nan("");
+    const double small = 1e-4;
+    double x[MAXD];
+#pragma unroll
+    for (int d = 0; d < MAXD; ++d) x[d] = d < ND ? x0[m * ND + d] : 0.0;
+
+    // where the state is: the cell, this lane's corner of it and the corner's weight
+    int lo[MAXD];
+    double w[MAXD];
+    bool inside;
+    long long off;
+    double wt;
+    int used;
+    auto find = [&]() {
+        inside = hjq::locate(G, x, lo, w);
+        wt = hjq::corner(G, lo, w, c, off);
+        used = wt != 0.0;
+    };
+    // V[f](x) in fp64: costate_points_kernel's `value`, the bits of interp_points_kernel
+    auto value_at = [&](int f) -> double {
+        T raw = T(0);
+        if (inside && used) raw = data[(long long)f * field_stride + off];
+        double p;
+        {
+#pragma clang fp contract(off)
+            p = wt * (double)raw;
+        }
+        const double v = hjq::group_sum(p, used, lanes);
+        return inside ? v : nan;
+    };
+    // grad V[f](x) in fp64: costate_points_kernel's `costate`
+    auto costate_at = [&](int f, double* p) {
+        T cC[ND];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) cC[d] = T(0);
+        if (inside && used) {
+            const T* pc0 = data + (long long)f * field_stride + off;
+            const T raw = *pc0;
+            if (!hjq::finite(raw)) {
+                // the node's own NaN / inf is put back after the differences (computeGradients: NaN stays NaN, +-inf becomes +inf)
+                const T back = raw != raw ? raw : T(__builtin_inf());
+#pragma unroll
+                for (int d = 0; d < ND; ++d) cC[d] = back;
+            } else {
+#pragma unroll
+                for (int d = 0; d < ND; ++d) {
+                    int j = lo[d] + ((c >> d) & 1);
+                    if (G.per[d] && j >= G.n[d]) j -= G.n[d];
+                    T v[7];
+                    hjq::gather_axis<T>(pc0, G.stride[d], j, G.n[d], G.per[d] != 0, S.km[d], raw, v);
+                    T L, R;
+                    UP::template lr<SCHEME, T>(v, S.K[d], L, R);
+                    cC[d] = T(0.5) * (L + R);
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < ND; ++d) {
+            double q;
+            {
+#pragma clang fp contract(off)
+                q = wt * (double)cC[d];
+            }
+            const double sC = hjq::group_sum(q, used, lanes);
+            p[d] = inside ? sC : nan;
+        }
+    };
+
+    double* __restrict__ row = O.traj + m * ND * (long long)ntimes;         // traj[m][d][col] = row[d * ntimes + col]
+    int* __restrict__ te_row = O.t_earliest ? O.t_earliest + m * (long long)ntimes : nullptr;
+    find();
+    if (c == 0) {
+#pragma unroll
+        for (int d = 0; d < ND; ++d) row[d * (long long)ntimes] = x[d];
+    }
+    int tE = 0, len = 1;
+    bool done = false, reached = false, left = !inside;
+    for (int it = 0; it < ntimes - 1; ++it) {
+        // the largest index of [tE, ntimes-1] whose set holds x: only the visited slices are interpolated
+        const bool active = !done;
+        int lower = tE, upper = active ? ntimes - 1 : tE;
+        while (upper > lower) {
+            const int mid = (upper + lower + 1) / 2;
+            if (value_at(mid) < small) lower = mid;
+            else upper = mid - 1;
+        }
+        if (active) {
+            tE = upper;
+            if (tE == ntimes - 1) done = reached = true;
+        }
+        if (te_row && c == 0) te_row[it] = active ? tE : -1;
+        if (!done) {
+            for (int s = 0; s < sub_samples; ++s) {
+                double p[ND], c0, c1;
+                costate_at(tE, p);
+                PL::controls(P, p, x, c0, c1);
+                rk4<PL>(P, x, dt_small, c0, c1);
+                find();
+            }
+            len = it + 2;
+            left = left || !inside;
+        }
+        if (c == 0) {
+#pragma unroll
+            for (int d = 0; d < ND; ++d) row[d * (long long)ntimes + it + 1] = done ? nan : x[d];
+        }
+    }
+    if (c == 0) {
+        if (te_row) te_row[ntimes - 1] = -1;
+        O.length[m] = len;
+        O.status[m] = left ? HJR_LEFT_GRID : (reached ? HJR_REACHED : HJR_EXHAUSTED);
+    }
+}
+
+}  // namespace hjr
+#endif

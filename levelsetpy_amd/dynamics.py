@@ -19,7 +19,8 @@ import numpy as np
 from . import _ffi, _hffi
 from .context import is_tensor
 
-__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "Plane5D", "DubinsPair6D", "native_of", "native_again", "native_plant"]
+__all__ = ["DubinsVehicleRel", "DoubleIntegrator", "DoublePendulum4D", "Plane5D", "DubinsPair6D", "native_of", "native_again", "native_plant",
+           "native_plant_hi"]
 
 
 def native_again(system):
@@ -462,3 +463,19 @@ def native_plant(dynSys):
         if getattr(type(dynSys), name, None) is not getattr(owner, name) or name in getattr(dynSys, "__dict__", {}):
             return None
     return dynSys.native()
+
+
+def native_plant_hi(dynSys):
+    """native_plant for the 5-D / 6-D systems and hi_rollout_kernel (libhj_hiquery.so): (plant id, the four parameters of
+    include/hj_hiquery.h's table) under the same identity rule, else None.  Plane5D's sign slot is not a plant parameter: the
+    rollout takes uMode from its caller, as get_opt_u does."""
+    owner = next((k for k in (Plane5D, DubinsPair6D) if isinstance(dynSys, k)), None)
+    if owner is None or getattr(dynSys, "_hj_native", None) is not None:
+        return None
+    for name in _PROTOCOL:
+        if getattr(type(dynSys), name, None) is not getattr(owner, name) or name in getattr(dynSys, "__dict__", {}):
+            return None
+    nat = dynSys.native()
+    if nat is None:
+        return None
+    return nat[0], (nat[1][:2] + [0.0, 0.0] if owner is Plane5D else list(nat[1]))

@@ -82,7 +82,7 @@ def _eval_point(g, data, x):
     x = np.asarray(x, dtype=np.float64).ravel()
     if x.size != g.dim:
         error('stopInit must be a vector of length g.dim!')
-    if is_tensor(data) and data.is_cuda and g.dim <= 4 and tuple(data.shape) == tuple(int(n) for n in np.asarray(g.N).ravel()):
+    if is_tensor(data) and data.is_cuda and g.dim <= 6 and tuple(data.shape) == tuple(int(n) for n in np.asarray(g.N).ravel()):
         from .query import interp_states
         from ._marshal import device_data as _device_data, device_states as _device_states
         t = _device_data(data)

@@ -4,7 +4,9 @@ HJIPDE_solve: V(x) and grad V(x) at many states, projections and slices.
 
 All of it runs in libhj_query.so (include/hj_query.h): `interp_points_kernel` (V at states),
 `costate_points_kernel` (grad V at states from the solver's own upwind source, without full-grid derivative
-arrays) and `project_minmax_kernel`.  NumPy in -> NumPy out (fp64); a device tensor or HostView in -> a tensor
+arrays) and `project_minmax_kernel`.  On 5-D and 6-D grids the same calls run in libhj_hiquery.so
+(include/hj_hiquery.h: `hi_interp_points_kernel`, `hi_costate_points_kernel`, `hi_project_minmax_kernel`), which compiles
+the same device functions at six axes; grids of seven and more axes are refused.  NumPy in -> NumPy out (fp64); a device tensor or HostView in -> a tensor
 on the same device, in the data's dtype.  Stored value functions with a time axis are time FIRST, as
 everywhere in this package.
 
@@ -19,38 +21,55 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, _qffi
+from . import _ffi, _qffi, _xffi
 from .context import grid_bc, is_tensor, require_gpu, _raw_stream_getter
 from .lazy import HostView, DeviceArray
 from .utilities import Bundle, error, warn
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, from_numpy as _from_numpy,      # noqa: F401
                        device_data as _device_data, device_states as _device_states, stream as _stream, ptr as _ptr,
-                       fields as _fields, descriptor as _descriptor, dtype_name as _dtype_name)
+                       fields as _fields, descriptor as _descriptor, dtype_name as _dtype_name, descriptor_hi as _descriptor_hi,
+                       is_hi as _is_hi)
 
 __all__ = ["eval_u", "eval_costate", "proj", "augmentPeriodicData"]
 
 
 # ------------------------------------------------------------------------------------------ marshalling
+def _library(g, dtype_name):
+    """(binding, function prefix, descriptor, shape) of the library that serves grid g: libhj_query.so up to 4-D, libhj_hiquery.so
+    (the same entry points on hjh_grid) at 5-D and 6-D."""
+    if _is_hi(g):
+        desc, N = _descriptor_hi(g, dtype_name)
+        return _xffi, "hjx_", desc, N
+    desc, N = _descriptor(g, dtype_name)
+    return _qffi, "hjq_", desc, N
+
+
+def last_kernel(g):
+    """The kernel the calling thread's last query on a grid of g's dimension launched."""
+    return (_xffi if _is_hi(g) else _qffi).last_kernel()
+
+
 def interp_states(g, data, xs, out_f64=False):
     """V at states for one array or a stack on grid g: device tensors in, a (F, M) tensor out (F = 1 for one array).
     `xs` is an (M, dim) fp64 device tensor.  out_f64: the unrounded fp64 sum whatever the data's dtype."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    ffi, pre, desc, N = _library(g, _dtype_name(data))
     F, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
         error('states must be an (M, %d) array' % g.dim)
     M = int(xs.shape[0])
     out = torch.empty((F, M), dtype=torch.float64 if out_f64 else data.dtype, device=data.device)
     with torch.cuda.device(data.device):
-        _qffi.check(_qffi.lib().hjq_interp_points(C.byref(desc), _ptr(data), F, stride, _ptr(xs), M, _ptr(out),
-                                                  int(bool(out_f64)), _stream(torch, data.device)))
+        ffi.check(getattr(ffi.lib(), pre + "interp_points")(C.byref(desc), _ptr(data), F, stride, _ptr(xs), M, _ptr(out),
+                                                            int(bool(out_f64)), _stream(torch, data.device)))
     return out
 
 
 def costate_states(g, data, xs, scheme, out_f64=False, want_lr=False, want_value=False):
-    """grad V at states: (F, M, dim) costates [, derivL, derivR (same shape), V (F, M)] from hjq_costate_points."""
+    """grad V at states: (F, M, dim) costates [, derivL, derivR (same shape), V (F, M)] from hjq_costate_points
+    (hjx_costate_points at 5-D / 6-D)."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    ffi, pre, desc, N = _library(g, _dtype_name(data))
     F, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim or xs.shape[0] < 1:
         error('states must be an (M, %d) array' % g.dim)
@@ -61,9 +80,9 @@ def costate_states(g, data, xs, scheme, out_f64=False, want_lr=False, want_value
     dl, dr = (mk(F, M, g.dim), mk(F, M, g.dim)) if want_lr else (None, None)
     val = mk(F, M) if want_value else None
     with torch.cuda.device(data.device):
-        _qffi.check(_qffi.lib().hjq_costate_points(C.byref(desc), int(scheme), _ptr(data), F, stride, _ptr(xs), M,
-                                                   _ptr(cs), _ptr(dl), _ptr(dr), _ptr(val), int(bool(out_f64)),
-                                                   _stream(torch, data.device)))
+        ffi.check(getattr(ffi.lib(), pre + "costate_points")(C.byref(desc), int(scheme), _ptr(data), F, stride, _ptr(xs), M,
+                                                             _ptr(cs), _ptr(dl), _ptr(dr), _ptr(val), int(bool(out_f64)),
+                                                             _stream(torch, data.device)))
     return cs, dl, dr, val
 
 
@@ -272,6 +291,52 @@ def _kept_grid(g, keep, N, process):
     return processGrid(gOut) if process else gOut
 
 
+# A projection kernel runs one thread (last axis kept) or one wavefront (last axis removed) per OUTPUT node.  On a 5-D / 6-D grid
+# the usual projections keep two axes of six -- 625 output nodes for 2.4e8 cells at 25^6 --, far too few to fill the device.  With
+# fewer output nodes than this, the leading removed axes are removed first, in a launch that still has this many output nodes and
+# reads the array once; the rest is removed from its result, which is smaller by those axes' extents.  min and max are exact and
+# a NaN survives both launches, so the result has the bits of the single launch.
+PROJ_STAGE_NODES = 1 << 16
+
+
+def _axes_bundle(g, keep):
+    """What the descriptors read of grid g (dim, N, dx, vs, bdry), for the axes `keep` alone."""
+    b = Bundle(dict(dim=len(keep), N=np.asarray(g.N).ravel()[keep].reshape(-1, 1), dx=np.asarray(g.dx).ravel()[keep].reshape(-1, 1),
+                    vs=[g.vs[i] for i in keep], bdry=[g.bdry[i] for i in keep]))
+    if hasattr(g, "bdryData") and g.bdryData is not None:
+        b.bdryData = [g.bdryData[i] for i in keep]
+    return b
+
+
+def _project_minmax(g, t, gone, op):
+    """min / max (op: _qffi.OP_*) of the contiguous (F,) + g.shape tensor t over the axes `gone` -> (F,) + kept shape."""
+    ffi, pre, desc, N = _library(g, _dtype_name(t))
+    F = int(t.shape[0])
+    keep = [i for i in range(g.dim) if i not in gone]
+    first = []
+    if _is_hi(g) and int(np.prod([N[i] for i in keep])) < PROJ_STAGE_NODES:
+        nodes = int(np.prod(N))
+        for i in gone[:-1]:                                   # ascending: the last removed axis stays for the second launch
+            if nodes // N[i] < PROJ_STAGE_NODES:
+                break
+            nodes //= N[i]
+            first.append(i)
+    if first:
+        rest = [i for i in range(g.dim) if i not in first]
+        part = _project_launch(ffi, pre, desc, N, t, F, first, op)
+        return _project_minmax(_axes_bundle(g, rest), part, [k for k, i in enumerate(rest) if i in gone], op)
+    return _project_launch(ffi, pre, desc, N, t, F, gone, op)
+
+
+def _project_launch(ffi, pre, desc, N, t, F, gone, op):
+    torch = require_gpu()
+    out = torch.empty((F,) + tuple(n for i, n in enumerate(N) if i not in gone), dtype=t.dtype, device=t.device)
+    with torch.cuda.device(t.device):
+        ffi.check(getattr(ffi.lib(), pre + "project_minmax")(C.byref(desc), _ptr(t), F, int(np.prod(N)), sum(1 << i for i in gone), op,
+                                                             _ptr(out), _stream(torch, t.device)))
+    return out
+
+
 def proj(g, data, dimsToRemove, xs=None, NOut=None, process=True):
     """data_proj.py:18: (gOut, dataOut) = the data on the grid of the axes NOT marked in dimsToRemove.
 
@@ -282,7 +347,8 @@ def proj(g, data, dimsToRemove, xs=None, NOut=None, process=True):
                                 resampled onto gOut's nodes through the interpolation kernel
 
     `data` may carry a time axis, time FIRST (the result is then (T,) + gOut.shape), or be a list of arrays.  gOut is
-    built as the reference builds it.  Keeping every dimension returns the inputs with a warning.  The shipped
+    built as the reference builds it.  Keeping every dimension returns the inputs with a warning.  On a 5-D / 6-D grid a
+    min / max that leaves fewer than PROJ_STAGE_NODES output nodes takes two launches (above), with the bits of one.  The shipped
     reference raises for every kind of projection: parity UNPINNED, checked against tests/query_ref.py."""
     rem = np.asarray(_unlazy(dimsToRemove) if not is_tensor(dimsToRemove) else dimsToRemove.cpu().numpy()).astype(bool).ravel()
     if rem.size != g.dim:
@@ -329,16 +395,11 @@ def proj(g, data, dimsToRemove, xs=None, NOut=None, process=True):
     gOut = _kept_grid(g, keep, Nout, process)
     torch = require_gpu()
     t = _device_data(data)
-    desc, N = _descriptor(g, _dtype_name(t))
-    F, stride = _fields(t, N)
+    N = _library(g, _dtype_name(t))[3]                   # (a grid no library serves is refused here, before any launch)
+    F = _fields(t, N)[0]
     resample = Nout != Nkeep
     if isinstance(xs, str):
-        out = torch.empty((F,) + tuple(Nkeep), dtype=t.dtype, device=t.device)
-        mask = sum(1 << i for i in gone)
-        with torch.cuda.device(t.device):
-            _qffi.check(_qffi.lib().hjq_project_minmax(C.byref(desc), _ptr(t), F, stride, mask,
-                                                       _qffi.OP_MIN if xs == 'min' else _qffi.OP_MAX, _ptr(out),
-                                                       _stream(torch, t.device)))
+        out = _project_minmax(g, t.reshape((F,) + tuple(N)), gone, _qffi.OP_MIN if xs == 'min' else _qffi.OP_MAX)
         if resample:
             gK = _kept_grid(g, keep, Nkeep, True)
             out = interp_states(gK, out, _device_states(_node_states(gK, gOut, range(len(keep)), [], []), t.device))

@@ -16,7 +16,9 @@ touched.
 With one of the built-in systems (dynamics.py) and upwindFirstENO2 / ENO3 / WENO5 (as shipped) the whole horizon of every
 trajectory -- the bisection over the stored sets, the costates, the controls, the RK4 sub-steps -- is ONE launch of
 rollout_kernel (libhj_rollout.so, include/hj_rollout.h), and the result equals computeOptTraj's with that system's own
-methods bit for bit up to the device's sin / cos.  Any other dynSys -- a foreign class, a subclass that overrides a
+methods bit for bit up to the device's sin / cos.  Plane5D and DubinsPair6D on a 5-D / 6-D grid take the same path in
+hi_rollout_kernel (libhj_hiquery.so, include/hj_hiquery.h), which compiles the trajectory's source at six axes; uMode and dMode
+are resolved as computeOptTraj resolves them.  Any other dynSys -- a foreign class, a subclass that overrides a
 protocol method, non-scalar bounds -- or derivative function takes a host loop: computeOptTraj on copy.copy(dynSys) once
 per state, padded the same way.
 
@@ -27,16 +29,16 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, _rffi
+from . import _ffi, _hffi, _rffi, _xffi
 from .context import grid_bc, is_tensor, require_gpu
-from .dynamics import native_plant
+from .dynamics import native_plant, native_plant_hi
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind
 from .query import point_scheme, states_2d
 from .spatial import upwindFirstWENO5
 from .utilities import Bundle, error, info, isfield
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, device_data as _device_data,
                        device_states as _device_states, stream as _stream, ptr as _ptr, fields as _fields,
-                       descriptor as _descriptor, dtype_name as _dtype_name)
+                       descriptor as _descriptor, dtype_name as _dtype_name, descriptor_hi as _descriptor_hi, is_hi as _is_hi)
 
 __all__ = ["computeOptTrajs", "REACHED", "EXHAUSTED", "LEFT_GRID"]
 
@@ -57,10 +59,10 @@ def _get(extraArgs, name, default):
 
 def _why_host(dynSys, derivFunc, g):
     """None when the kernel covers this call, else the reason for the host loop."""
-    nat = native_plant(dynSys)
+    nat = native_plant(dynSys) or native_plant_hi(dynSys)
     if nat is None:
         return None, "%s has no native plant" % type(dynSys).__name__
-    if _rffi.PLANT_DIMS.get(nat[0]) != g.dim:
+    if (_hffi.HAM_DIMS if nat[0] in _hffi.HAM_DIMS else _rffi.PLANT_DIMS).get(nat[0]) != g.dim:
         return None, "%s has no native plant on a %d-D grid" % (type(dynSys).__name__, g.dim)
     if point_scheme(derivFunc) is None:
         return None, "derivFunc %s has no point kernel" % getattr(derivFunc, "__name__", derivFunc)
@@ -71,7 +73,9 @@ def rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, want_te=Fals
     """hjr_rollout on device tensors: `data` a contiguous (T,) + g.shape stack, `xs` an (M, dim) fp64 tensor, `plant` an
     _rffi.Plant.  -> (traj (M, dim, T) fp64, length (M,) int32, tEarliest (M, T) int32 or None, status (M,) int32)."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    hi = _is_hi(g)                                   # 5-D / 6-D: hjx_rollout (libhj_hiquery.so), the same call on hjh_grid
+    desc, N = (_descriptor_hi if hi else _descriptor)(g, _dtype_name(data))
+    ffi, call = (_xffi, _xffi.lib().hjx_rollout) if hi else (_rffi, _rffi.lib().hjr_rollout)
     T, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim:
         error('states must be an (M, %d) array' % g.dim)
@@ -81,9 +85,9 @@ def rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, want_te=Fals
     status = torch.empty((M,), dtype=torch.int32, device=data.device)
     te = torch.empty((M, T), dtype=torch.int32, device=data.device) if want_te else None
     with torch.cuda.device(data.device):
-        _rffi.check(_rffi.lib().hjr_rollout(C.byref(desc), int(scheme), _ptr(data), T, stride, _ptr(xs), M, int(subSamples),
-                                            float(dtSmall), C.byref(plant), _ptr(traj), _ptr(length), _ptr(te), _ptr(status),
-                                            _stream(torch, data.device)))
+        ffi.check(call(C.byref(desc), int(scheme), _ptr(data), T, stride, _ptr(xs), M, int(subSamples),
+                       float(dtSmall), C.byref(plant), _ptr(traj), _ptr(length), _ptr(te), _ptr(status),
+                       _stream(torch, data.device)))
     return traj, length, te, status
 
 
@@ -151,7 +155,7 @@ def computeOptTrajs(g, data, tau, dynSys, x0s, extraArgs=None):
         plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
         dtSmall = (tau[1] - tau[0]) / subSamples                 # exactly as computeOptTraj forms it
         trajs, lengths, te, status = rollout_states(g, t, xs, point_scheme(derivFunc), subSamples, dtSmall, plant, want_te)
-        _last_path = _rffi.last_kernel()
+        _last_path = (_xffi if _is_hi(g) else _rffi).last_kernel()
         if not tensors:
             trajs, lengths, status = (a.cpu().numpy() for a in (trajs, lengths, status))
             te = te.cpu().numpy() if te is not None else None
