@@ -28,10 +28,17 @@
  *                             alpha = { |v_e cos x2|, |v_e sin x2|, w_e, |v_p cos x5|, |v_p sin x5|, w_p }
  *                             aux0 = cos(vs[2]), aux1 = sin(vs[2]), aux2 = cos(vs[5]), aux3 = sin(vs[5])
  * Sums run left to right.  With HJ_ENO2 / HJ_ENO3 every operation is rounded on its own, in that order.
+ *
+ * Any other system: hjh_ham_register (below) compiles the caller's H / alpha expression into these kernels at run time; its
+ * id (>= HJH_HAM_USER_BASE) is a `ham` like the two above.
  */
 #ifndef HJ_HIDIM_H
 #define HJ_HIDIM_H
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else                                  /* hipRTC (hjh_ham_register) has no system headers; hj_mi355x.h brings int64_t */
+typedef signed int int32_t;
+#endif
 #include "hj_mi355x.h"
 
 #ifdef __cplusplus
@@ -40,6 +47,7 @@ extern "C" {
 
 enum { HJH_MIN_DIM = 5, HJH_MAX_DIM = 6 };
 enum { HJH_HAM_PLANE5D = 50, HJH_HAM_DUBINS_PAIR6D = 51 };
+enum { HJH_HAM_USER_BASE = 1000 };     /* ids >= this: systems registered at run time (hjh_ham_register) */
 #define HJH_PAR_SLOTS 8
 
 /* hjq_grid (hj_query.h) with room for six axes */
@@ -57,7 +65,7 @@ typedef struct hjh_grid {
 /* 1-D tables of the grid's dtype */
 typedef struct hjh_tables {
     const void* coord[6];              /* grid.vs[d]: N[d] values */
-    const void* aux[4];                /* the cos / sin tables of `ham`, listed above */
+    const void* aux[4];                /* the cos / sin tables of `ham`, listed above; a registered system's own tables */
 } hjh_tables;
 
 /* post-step operators against arrays, numbered as hjb_entry's (hj_batch.h) */
@@ -96,6 +104,29 @@ int hjh_integrate(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham,
  * the substep's own one-sided derivatives, every operation rounded on its own.  Asynchronous on `stream`. */
 int hjh_upwind(const hjh_grid* g, int scheme, const void* src, unsigned axis_mask, void* const* derivL_host,
                void* const* derivR_host, void* keys, void* stream);
+
+/* ---- systems registered at run time.  `body` is a device expression (C++ statements) that assigns H and every alpha[d] from
+ *     x[d]    node coordinates, d = 0 .. ndim-1          p[d]    costates (the reference's derivC)
+ *     par[k]  the call's params_host, k < nparams        aux[k]  the value of the call's table tab->aux[k] (k < naux) at this cell's
+ *     T       the element type                                   index along axis aux_axes[k]: N[aux_axes[k]] values of the grid's dtype
+ * and device math functions.  It sees neither the time, the data nor the costate range (alpha must not depend on them: the step
+ * bound is a property of the grid).  hipRTC compiles hidim_substep_kernel / hidim_bound_kernel (csrc/hj_hidim_dev.h, found in
+ * include_dir) around it for gfx950, lazily at the first launch on each device, and keeps the code objects in the on-disk cache
+ * hj_mi355x.h describes.  With HJ_ENO2 / HJ_ENO3 the expression is compiled with contraction off: every operation is rounded on
+ * its own, as a NumPy callback written the same way rounds.  hjh_substep, hjh_step_bound and hjh_integrate take the id as `ham`;
+ * a null tab->aux[k], k < naux, is refused.  The same (name, ndim, nparams, body, axes) registered again gives the same id.
+ * hiprtc_path (may be null): the libhiprtc.so to load. */
+int hjh_ham_register(const char* name, int ndim, int nparams, const char* body, int naux, const int32_t* aux_axes,
+                     const char* include_dir, const char* hiprtc_path, int* ham_id);
+/* what was registered (any pointer may be null); aux_axes: 4 values, -1 past naux; kernels_built: on all devices */
+int hjh_ham_info(int ham_id, int* ndim, int* nparams, int* naux, int32_t* aux_axes, int* kernels_built);
+/* compile the substep kernel of (scheme, dtype) and the bound kernel now, without a launch (needs no GPU); HJ_EINVAL with the
+ * compiler's message, which names the registration and the line of `body` */
+int hjh_ham_compile_check(int ham_id, int scheme, int dtype);
+/* the generated translation unit, 0-terminated, for offline inspection (hipcc -I csrc -I include); n: the buffer's size */
+int hjh_ham_source(int ham_id, char* buf, int64_t n);
+/* kernels compiled with hipRTC / loaded from the disk cache by this library in this process */
+int hjh_ham_cache_stats(int* compiled, int* loaded_from_cache);
 
 const char* hjh_last_error(void);
 /* name of the kernel the calling thread's last successful launch ran, e.g.

@@ -42,5 +42,6 @@ from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCe
 from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
 from .eikonal import signedDistance, addCRadius                                  # noqa: F401
 from . import hidim                                                              # noqa: F401
+from .hidim_ham import register_hidim_hamiltonian, HidimRegistration, HidimSystem, hidim_kernel_cache_stats   # noqa: F401
 
 __version__ = "0.1.0"

@@ -14,6 +14,7 @@ ARR_NONE, ARR_MIN, ARR_MAX, ARR_MAX_NEG = 0, 1, 2, 3   # HJH_ARR_*
 SCHEMES = _qffi.POINT_SCHEMES                      # the schemes the kernels are instantiated for
 HAM_DIMS = {HAM_PLANE5D: 5, HAM_DUBINS_PAIR6D: 6}
 HAM_NAMES = {HAM_PLANE5D: "HamPlane5D", HAM_DUBINS_PAIR6D: "HamDubinsPair6D"}
+HAM_USER_BASE = 1000                               # HJH_HAM_USER_BASE: ids of systems registered at run time (hidim_ham.py)
 
 
 class Grid(C.Structure):
@@ -39,6 +40,11 @@ SIGNATURES = {
     "hjh_integrate": (_i, [_pg, _pt, _i, _i, _i, _i, _i, _pd, _d, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp, _d, _d, _d, _d, _d,
                            _pd, _pi64, _pi32, _vp]),
     "hjh_upwind": (_i, [_pg, _i, _vp, _u, _pvp, _pvp, _vp, _vp]),
+    "hjh_ham_register": (_i, [C.c_char_p, _i, _i, C.c_char_p, _i, _pi32, C.c_char_p, C.c_char_p, C.POINTER(C.c_int)]),
+    "hjh_ham_info": (_i, [_i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), _pi32, C.POINTER(C.c_int)]),
+    "hjh_ham_compile_check": (_i, [_i, _i, _i]),
+    "hjh_ham_source": (_i, [_i, C.c_char_p, _i64]),
+    "hjh_ham_cache_stats": (_i, [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hjh_last_error": (C.c_char_p, []),
     "hjh_last_kernel": (C.c_char_p, []),
 }
@@ -67,6 +73,22 @@ def params(values):
     return (C.c_double * PAR_SLOTS)(*(v + [0.0] * (PAR_SLOTS - len(v))))
 
 
+def ham_dim(ham):
+    """State dimension of a system id: a built-in's, or a registration's (hjh_ham_info); None for an id nothing answers to."""
+    ham = int(ham)
+    if ham < HAM_USER_BASE:
+        return HAM_DIMS.get(ham)
+    nd = C.c_int()
+    if lib().hjh_ham_info(ham, C.byref(nd), None, None, None, None) != 0:
+        return None
+    return int(nd.value)
+
+
 def kernel_name(dtype_name, ham, scheme):
     """What hjh_last_kernel() reads after a substep of this instantiation."""
-    return "hidim_substep_kernel<%s, %s, %d>" % ("double" if dtype_name == "float64" else "float", HAM_NAMES[ham], scheme)
+    if int(ham) >= HAM_USER_BASE:
+        from .hidim_ham import name_of
+        system = "HamUser:%s" % name_of(ham)
+    else:
+        system = HAM_NAMES[ham]
+    return "hidim_substep_kernel<%s, %s, %d>" % ("double" if dtype_name == "float64" else "float", system, scheme)

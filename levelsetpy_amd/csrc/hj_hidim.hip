@@ -6,26 +6,29 @@
 // The per-cell functions (decode, gather_stencils, upwind_cd, upwind, rk_stage_out, post_step) are the solver's own source (hj_device.h,
 // hj_split.h), instantiated at ND = 5 and 6 and compiled with the solver's flags.  HJ_MAX_DIM stays 4: HamTables cannot hold the coordinates
 // of axes 4 and 5, so the two systems here read a table struct of their own (HiTables), and the one solver function that takes a HamTables,
-// lf_ydot, has its dissipation sum restated below (hidim_ydot).  The library links nothing of libhj_mi355x.so.
+// lf_ydot, has its dissipation sum restated (hidim_ydot).  The library links nothing of libhj_mi355x.so.
+// The substep and bound kernels, HiTables, hidim_ydot, array_op and SubstepArgs live in hj_hidim_dev.h: this file instantiates them for the two
+// built-in systems, and hipRTC compiles them around an expression registered with hjh_ham_register (HamUser<T>, generated below; ids from
+// HJH_HAM_USER_BASE).  Such a kernel is built lazily at its first launch, per device, under the lock of hj_rtc_host.h, kept in the on-disk
+// code-object cache that libhj_mi355x.so's registrations use, and launched through the module API with the very SubstepArgs block the
+// built-in instantiations get: 256 threads, one thread per cell, 64-bit indexing.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <deque>
+#include <map>
+#include <sstream>
 #include <vector>
 #include "hj_tool_host.h"
-#include "hj_split.h"
-#include "../../include/hj_hidim.h"
+#include "hj_hidim_dev.h"
+#define HJ_RTC_FAIL ::hj_tool::fail
+#include "hj_rtc_host.h"
 
 namespace hjh {
 
 using namespace hj;
 using namespace hj_tool;
-
-template <typename T> struct HiTables {
-    const T* coord[HJH_MAX_DIM];       // grid.vs[d]
-    const T* aux[4];                   // cos / sin tables (include/hj_hidim.h)
-    T par[HJH_PAR_SLOTS];
-};
 
 // ---- the systems.  Interface and scaling as hj_device.h's: cell() folds the costate scales sc[d] into the cell's coefficients, eval() takes
 // the UNSCALED costates q (p_d = sc[d] q_d), returns H(x, p) and alpha_s[d] = sc[d] alpha_d.  NP (ENO2 / ENO3, sc = 1): the expression of
@@ -125,92 +128,6 @@ template <typename T> struct HamDubinsPair6D {
     }
 };
 
-// lf_ydot (hj_device.h) for a system that reads HiTables: ydot = -(H - sum_d hd_d alpha_d), the sum in axis order, NP as there
-template <bool NP, typename HAM, typename T>
-__device__ __forceinline__ T hidim_ydot(const typename HAM::Cell& c, const T* pc, const T* hd, T* alpha) {
-    T H;
-    HAM::template eval<NP>(c, pc, H, alpha);
-    if constexpr (NP) {
-#pragma clang fp contract(off)
-        T diss = T(0);
-#pragma unroll
-        for (int d = 0; d < HAM::ND; ++d) diss = diss + hd[d] * alpha[d];
-        return -(H - diss);
-    } else {
-        T diss = T(0);
-#pragma unroll
-        for (int d = 0; d < HAM::ND; ++d) diss += hd[d] * alpha[d];
-        return -(H - diss);
-    }
-}
-
-// min / max against an array: batch_substep_kernel's expression, NaN propagating as NumPy's minimum / maximum
-template <typename T>
-__device__ __forceinline__ T array_op(int op, T a, T b) {
-    T r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else if (op == HJH_ARR_MIN) r = a < b ? a : b;
-    else if (op == HJH_ARR_MAX) r = a > b ? a : b;
-    else r = a > -b ? a : -b;
-    return r;
-}
-
-template <typename T, int ND> struct SubstepArgs {
-    GridArgs<T, ND> G;
-    T sc[ND];                          // costate scale of the scheme (hj_device.h)
-    HiTables<T> P;
-    const T* src;
-    const T* y0;
-    T* dst;
-    const T* post_a;
-    const T* post_b;
-    T dt;
-    int stage, restrict_sign, post_prev, op_a, op_b;
-};
-
-template <typename T, typename HAM, int SCHEME>
-__global__ __launch_bounds__(256) void hidim_substep_kernel(const SubstepArgs<T, HAM::ND> A) {
-    constexpr int ND = HAM::ND;
-    constexpr bool NP = np_order(SCHEME);
-    static_assert(SCHEME != HJ_WENO5, "the intended WENO5 needs an epsilon reduction over the grid");
-    const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    if (t >= A.G.total) return;
-    const int stage = A.stage;
-    WenoK<T> wk;
-    wk.c13 = T(0); wk.c4 = T(0);
-    T ca = T(0), cb = T(1);
-    if (stage == HJ_STAGE_RK3_HALF) { ca = T(0.75); cb = T(0.25); }
-    else if (stage == HJ_STAGE_RK3_FULL) { ca = T(1.0 / 3.0); cb = T(2.0 / 3.0); }
-    else if (stage == HJ_STAGE_RK2_FULL) { ca = T(0.5); cb = T(0.5); }
-    const bool use_y0 = stage >= HJ_STAGE_RK3_HALF;
-    int idx[ND];
-    decode<T, ND>(A.G, t, idx);
-    const T* pc0 = A.src + t;
-    T v[ND][7];
-    const T centre = pc0[0];
-    const T y0v = use_y0 ? A.y0[t] : T(0);
-    const typename HAM::Cell hc = HAM::cell(A.P, idx, A.sc);
-    gather_stencils<T, ND>(A.G, pc0, idx, centre, v);
-    T pc[ND], hd[ND];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], T(0), wk, pc[d], hd[d]);
-    T alpha[ND];
-    T ydot = hidim_ydot<NP, HAM>(hc, pc, hd, alpha);
-    // termRestrictUpdate clamp, written like direct_substep_kernel's (a NaN stays a NaN)
-    if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
-    else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
-    T o;
-    if (stage == HJ_STAGE_YDOT) o = ydot;
-    else {
-        o = rk_stage_out<NP>(stage, ca, cb, A.dt, y0v, centre, ydot);
-        if (A.post_prev) o = post_step(A.post_prev, o, use_y0 ? y0v : centre);
-        if (A.op_a) o = array_op(A.op_a, o, A.post_a[t]);
-        if (A.op_b) o = array_op(A.op_b, o, A.post_b[t]);
-    }
-    A.dst[t] = o;
-}
-
 // (the one-sided derivatives of hidim_upwind_kernel: hj_device.h's upwind_lr_hidim -- the exact form for ENO2 / ENO3 -- shared with hj_hiquery.hip)
 template <typename T, int ND> struct UpwindArgs {
     GridArgs<T, ND> G;
@@ -263,40 +180,97 @@ __global__ __launch_bounds__(256) void hidim_upwind_kernel(const UpwindArgs<T, N
     }
 }
 
-// max over the grid of alpha_d at zero costate: batch_bound_kernel's evaluation (unit scales), one workgroup maximum per axis folded into
-// keys[d] (order-preserving keys, zero at launch)
-template <typename T, typename HAM>
-__global__ __launch_bounds__(256) void hidim_bound_kernel(const GridArgs<T, HAM::ND> G, const HiTables<T> P, unsigned long long* keys) {
-    constexpr int ND = HAM::ND;
-    double m[ND];
-    T one[ND], p[ND];
-#pragma unroll
-    for (int d = 0; d < ND; ++d) { m[d] = -1e300; one[d] = T(1); p[d] = T(0); }
-    for (long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x; t < G.total; t += (long long)gridDim.x * blockDim.x) {
-        int idx[ND];
-        decode<T, ND>(G, t, idx);
-        T H, a[ND];
-        HAM::template eval<false>(HAM::cell(P, idx, one), p, H, a);
-#pragma unroll
-        for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
-    }
-    __shared__ double red[4][ND];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const double w = wave_max(m[d]);
-        if (lane == 0) red[wv][d] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < ND) {
-        const int d = threadIdx.x;
-        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
-        if (w > -1e299) key_max(keys + d, w);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- host side
 static int hidim_ham_ndim(int ham) { return ham == HJH_HAM_PLANE5D ? 5 : (ham == HJH_HAM_DUBINS_PAIR6D ? 6 : 0); }
+
+// ---- systems registered at run time (hjh_ham_register).  They live in a deque (registration never moves an element another thread may be
+// launching); every look at it and at the kernel tables takes HJ_RTC_LOCK.
+struct HiKernel {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+};
+struct HiUserHam {
+    std::string name, body, include_dir, rtc_path;
+    int ndim = 0, nparams = 0, naux = 0;
+    int aux_axes[4] = {0, 0, 0, 0};
+    std::map<long long, HiKernel> substep;      // key: ((device * 2 + fp32) * 4 + scheme)
+    std::map<long long, HiKernel> bound;        // key: device * 2 + fp32
+};
+static std::deque<HiUserHam> g_user;
+
+static HiUserHam* user_of(int ham) {
+    const long long i = (long long)ham - HJH_HAM_USER_BASE;
+    return (i >= 0 && i < (long long)g_user.size()) ? &g_user[(size_t)i] : nullptr;
+}
+
+// The translation unit hipRTC compiles: the kernel header and the system type around the caller's expression.  cell() reads the node's
+// coordinates and the naux table values once; eval() forms p[d] = sc[d] q[d], runs the expression -- under contraction off where NP holds
+// (ENO2 / ENO3), so that a C++ expression written like a NumPy callback rounds every operation where NumPy does -- and scales alpha[d] by
+// sc[d].  Every array of Cell is indexed by constants once cell() and eval() are inlined and unrolled: the values stay in registers.
+static std::string user_source(const HiUserHam& u, int id) {
+    std::ostringstream o;
+    o << "#include \"hj_hidim_dev.h\"\nnamespace hjh {\n"
+         "template <typename T> struct HamUser {\n"
+         "    static constexpr int ND = " << u.ndim << ";\n"
+         "    static constexpr int ID = " << id << ";\n"
+         "    static constexpr int NAUX = " << u.naux << ";\n"
+         "    struct Cell { T x[ND]; T sc[ND]; T aux[NAUX > 0 ? NAUX : 1]; T par[HJH_PAR_SLOTS]; };\n"
+         "    __device__ static __forceinline__ Cell cell(const HiTables<T>& P, const int* idx, const T* sc) {\n"
+         "        Cell c;\n"
+         "#pragma unroll\n"
+         "        for (int d = 0; d < ND; ++d) { c.x[d] = P.coord[d][idx[d]]; c.sc[d] = sc[d]; }\n"
+         "        c.aux[0] = T(0);\n";
+    for (int k = 0; k < u.naux; ++k) o << "        c.aux[" << k << "] = P.aux[" << k << "][idx[" << u.aux_axes[k] << "]];\n";
+    o << "#pragma unroll\n"
+         "        for (int k = 0; k < HJH_PAR_SLOTS; ++k) c.par[k] = P.par[k];\n"
+         "        return c;\n    }\n"
+         "    template <bool NP>\n"
+         "    __device__ static __forceinline__ void eval(const Cell& c, const T* q, T& H, T* alpha) {\n"
+         "        T p[ND];\n"
+         "#pragma unroll\n"
+         "        for (int d = 0; d < ND; ++d) { p[d] = c.sc[d] * q[d]; alpha[d] = T(0); }\n"
+         "        const T* x = c.x;\n        const T* aux = c.aux;\n        const T* par = c.par;\n"
+         "        (void)x; (void)aux; (void)par;\n        H = T(0);\n"
+         "        if constexpr (NP) {\n"
+         "#pragma clang fp contract(off)\n"
+         "            {\n#line 1 \"" << u.name << "\"\n" << u.body << "\n            }\n"
+         "        } else {\n"
+         "            {\n#line 1 \"" << u.name << "\"\n" << u.body << "\n            }\n"
+         "        }\n"
+         "#pragma unroll\n"
+         "        for (int d = 0; d < ND; ++d) alpha[d] = c.sc[d] * alpha[d];     // the kernel carries alpha in the stencil's scale\n"
+         "    }\n};\n}\n";
+    return o.str();
+}
+
+// what the disk cache's key covers besides the generated source (hj_rtc_host.h)
+static const hj_rtc::Unit& hidim_unit() {
+    static const hj_rtc::Unit u = {{"/hj_hidim_dev.h", "/hj_split.h", "/hj_device.h", "/../../include/hj_hidim.h", "/../../include/hj_mi355x.h"},
+                                   {sizeof(SubstepArgs<double, 5>), sizeof(SubstepArgs<double, 6>), sizeof(SubstepArgs<float, 5>),
+                                    sizeof(SubstepArgs<float, 6>), sizeof(HiTables<double>), sizeof(HiTables<float>)}};
+    return u;
+}
+
+static std::string substep_expr(const char* tn, int scheme) {
+    return std::string("hjh::hidim_substep_kernel<") + tn + ", hjh::HamUser<" + tn + ">, " + std::to_string(scheme) + ">";
+}
+static std::string bound_expr(const char* tn) { return std::string("hjh::hidim_bound_kernel<") + tn + ", hjh::HamUser<" + tn + ">>"; }
+
+// the kernel of (system, current device, type[, scheme]): built at its first use.  Call with HJ_RTC_LOCK held.
+static int user_kernel(HiUserHam& u, int ham, bool f32, int scheme, bool bound, hipFunction_t& fn) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    const long long key = bound ? (long long)dev * 2 + (f32 ? 1 : 0) : (((long long)dev * 2 + (f32 ? 1 : 0)) * 4 + scheme);
+    HiKernel& k = (bound ? u.bound : u.substep)[key];
+    if (!k.fn) {
+        const char* tn = f32 ? "float" : "double";
+        int rc = hj_rtc::rtc_build(hidim_unit(), user_source(u, ham), bound ? bound_expr(tn) : substep_expr(tn, scheme), u.name, u.include_dir,
+                                   u.rtc_path, k.mod, k.fn);
+        if (rc) { k.mod = nullptr; k.fn = nullptr; return rc; }
+    }
+    fn = k.fn;
+    return HJ_OK;
+}
 
 static int check_grid(const hjh_grid* g, long long& total) {
     if (!g) return fail(HJ_EINVAL, "null grid descriptor");
@@ -320,12 +294,18 @@ static int check_setup(const hjh_grid* g, const hjh_tables* tab, int ham, const 
     int rc = check_grid(g, total);
     if (rc) return rc;
     if (!tab) return fail(HJ_EINVAL, "null tables");
-    const int nd = hidim_ham_ndim(ham);
+    int nd = hidim_ham_ndim(ham), naux = ham == HJH_HAM_PLANE5D ? 2 : 4;
+    if (ham >= HJH_HAM_USER_BASE) {
+        HJ_RTC_LOCK;
+        const HiUserHam* u = user_of(ham);
+        if (!u) return fail(HJ_EINVAL, "unknown Hamiltonian id %d: nothing is registered under it (hjh_ham_register)", ham);
+        nd = u->ndim;
+        naux = u->naux;
+    }
     if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no kernel here (HJH_HAM_PLANE5D, HJH_HAM_DUBINS_PAIR6D)", ham);
     if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
     for (int d = 0; d < nd; ++d)
         if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
-    const int naux = ham == HJH_HAM_PLANE5D ? 2 : 4;
     for (int s = 0; s < naux; ++s)
         if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
     if (!params_host) return fail(HJ_EINVAL, "null parameters");
@@ -374,25 +354,34 @@ struct Stage {
     const void* post_b;
 };
 
+// the argument block of one call's stages (every stage of a call shares it but for set_stage's fields), and its workgroup count
+template <typename T, int ND>
+static int fill_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int restrict_sign, const double* params_host, SubstepArgs<T, ND>& A,
+                        unsigned& bx) {
+    memset(&A, 0, sizeof(A));
+    fill_grid<T, ND>(g, A.G);
+    for (int d = 0; d < ND; ++d) A.sc[d] = scheme_scale<T>(scheme, g->dx[d]);
+    fill_tables<T>(tab, params_host, A.P);
+    A.restrict_sign = restrict_sign;
+    return blocks_for(A.G.total, "grid too large for one thread per cell", bx);
+}
+template <typename T, int ND> static void set_stage(const Stage& s, SubstepArgs<T, ND>& A) {
+    A.src = (const T*)s.src; A.y0 = (const T*)s.y0; A.dst = (T*)s.dst;
+    A.post_a = (const T*)s.post_a; A.post_b = (const T*)s.post_b;
+    A.dt = (T)s.dt;
+    A.stage = s.stage; A.post_prev = s.post_prev; A.op_a = s.op_a; A.op_b = s.op_b;
+}
+
 template <typename T, typename HAM, int SCHEME>
 static int launch_substep(const hjh_grid* g, const hjh_tables* tab, int restrict_sign, const double* params_host, const Stage* st, int nst,
                           hipStream_t stream, const char* name) {
     constexpr int ND = HAM::ND;
     SubstepArgs<T, ND> A;
-    memset(&A, 0, sizeof(A));
-    fill_grid<T, ND>(g, A.G);
-    for (int d = 0; d < ND; ++d) A.sc[d] = scheme_scale<T>(SCHEME, g->dx[d]);
-    fill_tables<T>(tab, params_host, A.P);
-    A.restrict_sign = restrict_sign;
     unsigned bx;
-    int rc = blocks_for(A.G.total, "grid too large for one thread per cell", bx);
+    int rc = fill_substep<T, ND>(g, tab, SCHEME, restrict_sign, params_host, A, bx);
     if (rc) return rc;
     for (int k = 0; k < nst; ++k) {
-        const Stage& s = st[k];
-        A.src = (const T*)s.src; A.y0 = (const T*)s.y0; A.dst = (T*)s.dst;
-        A.post_a = (const T*)s.post_a; A.post_b = (const T*)s.post_b;
-        A.dt = (T)s.dt;
-        A.stage = s.stage; A.post_prev = s.post_prev; A.op_a = s.op_a; A.op_b = s.op_b;
+        set_stage<T, ND>(st[k], A);
         hipLaunchKernelGGL((hidim_substep_kernel<T, HAM, SCHEME>), dim3(bx), dim3(256), 0, stream, A);
         HIP_TRY(hipGetLastError());
     }
@@ -400,8 +389,39 @@ static int launch_substep(const hjh_grid* g, const hjh_tables* tab, int restrict
     return HJ_OK;
 }
 
+// the same for a registered system: its kernel is built (or found in the disk cache) before the first launch, so a call that fails to
+// compile has launched nothing
+template <typename T, int ND>
+static int launch_user_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, int restrict_sign, const double* params_host,
+                               const Stage* st, int nst, hipStream_t stream) {
+    HJ_RTC_LOCK;
+    HiUserHam* u = user_of(ham);
+    if (!u || u->ndim != ND) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham);
+    SubstepArgs<T, ND> A;
+    unsigned bx;
+    int rc = fill_substep<T, ND>(g, tab, scheme, restrict_sign, params_host, A, bx);
+    if (rc) return rc;
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(*u, ham, sizeof(T) == 4, scheme, false, fn))) return rc;
+    for (int k = 0; k < nst; ++k) {
+        set_stage<T, ND>(st[k], A);
+        if ((rc = hj_rtc::module_launch(fn, bx, 256, 0, stream, &A, sizeof(A)))) return rc;
+    }
+    const std::string name = std::string("hidim_substep_kernel<") + (sizeof(T) == 4 ? "float" : "double") + ", HamUser:" + u->name + ", " +
+                             std::to_string(scheme) + ">";
+    launched(name.c_str());
+    return HJ_OK;
+}
+
 static int dispatch_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, int restrict_sign, const double* params_host,
                             const Stage* st, int nst, hipStream_t stream) {
+    if (ham >= HJH_HAM_USER_BASE) {
+        if (g->dtype == HJ_F64)
+            return g->ndim == 5 ? launch_user_substep<double, 5>(g, tab, scheme, ham, restrict_sign, params_host, st, nst, stream)
+                                : launch_user_substep<double, 6>(g, tab, scheme, ham, restrict_sign, params_host, st, nst, stream);
+        return g->ndim == 5 ? launch_user_substep<float, 5>(g, tab, scheme, ham, restrict_sign, params_host, st, nst, stream)
+                            : launch_user_substep<float, 6>(g, tab, scheme, ham, restrict_sign, params_host, st, nst, stream);
+    }
 #define HJH_GO(T, HAM, SCH) \
     return launch_substep<T, HAM<T>, SCH>(g, tab, restrict_sign, params_host, st, nst, stream, "hidim_substep_kernel<" #T ", " #HAM ", " #SCH ">")
 #define HJH_HAMS(T, SCH)                                              \
@@ -441,6 +461,53 @@ static int launch_upwind(const hjh_grid* g, const void* src, unsigned mask, void
     return launch_done(name);
 }
 
+// hidim_bound_kernel's argument block as the module API takes it
+template <typename T, int ND> struct BoundKernArgs {
+    GridArgs<T, ND> G;
+    HiTables<T> P;
+    unsigned long long* keys;
+};
+template <typename T, int ND>
+static int launch_user_bound(const hjh_grid* g, const hjh_tables* tab, int ham, const double* params_host, unsigned long long* keys, unsigned bx,
+                             hipStream_t stream) {
+    HJ_RTC_LOCK;
+    HiUserHam* u = user_of(ham);
+    if (!u || u->ndim != ND) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham);
+    hipFunction_t fn = nullptr;
+    int rc = user_kernel(*u, ham, sizeof(T) == 4, 0, true, fn);
+    if (rc) return rc;
+    BoundKernArgs<T, ND> K;
+    memset(&K, 0, sizeof(K));
+    fill_grid<T, ND>(g, K.G);
+    fill_tables<T>(tab, params_host, K.P);
+    K.keys = keys;
+    HIP_TRY(hipMemsetAsync(keys, 0, sizeof(unsigned long long) * HJH_MAX_DIM, stream));
+    if ((rc = hj_rtc::module_launch(fn, bx, 256, 0, stream, &K, sizeof(K)))) return rc;
+    const std::string name = std::string("hidim_bound_kernel<") + (sizeof(T) == 4 ? "float" : "double") + ", HamUser:" + u->name + ">";
+    launched(name.c_str());
+    return HJ_OK;
+}
+
+static int launch_builtin_bound(const hjh_grid* g, const hjh_tables* tab, int ham, const double* params_host, unsigned long long* k, unsigned bx,
+                                hipStream_t s) {
+    HIP_TRY(hipMemsetAsync(k, 0, sizeof(unsigned long long) * HJH_MAX_DIM, s));
+#define HJH_B(T, HAM)                                                                                          \
+    do {                                                                                                       \
+        GridArgs<T, HAM<T>::ND> G;                                                                             \
+        memset(&G, 0, sizeof(G));                                                                              \
+        fill_grid<T, HAM<T>::ND>(g, G);                                                                        \
+        HiTables<T> P;                                                                                         \
+        fill_tables<T>(tab, params_host, P);                                                                   \
+        hipLaunchKernelGGL((hidim_bound_kernel<T, HAM<T>>), dim3(bx), dim3(256), 0, s, G, P, k);               \
+        HIP_TRY(hipGetLastError());                                                                            \
+        launched("hidim_bound_kernel<" #T ", " #HAM ">");                                                      \
+    } while (0)
+    if (g->dtype == HJ_F64) { if (ham == HJH_HAM_PLANE5D) HJH_B(double, HamPlane5D); else HJH_B(double, HamDubinsPair6D); }
+    else { if (ham == HJH_HAM_PLANE5D) HJH_B(float, HamPlane5D); else HJH_B(float, HamDubinsPair6D); }
+#undef HJH_B
+    return HJ_OK;
+}
+
 static double key_to_double(unsigned long long k) {
     const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
     double v;
@@ -478,22 +545,12 @@ int hjh_step_bound(const hjh_grid* g, const hjh_tables* tab, int ham, const doub
     if (!keys || !sb_host) return fail(HJ_EINVAL, "null argument");
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* k = (unsigned long long*)keys;
-    HIP_TRY(hipMemsetAsync(k, 0, sizeof(unsigned long long) * HJH_MAX_DIM, s));
     const unsigned bx = (unsigned)std::min<long long>((total + 255) / 256, 1024);
-#define HJH_B(T, HAM)                                                                                          \
-    do {                                                                                                       \
-        GridArgs<T, HAM<T>::ND> G;                                                                             \
-        memset(&G, 0, sizeof(G));                                                                              \
-        fill_grid<T, HAM<T>::ND>(g, G);                                                                        \
-        HiTables<T> P;                                                                                         \
-        fill_tables<T>(tab, params_host, P);                                                                   \
-        hipLaunchKernelGGL((hidim_bound_kernel<T, HAM<T>>), dim3(bx), dim3(256), 0, s, G, P, k);               \
-        HIP_TRY(hipGetLastError());                                                                            \
-        launched("hidim_bound_kernel<" #T ", " #HAM ">");                                                      \
-    } while (0)
-    if (g->dtype == HJ_F64) { if (ham == HJH_HAM_PLANE5D) HJH_B(double, HamPlane5D); else HJH_B(double, HamDubinsPair6D); }
-    else { if (ham == HJH_HAM_PLANE5D) HJH_B(float, HamPlane5D); else HJH_B(float, HamDubinsPair6D); }
-#undef HJH_B
+    if (ham >= HJH_HAM_USER_BASE) {
+        if (g->dtype == HJ_F64) rc = g->ndim == 5 ? launch_user_bound<double, 5>(g, tab, ham, params_host, k, bx, s) : launch_user_bound<double, 6>(g, tab, ham, params_host, k, bx, s);
+        else rc = g->ndim == 5 ? launch_user_bound<float, 5>(g, tab, ham, params_host, k, bx, s) : launch_user_bound<float, 6>(g, tab, ham, params_host, k, bx, s);
+    } else rc = launch_builtin_bound(g, tab, ham, params_host, k, bx, s);
+    if (rc) return rc;
     unsigned long long h[HJH_MAX_DIM];
     HIP_TRY(hipMemcpyAsync(h, k, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -587,6 +644,88 @@ int hjh_upwind(const hjh_grid* g, int scheme, const void* src, unsigned axis_mas
     HJH_DIMS(float, 3);
 #undef HJH_DIMS
 #undef HJH_U
+}
+
+int hjh_ham_register(const char* name, int ndim, int nparams, const char* body, int naux, const int32_t* aux_axes, const char* include_dir,
+                     const char* hiprtc_path, int* ham_id) {
+    if (!name || !body || !include_dir || !ham_id) return fail(HJ_EINVAL, "null argument");
+    // the name goes into #line directives of the generated source (compiler messages then point into the caller's text)
+    for (const char* ch = name; *ch; ++ch)
+        if (*ch == '"' || *ch == '\\' || (unsigned char)*ch < 32) return fail(HJ_EINVAL, "the name of a Hamiltonian must not contain quotes, backslashes or control characters");
+    if (ndim < HJH_MIN_DIM || ndim > HJH_MAX_DIM)
+        return fail(HJ_EUNSUPPORTED, "hjh_ham_register: grid.dim must be %d or %d, got %d (2..%d: hj_ham_register of hj_mi355x.h)", (int)HJH_MIN_DIM, (int)HJH_MAX_DIM, ndim, HJ_MAX_DIM);
+    if (nparams < 0 || nparams > HJH_PAR_SLOTS) return fail(HJ_EINVAL, "a Hamiltonian takes 0..%d parameters (HJH_PAR_SLOTS), got %d", HJH_PAR_SLOTS, nparams);
+    if (naux < 0 || naux > 4) return fail(HJ_EINVAL, "a Hamiltonian reads 0..4 tables (the aux slots of hjh_tables), got %d", naux);
+    if (naux > 0 && !aux_axes) return fail(HJ_EINVAL, "naux > 0 needs the tables' axes");
+    for (int k = 0; k < naux; ++k)
+        if (aux_axes[k] < 0 || aux_axes[k] >= ndim) return fail(HJ_EINVAL, "table %d runs along axis %d, outside the grid's 0..%d", k, (int)aux_axes[k], ndim - 1);
+    HJ_RTC_LOCK;
+    for (size_t i = 0; i < g_user.size(); ++i) {
+        const HiUserHam& v = g_user[i];
+        bool same = v.name == name && v.ndim == ndim && v.nparams == nparams && v.body == body && v.naux == naux;
+        for (int k = 0; same && k < naux; ++k) same = v.aux_axes[k] == aux_axes[k];
+        if (same) {
+            *ham_id = HJH_HAM_USER_BASE + (int)i;       // registering the same expression again: the same id, nothing recompiled
+            return HJ_OK;
+        }
+    }
+    HiUserHam u;
+    u.name = name;
+    u.body = body;
+    u.include_dir = include_dir;
+    u.rtc_path = hiprtc_path ? hiprtc_path : "";
+    u.ndim = ndim;
+    u.nparams = nparams;
+    u.naux = naux;
+    for (int k = 0; k < naux; ++k) u.aux_axes[k] = aux_axes[k];
+    g_user.push_back(u);
+    *ham_id = HJH_HAM_USER_BASE + (int)g_user.size() - 1;
+    return HJ_OK;
+}
+
+int hjh_ham_info(int ham_id, int* ndim, int* nparams, int* naux, int32_t* aux_axes, int* kernels_built) {
+    HJ_RTC_LOCK;
+    const HiUserHam* u = user_of(ham_id);
+    if (!u) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham_id);
+    if (ndim) *ndim = u->ndim;
+    if (nparams) *nparams = u->nparams;
+    if (naux) *naux = u->naux;
+    for (int k = 0; k < 4 && aux_axes; ++k) aux_axes[k] = k < u->naux ? u->aux_axes[k] : -1;
+    if (kernels_built) {
+        int n = 0;
+        for (const auto& kv : u->bound) n += kv.second.fn ? 1 : 0;
+        for (const auto& kv : u->substep) n += kv.second.fn ? 1 : 0;
+        *kernels_built = n;
+    }
+    return HJ_OK;
+}
+
+int hjh_ham_compile_check(int ham_id, int scheme, int dtype) {
+    HJ_RTC_LOCK;
+    const HiUserHam* u = user_of(ham_id);
+    if (!u) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham_id);
+    int rc = check_point_scheme(scheme, "5-D / 6-D substep");
+    if (rc) return rc;
+    if (dtype != HJ_F64 && dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", dtype);
+    const char* tn = dtype == HJ_F32 ? "float" : "double";
+    return hj_rtc::rtc_compile_check(user_source(*u, ham_id), {substep_expr(tn, scheme), bound_expr(tn)}, u->name, u->include_dir, u->rtc_path);
+}
+
+int hjh_ham_source(int ham_id, char* buf, int64_t n) {
+    HJ_RTC_LOCK;
+    const HiUserHam* u = user_of(ham_id);
+    if (!u) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham_id);
+    const std::string src = user_source(*u, ham_id);
+    if (!buf || n < (int64_t)src.size() + 1) return fail(HJ_EINVAL, "the generated source needs a buffer of %zu bytes", src.size() + 1);
+    memcpy(buf, src.c_str(), src.size() + 1);
+    return HJ_OK;
+}
+
+int hjh_ham_cache_stats(int* compiled, int* loaded_from_cache) {
+    HJ_RTC_LOCK;
+    if (compiled) *compiled = hj_rtc::g_rtc_compiles;
+    if (loaded_from_cache) *loaded_from_cache = hj_rtc::g_rtc_cache_hits;
+    return HJ_OK;
 }
 
 HJ_TOOL_LAST_SYMBOLS(hjh)

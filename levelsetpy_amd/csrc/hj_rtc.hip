@@ -19,62 +19,16 @@
 // (the range pass -- MODE 3 of the tiled kernel: derivL / derivR of every cell reduced to 2*ND minima / maxima, nothing written --
 // then the substep with the range visible to the expression and the in-kernel max(alpha) reduction kept) and hj_rk_step takes
 // dt from the first stage's reduced bound, as ode_cfl_3.py:142 does.  fp64 and fp32; 2-D, 3-D and 4-D grids.
-#include <dlfcn.h>
-#include <errno.h>
-#include <sys/stat.h>
-#include <sys/types.h>
-#include <unistd.h>
 #include <deque>
-#include <mutex>
 #include <sstream>
 #include "hj_launch.h"
 #include "hj_fusedv.h"
+#define HJ_RTC_FAIL ::hjh::fail
+#include "hj_rtc_host.h"      // the loader, the compile step, the disk cache, the module launch, the lock
 
 namespace hjh {
 
-typedef struct _hiprtcProgram* rtcProgram;
-struct Rtc {
-    void* handle = nullptr;
-    int (*CreateProgram)(rtcProgram*, const char*, const char*, int, const char**, const char**) = nullptr;
-    int (*CompileProgram)(rtcProgram, int, const char**) = nullptr;
-    int (*AddNameExpression)(rtcProgram, const char*) = nullptr;
-    int (*GetLoweredName)(rtcProgram, const char*, const char**) = nullptr;
-    int (*GetCodeSize)(rtcProgram, size_t*) = nullptr;
-    int (*GetCode)(rtcProgram, char*) = nullptr;
-    int (*GetProgramLogSize)(rtcProgram, size_t*) = nullptr;
-    int (*GetProgramLog)(rtcProgram, char*) = nullptr;
-    int (*DestroyProgram)(rtcProgram*) = nullptr;
-    const char* (*GetErrorString)(int) = nullptr;
-};
-static Rtc g_rtc;
-
-static int rtc_load(const char* path) {
-    if (g_rtc.handle) return HJ_OK;
-    const char* names[] = {path, "libhiprtc.so", "libhiprtc.so.7", "/opt/rocm/lib/libhiprtc.so"};
-    void* h = nullptr;
-    for (const char* n : names) {
-        if (!n || !*n) continue;
-        h = dlopen(n, RTLD_NOW | RTLD_GLOBAL);
-        if (h) break;
-    }
-    if (!h) return fail(HJ_ESTATE, "cannot dlopen hipRTC: %s", dlerror());
-#define HJ_SYM(field, name)                                                     \
-    *(void**)(&g_rtc.field) = dlsym(h, name);                                   \
-    if (!g_rtc.field) return fail(HJ_ESTATE, "hipRTC symbol %s missing", name);
-    HJ_SYM(CreateProgram, "hiprtcCreateProgram")
-    HJ_SYM(CompileProgram, "hiprtcCompileProgram")
-    HJ_SYM(AddNameExpression, "hiprtcAddNameExpression")
-    HJ_SYM(GetLoweredName, "hiprtcGetLoweredName")
-    HJ_SYM(GetCodeSize, "hiprtcGetCodeSize")
-    HJ_SYM(GetCode, "hiprtcGetCode")
-    HJ_SYM(GetProgramLogSize, "hiprtcGetProgramLogSize")
-    HJ_SYM(GetProgramLog, "hiprtcGetProgramLog")
-    HJ_SYM(DestroyProgram, "hiprtcDestroyProgram")
-    HJ_SYM(GetErrorString, "hiprtcGetErrorString")
-#undef HJ_SYM
-    g_rtc.handle = h;
-    return HJ_OK;
-}
+using namespace hj_rtc;
 
 // a module is loaded on ONE device (hipModuleLoadData binds it to the device that is current): kernels are kept per device
 // (ADVICE r04), their occupancy per dynamic-LDS size
@@ -94,13 +48,8 @@ struct UserHam {
     std::map<int, UserKernel> alpha;        // key: device * 2 + fp32
 };
 // Registered Hamiltonians live in a deque (registration never moves an element another thread may be launching) and every entry point that
-// looks at or extends the per-Hamiltonian kernel tables takes g_rtc_mu: kernels are compiled lazily at the first launch, and several host
-// threads driving their own contexts (virtual ranks in one process: tests/fuzz_slabs.py found the race in round 5 -- eight threads met in
-// the first compile of the same kernel) must see either no kernel or a complete one.  The launches themselves are asynchronous: the lock is
-// held for microseconds once the kernels exist.
+// looks at or extends the per-Hamiltonian kernel tables takes HJ_RTC_LOCK (hj_rtc_host.h): kernels are compiled lazily at the first launch.
 static std::deque<UserHam> g_user;
-static std::recursive_mutex g_rtc_mu;
-#define HJ_RTC_LOCK std::lock_guard<std::recursive_mutex> hj_rtc_guard(g_rtc_mu)
 
 static UserHam* user_of(int ham) {
     const int i = ham - HJ_HAM_USER_BASE;
@@ -160,165 +109,15 @@ static std::string user_source(const UserHam& u, int id) {
     return o.str();
 }
 
-// ---- code-object cache on disk: a registered expression is compiled once per (source, kernel headers, options), not once per
-// process.  Directory: $HJ_RTC_CACHE ("0" / "off" disables), else $XDG_CACHE_HOME/levelsetpy_amd, else $HOME/.cache/levelsetpy_amd;
-// it must belong to the user and not be writable by group or others (a planted file would be code run on the GPU), else the cache
-// is off.  File <key>.hjco = "HJCO2\n" + lowered kernel name + "\n" + 16 hex digits: size of the code object + "\n" + 16 hex digits:
-// FNV-1a of (key material, code object) + "\n" + code object; key = two FNV-1a hashes (128 bits) of the generated source, the name
-// expression, the compile options, the TEXT of every kernel header the source includes, sizeof(FusedArgs) (the kernel-argument ABI)
-// and the HIP runtime version.  A header that cannot be read turns the cache off (the key would not cover it).  Written atomically
-// (temporary + rename); a file whose size or checksum does not match is ignored and replaced.
-static unsigned long long fnv1a(const void* data, size_t n, unsigned long long h = 1469598103934665603ull) {
-    const unsigned char* p = (const unsigned char*)data;
-    for (size_t i = 0; i < n; ++i) { h ^= p[i]; h *= 1099511628211ull; }
-    return h;
+// what the disk cache's key covers besides the generated source (hj_rtc_host.h): every header that source can include, the kernel-argument ABI
+static const Unit& tiled_unit() {
+    static const Unit u = {{"/hj_fusedv.h", "/hj_fused4v.h", "/hj_fused.h", "/hj_termop.h", "/hj_device.h", "/hj_split.h", "/../../include/hj_mi355x.h"},
+                           {sizeof(FusedArgs<double, 3>), sizeof(FusedArgs<float, 4>), sizeof(HamTables<double>)}};
+    return u;
 }
-static bool read_file(const std::string& path, std::string& out) {
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    char buf[65536];
-    size_t n;
-    out.clear();
-    while ((n = fread(buf, 1, sizeof(buf), f)) > 0) out.append(buf, n);
-    fclose(f);
-    return true;
-}
-static std::string cache_dir() {
-    const char* e = getenv("HJ_RTC_CACHE");
-    if (e && (!strcmp(e, "0") || !strcmp(e, "off"))) return "";
-    std::string d;
-    if (e && *e) d = e;
-    else if ((e = getenv("XDG_CACHE_HOME")) && *e) d = std::string(e) + "/levelsetpy_amd";
-    else if ((e = getenv("HOME")) && *e) d = std::string(e) + "/.cache/levelsetpy_amd";
-    else return "";
-    // mkdir -p of the last two components (the parents of a cache home exist)
-    const size_t cut = d.find_last_of('/');
-    if (cut != std::string::npos && cut > 0) (void)mkdir(d.substr(0, cut).c_str(), 0700);
-    if (mkdir(d.c_str(), 0700) != 0 && errno != EEXIST) return "";
-    struct stat st;
-    if (stat(d.c_str(), &st) != 0 || !S_ISDIR(st.st_mode) || st.st_uid != geteuid() || (st.st_mode & (S_IWGRP | S_IWOTH))) return "";
-    return d;
-}
-// hash of the text of every header the generated source can include; ok = false if one of them cannot be read
-static unsigned long long headers_hash(const std::string& include_dir, unsigned long long seed, bool& ok) {
-    static std::map<std::string, std::pair<unsigned long long, bool>> memo;
-    const std::string key = include_dir + "#" + std::to_string(seed);
-    auto it = memo.find(key);
-    if (it != memo.end()) { ok = it->second.second; return it->second.first; }
-    unsigned long long h = seed;
-    ok = true;
-    const char* files[] = {"/hj_fusedv.h", "/hj_fused4v.h", "/hj_fused.h", "/hj_termop.h", "/hj_device.h", "/hj_split.h", "/../../include/hj_mi355x.h"};
-    std::string text;
-    for (const char* f : files) {
-        if (read_file(include_dir + f, text)) h = fnv1a(text.data(), text.size(), h);
-        else {
-            // the key cannot cover this header's text: the caller keeps the disk cache OFF for this include directory (and says so once)
-            ok = false;
-            fprintf(stderr, "[hj] run-time kernels: cannot read %s%s -- the on-disk code-object cache is disabled\n", include_dir.c_str(), f);
-        }
-    }
-    memo[key] = std::make_pair(h, ok);
-    return h;
-}
-static int g_rtc_cache_hits = 0, g_rtc_compiles = 0;
 
 static int rtc_build(UserHam& u, int id, const std::string& name_expr, UserKernel& out) {
-    const std::string src = user_source(u, id);
-    const char* base_opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", "-DHJ_RTC=1"};
-    std::string cache_file;
-    unsigned long long key_lo = 0;
-    {
-        const std::string dir = cache_dir();
-        if (!dir.empty()) {
-            unsigned long long h[2];
-            bool ok = true;
-            for (int w = 0; w < 2; ++w) {
-                const unsigned long long seed = w == 0 ? 1469598103934665603ull : 0x9e3779b97f4a7c15ull;
-                unsigned long long x = fnv1a(src.data(), src.size(), seed);
-                x = fnv1a(name_expr.data(), name_expr.size(), x);
-                for (const char* o : base_opts) x = fnv1a(o, strlen(o), x);
-                bool okh = true;
-                const unsigned long long hh = headers_hash(u.include_dir, seed, okh);
-                ok = ok && okh;
-                x = fnv1a(&hh, sizeof(hh), x);
-                const unsigned long long abi[3] = {sizeof(FusedArgs<double, 3>), sizeof(FusedArgs<float, 4>), sizeof(HamTables<double>)};
-                x = fnv1a(abi, sizeof(abi), x);
-                int rtv = 0;                                   // a new ROCm release compiles again
-                (void)hipRuntimeGetVersion(&rtv);
-                x = fnv1a(&rtv, sizeof(rtv), x);
-                h[w] = x;
-            }
-            if (ok) {
-                key_lo = h[0];
-                char nm[64];
-                snprintf(nm, sizeof(nm), "/%016llx%016llx.hjco", h[0], h[1]);
-                cache_file = dir + nm;
-                std::string blob;
-                if (read_file(cache_file, blob) && blob.compare(0, 6, "HJCO2\n") == 0) {
-                    const size_t n1 = blob.find('\n', 6);
-                    if (n1 != std::string::npos && blob.size() >= n1 + 1 + 17 + 17) {
-                        const std::string kname = blob.substr(6, n1 - 6);
-                        const unsigned long long want_size = strtoull(blob.substr(n1 + 1, 16).c_str(), nullptr, 16);
-                        const unsigned long long want_sum = strtoull(blob.substr(n1 + 18, 16).c_str(), nullptr, 16);
-                        const size_t off = n1 + 1 + 17 + 17;
-                        if (blob[n1 + 17] == '\n' && blob[n1 + 34] == '\n' && blob.size() - off == want_size &&
-                            fnv1a(blob.data() + off, blob.size() - off, key_lo) == want_sum &&
-                            hipModuleLoadData(&out.mod, blob.data() + off) == hipSuccess &&
-                            hipModuleGetFunction(&out.fn, out.mod, kname.c_str()) == hipSuccess) {
-                            ++g_rtc_cache_hits;
-                            return HJ_OK;
-                        }
-                        (void)hipGetLastError();
-                        out.mod = nullptr; out.fn = nullptr;
-                    }
-                }
-            }
-        }
-    }
-    int rc = rtc_load(u.rtc_path.empty() ? nullptr : u.rtc_path.c_str());
-    if (rc) return rc;
-    ++g_rtc_compiles;
-    rtcProgram prog = nullptr;
-    int e = g_rtc.CreateProgram(&prog, src.c_str(), "hj_user_ham.hip", 0, nullptr, nullptr);
-    if (e) return fail(HJ_EHIP, "hiprtcCreateProgram: %s", g_rtc.GetErrorString(e));
-    e = g_rtc.AddNameExpression(prog, name_expr.c_str());
-    const std::string inc1 = "-I" + u.include_dir, inc2 = "-I" + u.include_dir + "/../../include";
-    const char* opts[] = {base_opts[0], base_opts[1], base_opts[2], base_opts[3], inc1.c_str(), inc2.c_str(), base_opts[4]};
-    if (!e) e = g_rtc.CompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
-    if (e) {
-        size_t n = 0;
-        std::string log;
-        if (g_rtc.GetProgramLogSize(prog, &n) == 0 && n > 1) { log.resize(n); (void)g_rtc.GetProgramLog(prog, &log[0]); }
-        (void)g_rtc.DestroyProgram(&prog);
-        if (log.size() > 3000) log = log.substr(0, 3000) + " ...";
-        return fail(HJ_EINVAL, "the Hamiltonian '%s' does not compile (%s):\n%s", u.name.c_str(), g_rtc.GetErrorString(e), log.c_str());
-    }
-    const char* lowered = nullptr;
-    e = g_rtc.GetLoweredName(prog, name_expr.c_str(), &lowered);
-    size_t n = 0;
-    if (!e) e = g_rtc.GetCodeSize(prog, &n);
-    std::vector<char> code(n);
-    if (!e) e = g_rtc.GetCode(prog, code.data());
-    const std::string kname = lowered ? lowered : "";
-    (void)g_rtc.DestroyProgram(&prog);
-    if (e) return fail(HJ_EHIP, "hipRTC: %s", g_rtc.GetErrorString(e));
-    HIP_TRY(hipModuleLoadData(&out.mod, code.data()));
-    HIP_TRY(hipModuleGetFunction(&out.fn, out.mod, kname.c_str()));
-    if (!cache_file.empty()) {
-        char tmpn[64];
-        snprintf(tmpn, sizeof(tmpn), ".tmp%ld", (long)getpid());
-        const std::string tmp = cache_file + tmpn;
-        FILE* f = fopen(tmp.c_str(), "wb");
-        if (f) {
-            char meta[64];
-            snprintf(meta, sizeof(meta), "%016llx\n%016llx\n", (unsigned long long)code.size(), fnv1a(code.data(), code.size(), key_lo));
-            bool ok = fwrite("HJCO2\n", 1, 6, f) == 6 && fwrite(kname.data(), 1, kname.size(), f) == kname.size() && fputc('\n', f) != EOF &&
-                      fwrite(meta, 1, 34, f) == 34 && fwrite(code.data(), 1, code.size(), f) == code.size();
-            ok = (fclose(f) == 0) && ok;
-            if (!ok || rename(tmp.c_str(), cache_file.c_str()) != 0) (void)remove(tmp.c_str());
-        }
-    }
-    return HJ_OK;
+    return hj_rtc::rtc_build(tiled_unit(), user_source(u, id), name_expr, u.name, u.include_dir, u.rtc_path, out.mod, out.fn);
 }
 
 // kernel-argument block of the tiled kernels: (const T* y, const T* y0, T* out, const FusedArgs<T, ND> A)
@@ -339,12 +138,6 @@ template <typename T, int ND> struct AlphaKernArgs {
     unsigned long long seq;
     DtArgs DT;
 };
-
-static int module_launch(hipFunction_t fn, unsigned grid, unsigned block, size_t lds, hipStream_t st, void* args, size_t nbytes) {
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &nbytes, HIP_LAUNCH_PARAM_END};
-    HIP_TRY(hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, (unsigned)lds, st, nullptr, cfg));
-    return HJ_OK;
-}
 
 // Kernel shapes of the run-time instantiations -- those of the built-in systems (hj_inst.hip):
 //   0 "small": pair kernel, one pair per thread in 256-thread workgroups -- ~120 VGPRs are left for an arbitrary expression
@@ -683,37 +476,18 @@ int hj_ham_compile_check(int ham_id, int scheme) {
     UserHam* u = user_of(ham_id);
     if (!u) return fail(HJ_EINVAL, "unknown Hamiltonian id %d", ham_id);
     if (scheme < 0 || scheme > HJ_ENO3_FAST) return fail(HJ_EINVAL, "unknown scheme %d", scheme);
-    int rc = rtc_load(u->rtc_path.empty() ? nullptr : u->rtc_path.c_str());
-    if (rc) return rc;
     const bool dynamic = (u->flags & HJ_HAM_RANGE) != 0;
     const UShape sh = shape_of(u->ndim == 4 ? 2 : 0, false);
-    const std::string src = user_source(*u, ham_id);
-    if (const char* dump = getenv("HJ_RTC_DUMP")) {        // the translation unit hipRTC is given, for a look at it (or an offline hipcc -S)
-        if (FILE* f = fopen(dump, "w")) { fputs(src.c_str(), f); fclose(f); }
-    }
-    rtcProgram prog = nullptr;
-    int e = g_rtc.CreateProgram(&prog, src.c_str(), "hj_user_ham.hip", 0, nullptr, nullptr);
-    if (e) return fail(HJ_EHIP, "hiprtcCreateProgram: %s", g_rtc.GetErrorString(e));
     // every instantiation a step can launch, in BOTH dtypes (an expression that fails only in the float instantiation, or in the
     // bound kernel of a range-reading Hamiltonian -- hj_rk_step under GLF and hj_range_alpha_max launch it -- passed the check and failed at the
     // first step)
+    std::vector<std::string> names;
     for (const char* tn : {"double", "float"}) {
-        if (!e) e = g_rtc.AddNameExpression(prog, kernel_name(sh, tn, scheme, 0).c_str());
-        if (!e && dynamic) e = g_rtc.AddNameExpression(prog, kernel_name(sh, tn, scheme, 3).c_str());
-        if (!e) e = g_rtc.AddNameExpression(prog, (std::string("hj::alpha_bound_kernel<") + tn + ", hj::HamUser<" + tn + ">>").c_str());
+        names.push_back(kernel_name(sh, tn, scheme, 0));
+        if (dynamic) names.push_back(kernel_name(sh, tn, scheme, 3));
+        names.push_back(std::string("hj::alpha_bound_kernel<") + tn + ", hj::HamUser<" + tn + ">>");
     }
-    const std::string inc1 = "-I" + u->include_dir, inc2 = "-I" + u->include_dir + "/../../include";
-    const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=on", inc1.c_str(), inc2.c_str(), "-DHJ_RTC=1"};
-    if (!e) e = g_rtc.CompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
-    std::string log;
-    if (e) {
-        size_t n = 0;
-        if (g_rtc.GetProgramLogSize(prog, &n) == 0 && n > 1) { log.resize(n); (void)g_rtc.GetProgramLog(prog, &log[0]); }
-        if (log.size() > 3000) log = log.substr(0, 3000) + " ...";
-    }
-    (void)g_rtc.DestroyProgram(&prog);
-    if (e) return fail(HJ_EINVAL, "the Hamiltonian '%s' does not compile (%s):\n%s", u->name.c_str(), g_rtc.GetErrorString(e), log.c_str());
-    return HJ_OK;
+    return rtc_compile_check(user_source(*u, ham_id), names, u->name, u->include_dir, u->rtc_path);
 }
 
 }  // extern "C"

@@ -6,8 +6,9 @@ upwindFirstENO2 / ENO3 / WENO5 as shipped and computeGradients (upwind_one, upwi
 stay refused.
 
 Two paths:
-  fused   hamFunc / partialFunc are the methods of Plane5D or DubinsPair6D (dynamics.py, native_of's identity rule):
-          every Runge-Kutta stage is ONE launch of hidim_substep_kernel, a whole tau interval one native call
+  fused   hamFunc / partialFunc are the methods of Plane5D or DubinsPair6D (dynamics.py, native_of's identity rule), or of a
+          system registered with hidim_ham.register_hidim_hamiltonian (its kernel is compiled at run time around the
+          user's expression and reads the system's own tables): every Runge-Kutta stage is ONE launch of hidim_substep_kernel, a whole tau interval one native call
           (hjh_integrate), the compMethod minimum / maximum and the obstacle mask applied by the last stage of a step.
   split   any other callbacks: hjh_upwind writes derivL[d], derivR[d] of every axis from one gather per cell, the
           callbacks run on device tensors, and the dissipation sum, -(ham - diss) and the stage expressions follow as
@@ -88,6 +89,28 @@ class HiGrid(DeviceGrid):
         self._raw_stream = _raw_stream_getter(torch)
         self._keys = torch.zeros((4 * _hffi.MAX_DIM,), dtype=torch.int64, device=self.device)
         self._sb = {}
+        self._user_tabs = weakref.WeakKeyDictionary()      # registered system -> (fingerprint, Tables, its tensors)
+
+    def tables_of(self, system):
+        """(Tables, fingerprint) for a launch of `system`: the grid's own for a built-in, and for a registered system (hidim_ham.py) the
+        grid's coordinate tables with that system's aux tables -- kept on the device per system, away from the grid-wide cos / sin cache,
+        and uploaded again when the system's tables change."""
+        att = getattr(system, "_hj_native", None)
+        if att is None or not hasattr(att, "tables"):
+            return self.tab, ()
+        fp = tuple(t.tobytes() for t in att.tables)
+        hit = self._user_tabs.get(system)
+        if hit is None or hit[0] != fp:
+            torch = self.torch
+            keep = [torch.from_numpy(np.array(t, dtype=np.float64)).to(self.tdtype).to(self.device) for t in att.tables]
+            tab = _hffi.Tables()
+            for d in range(self.dim):
+                tab.coord[d] = self.tab.coord[d]
+            for k, t in enumerate(keep):
+                tab.aux[k] = t.data_ptr()
+            hit = (fp, tab, keep)
+            self._user_tabs[system] = hit
+        return hit[1], fp
 
     def stream(self):
         return C.c_void_p(self._raw_stream(self.device.index))
@@ -95,13 +118,15 @@ class HiGrid(DeviceGrid):
     def bind_stream(self):
         pass
 
-    def step_bound(self, ham, par):
-        """stepBound of (grid, system): data independent, one hjh_step_bound call per parameter set."""
-        key = (ham, tuple(par))
+    def step_bound(self, ham, par, system=None):
+        """stepBound of (grid, system): data independent, one hjh_step_bound call per parameter set (and, for a registered system, per
+        content of its tables)."""
+        tab, fp = self.tables_of(system)
+        key = (ham, tuple(par), fp)
         sb = self._sb.get(key)
         if sb is None:
             v = C.c_double()
-            _hffi.check(self.lib.hjh_step_bound(C.byref(self.desc), C.byref(self.tab), int(ham), _hffi.params(par),
+            _hffi.check(self.lib.hjh_step_bound(C.byref(self.desc), C.byref(tab), int(ham), _hffi.params(par),
                                                 self.ptr(self._keys), C.byref(v), None, self.stream()))
             sb = self._sb[key] = float(v.value)
         return sb
@@ -122,8 +147,9 @@ def hi_grid(grid, dtype="float64"):
     return hg
 
 
-def step_bound(grid, ham, par, dtype="float64"):
-    return hi_grid(grid, dtype).step_bound(ham, par)
+def step_bound(grid, ham, par, dtype="float64", system=None):
+    """system: the registered system object whose tables the kernel reads (hidim_ham.py); not needed for the built-ins."""
+    return hi_grid(grid, dtype).step_bound(ham, par, system)
 
 
 def _check_scheme(sid):
@@ -177,8 +203,8 @@ def upwind_one(scheme_name, grid, data, dim):
 
 
 # ------------------------------------------------------------------------------------------ the term
-def _substep(hg, sid, ham, par, stage, rs, src, y0, dst, dt=0.0, post_prev=0, op_a=0, post_a=None, op_b=0, post_b=None):
-    _hffi.check(hg.lib.hjh_substep(C.byref(hg.desc), C.byref(hg.tab), int(sid), int(ham), int(stage), int(rs), _hffi.params(par),
+def _substep(hg, sid, ham, par, stage, rs, src, y0, dst, dt=0.0, post_prev=0, op_a=0, post_a=None, op_b=0, post_b=None, tab=None):
+    _hffi.check(hg.lib.hjh_substep(C.byref(hg.desc), C.byref(hg.tab if tab is None else tab), int(sid), int(ham), int(stage), int(rs), _hffi.params(par),
                                    hg.ptr(src), hg.ptr(y0), hg.ptr(dst), float(dt), int(post_prev), int(op_a), hg.ptr(post_a),
                                    int(op_b), hg.ptr(post_b), hg.stream()))
 
@@ -193,9 +219,10 @@ def fused_term(plan, t, y, restrict_sign):
         raise ValueError('y does not agree in size with grid')
     yd = hg.to_device(y)
     out = hg.empty()
-    _substep(hg, sid, ham, par, _ffi.STAGE_YDOT, restrict_sign, yd, None, out)
+    system = getattr(plan, "system", None)
+    _substep(hg, sid, ham, par, _ffi.STAGE_YDOT, restrict_sign, yd, None, out, tab=hg.tables_of(system)[0])
     _set_path(_hffi.last_kernel())
-    return out, hg.step_bound(ham, par), hg
+    return out, hg.step_bound(ham, par, system), hg
 
 
 # ------------------------------------------------------------------------------------------ HJIPDE_solve
@@ -305,15 +332,16 @@ def solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
     nat = native_of(schemeData.hamFunc, schemeData.partialFunc) if (isfield(schemeData, 'hamFunc') and isfield(schemeData, 'partialFunc')) else None
     why = None
     if nat is None:
-        why = 'hamFunc / partialFunc are not the methods of Plane5D / DubinsPair6D'
-    elif _hffi.HAM_DIMS.get(nat[1]) != gDim or nat[0].grid is not g:
+        why = 'hamFunc / partialFunc are not the methods of Plane5D / DubinsPair6D or of a system registered with register_hidim_hamiltonian'
+    elif _hffi.ham_dim(nat[1]) != gDim or nat[0].grid is not g:
         why = 'the system does not live on this grid'
     elif sid is None:
         why = 'the derivative function is not one of upwindFirstENO2 / ENO3 / WENO5'
     fused = why is None
     if fused:
         ham, par = nat[1], [float(v) for v in nat[2]]
-        sb = hg.step_bound(ham, par)
+        tab = hg.tables_of(nat[0])[0]
+        sb = hg.step_bound(ham, par, nat[0])
         path = "%s (no step taken)" % _hffi.kernel_name("float64", ham, sid)
     else:
         path = "split: " + why
@@ -351,7 +379,7 @@ def solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
             free = [b for b in bufs if b.data_ptr() != y.data_ptr()]
             tout, nsteps, where = C.c_double(), C.c_int64(), C.c_int32()
             _hffi.check(hg.lib.hjh_integrate(
-                C.byref(hg.desc), C.byref(hg.tab), int(sid), int(ham), 3, rs, int(post_prev), _hffi.params(par), float(sb),
+                C.byref(hg.desc), C.byref(tab), int(sid), int(ham), 3, rs, int(post_prev), _hffi.params(par), float(sb),
                 hg.ptr(y), hg.ptr(free[0]), hg.ptr(free[1]), hg.ptr(work), int(op_a), hg.ptr(arr_a), int(op_b), hg.ptr(arr_b),
                 float(tNow), float(tau[i]), FACTOR_CFL, float(realmax), SMALL, C.byref(tout), C.byref(nsteps), C.byref(where),
                 hg.stream()))

@@ -15,7 +15,7 @@ import weakref
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, _hffi
 from .context import device_grid, array_dtype_name, is_tensor
 from . import dissipation as _diss
 from .dissipation import artificialDissipationGLF, artificialDissipationLLF, artificialDissipationLLLF, glf_device
@@ -125,6 +125,8 @@ def explain_plan(schemeData):
     plan = _plan_of(sd)
     if int(sd.grid.dim) > 4:
         # 5-D / 6-D grids (hidim.py): the two systems of libhj_hidim.so run fused, everything else through hjh_upwind and array expressions
+        if plan is not None and plan[2] >= _hffi.HAM_USER_BASE:      # hidim_ham.register_hidim_hamiltonian
+            return dict(path='registered', ham_id=plan[2], params=list(plan[3]), library='libhj_hidim.so')
         if plan is not None:
             return dict(path='built-in', ham_id=plan[2], params=list(plan[3]), library='libhj_hidim.so')
         return dict(path='split', reason='on a grid of %d dimensions only Plane5D / DubinsPair6D with artificialDissipationGLF run fused; the '

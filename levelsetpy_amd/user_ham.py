@@ -23,6 +23,7 @@ alpha[d].  Values that depend on the in-plane coordinates only (cos / sin of x[2
 `column_src="col[0] = cos(x[2]); col[1] = sin(x[2]);", ncol=2` evaluates them once per grid column, `col[k]` is then
 readable in the expression (8 % faster for the Dubins systems).  fp64 and fp32, 2-D / 3-D / 4-D grids; the kernels are built with hipRTC on first
 use (1-2 s per scheme) and kept on disk (kernel_cache_stats): a later process loads them in milliseconds.
+5-D and 6-D grids: hidim_ham.register_hidim_hamiltonian (no march there, so no column_src; tables instead).
 """
 import ctypes as C
 import os
