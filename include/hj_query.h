@@ -17,7 +17,11 @@
  */
 #ifndef HJ_QUERY_H
 #define HJ_QUERY_H
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else                                  /* hipRTC (hjp_plant_register) has no system headers; hj_mi355x.h brings int64_t */
+typedef signed int int32_t;
+#endif
 #include "hj_mi355x.h"
 
 #ifdef __cplusplus

@@ -32,7 +32,9 @@
  */
 #ifndef HJ_ROLLOUT_H
 #define HJ_ROLLOUT_H
+#ifndef __HIPCC_RTC__                  /* hipRTC (hjp_plant_register) has no system headers */
 #include <stdint.h>
+#endif
 #include "hj_query.h"
 
 #ifdef __cplusplus

@@ -43,5 +43,6 @@ from .decomp import sepGrid, backProject, Decomposition                         
 from .eikonal import signedDistance, addCRadius                                  # noqa: F401
 from . import hidim                                                              # noqa: F401
 from .hidim_ham import register_hidim_hamiltonian, HidimRegistration, HidimSystem, hidim_kernel_cache_stats   # noqa: F401
+from .plant import register_plant, PlantRegistration, PlantSystem, plant_kernel_cache_stats   # noqa: F401
 
 __version__ = "0.1.0"

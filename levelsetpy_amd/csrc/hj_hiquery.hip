@@ -43,12 +43,8 @@ template <int ND> __device__ __forceinline__ QGrid at(const QGrid& G) {
     return g;
 }
 
-// The one-sided derivatives of a corner's stencil: computeGradients' at 5-D / 6-D (hidim_upwind_kernel), so that a corner
-// costate has the bits it gives that node -- ENO2 / ENO3 with every operation rounded on its own, the as-shipped WENO5 by upwind<>.
-struct UpwindHidim {
-    template <int SCHEME, typename T>
-    __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind_lr_hidim<SCHEME, T>(v, K, L, R); }
-};
+// the one-sided derivatives of a corner's stencil at 5-D / 6-D: hj_rollout_dev.h's, which libhj_plant.so's run-time kernels share
+using hjr::UpwindHidim;
 
 template <typename T>
 __device__ __forceinline__ void put(void* out, long long i, double v, int out_f64) {

@@ -1,0 +1,317 @@
+// libhj_plant.so (include/hj_plant.h): trajectory rollouts of a plant the caller writes, for gfx950.
+//   user_rollout_kernel<T, SCHEME>   rollout_kernel / hi_rollout_kernel around PlantUser, the two registered bodies: 2^ND lanes per
+//                                    trajectory, 256 threads per workgroup, the trajectory hj_rollout_dev.h's rollout_body
+// This file holds NO kernel.  It keeps the table of registered plants, generates a translation unit per plant (plant_source:
+// HJ_QUERY_MAXD for the plant's dimension, hj_query_dev.h, hj_rollout_dev.h, PlantUser, the kernel), has hipRTC compile the
+// instantiation a launch needs -- lazily per (plant, element type, scheme, device), under hj_rtc_host.h's lock, through its disk
+// cache -- and launches it through the module API with one argument block (hj_plant_dev.h's RolloutArgs).  The library links
+// nothing of the other eleven.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstring>
+#include <deque>
+#include <map>
+#include <sstream>
+#include <vector>
+#include "hj_tool_host.h"
+#include "hj_plant_dev.h"
+#define HJ_RTC_FAIL ::hj_tool::fail
+#define HJ_RTC_WHAT "plant"
+#include "hj_rtc_host.h"
+
+namespace hjp {
+
+using namespace hj_tool;
+
+struct Kernel {
+    hipModule_t mod = nullptr;
+    hipFunction_t fn = nullptr;
+};
+// registered plants live in a deque (registration never moves an element another thread may be launching); every look at it
+// and at the kernel tables takes HJ_RTC_LOCK
+struct UserPlant {
+    std::string name, controls, dynamics, include_dir, rtc_path;
+    int ndim = 0, nu = 0, nd = 0, nparams = 0;
+    std::map<long long, Kernel> kernels;        // key: ((device * 2 + fp32) * 4 + scheme)
+};
+static std::deque<UserPlant> g_plants;
+
+static UserPlant* plant_of(int id) {
+    const long long i = (long long)id - HJP_PLANT_BASE;
+    return (i >= 0 && i < (long long)g_plants.size()) ? &g_plants[(size_t)i] : nullptr;
+}
+
+// The translation unit hipRTC compiles.  Both bodies run in fp64 under contraction off, each in a block of its own after a
+// #line directive, so that a compiler message reads name:line with the line counted inside that body.  u, dst and dx start at
+// zero: a body that leaves one out leaves a number, not a register's last content.
+static std::string plant_source(const UserPlant& u) {
+    std::ostringstream o;
+    const bool hi = u.ndim > HJ_MAX_DIM;
+    o << "#define HJ_QUERY_MAXD " << (hi ? HJH_MAX_DIM : HJ_MAX_DIM) << "\n";
+    if (hi) o << "#define HJ_QUERY_MIND " << HJH_MIN_DIM << "\n";
+    o << "#include \"hj_query_dev.h\"\n#include \"hj_rollout_dev.h\"\n#include \"hj_plant_dev.h\"\n"
+         "namespace hjp {\n"
+         "struct PlantUser {\n"
+         "    static constexpr int ND = " << u.ndim << ", NU = " << u.nu << ", NDST = " << u.nd << ";\n"
+         "    struct Control { double u[NU > 0 ? NU : 1]; double dst[NDST > 0 ? NDST : 1]; };\n"
+         "    __device__ static __forceinline__ void controls(const hjp_plant& hj_P, const double* p, const double* x, Control& hj_c) {\n"
+         "#pragma clang fp contract(off)\n"
+         "        using hjr::sgn;\n"
+         "        const double* par = hj_P.params;\n"
+         "        const bool u_max = hj_P.u_mode == HJR_MODE_MAX, d_max = hj_P.d_mode == HJR_MODE_MAX;\n"
+         "        double* u = hj_c.u;\n        double* dst = hj_c.dst;\n"
+         "        for (int i = 0; i < (NU > 0 ? NU : 1); ++i) u[i] = 0.0;\n"
+         "        for (int j = 0; j < (NDST > 0 ? NDST : 1); ++j) dst[j] = 0.0;\n"
+         "        (void)p; (void)x; (void)par; (void)u_max; (void)d_max;\n"
+         "        {\n#line 1 \"" << u.name << "\"\n" << u.controls << "\n#line 1 \"PlantUser\"\n        }\n"
+         "    }\n"
+         "    __device__ static __forceinline__ void f(const hjp_plant& hj_P, const double* x, const Control& hj_c, double* dx) {\n"
+         "#pragma clang fp contract(off)\n"
+         "        using hjr::sgn;\n"
+         "        const double* par = hj_P.params;\n"
+         "        const double* u = hj_c.u;\n        const double* dst = hj_c.dst;\n"
+         "        for (int d = 0; d < ND; ++d) dx[d] = 0.0;\n"
+         "        (void)x; (void)par; (void)u; (void)dst;\n"
+         "        {\n#line 1 \"" << u.name << "\"\n" << u.dynamics << "\n#line 1 \"PlantUser\"\n        }\n"
+         "    }\n"
+         "};\n"
+         "// A finished trajectory idles in its wavefront (rollout_body never returns early), so every __shfl of group_sum runs with\n"
+         "// all lanes of its group active.\n"
+         "template <typename T, int SCHEME>\n"
+         "__global__ __launch_bounds__(256) void user_rollout_kernel(RolloutArgs<T, hjq::MAXD> A) { user_rollout<T, SCHEME, PlantUser>(A); }\n"
+         "}\n";
+    return o.str();
+}
+
+// what the disk cache's key covers besides the generated source (hj_rtc_host.h): every header the unit includes, the public ones
+// among them, and the sizes of the kernel's argument block
+static const hj_rtc::Unit& plant_unit() {
+    static const hj_rtc::Unit u = {{"/hj_plant_dev.h", "/hj_query_dev.h", "/hj_rollout_dev.h", "/hj_device.h", "/../../include/hj_plant.h",
+                                    "/../../include/hj_rollout.h", "/../../include/hj_query.h", "/../../include/hj_hidim.h",
+                                    "/../../include/hj_mi355x.h"},
+                                   {sizeof(RolloutArgs<double, HJ_MAX_DIM>), sizeof(RolloutArgs<float, HJ_MAX_DIM>),
+                                    sizeof(RolloutArgs<double, HJH_MAX_DIM>), sizeof(RolloutArgs<float, HJH_MAX_DIM>), sizeof(hjp_plant)}};
+    return u;
+}
+
+static std::string kernel_expr(const char* tn, int scheme) {
+    return std::string("hjp::user_rollout_kernel<") + tn + ", " + std::to_string(scheme) + ">";
+}
+
+// the kernel of (plant, current device, type, scheme): built at its first use.  Call with HJ_RTC_LOCK held.
+static int user_kernel(UserPlant& u, bool f32, int scheme, hipFunction_t& fn) {
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    Kernel& k = u.kernels[((long long)dev * 2 + (f32 ? 1 : 0)) * 4 + scheme];
+    if (!k.fn) {
+        int rc = hj_rtc::rtc_build(plant_unit(), plant_source(u), kernel_expr(f32 ? "float" : "double", scheme), u.name, u.include_dir,
+                                   u.rtc_path, k.mod, k.fn);
+        if (rc) { k.mod = nullptr; k.fn = nullptr; return rc; }
+    }
+    fn = k.fn;
+    return HJ_OK;
+}
+
+// the descriptor's checks (hj_query_dev.h's make_grid) and the block's grid and stencil fields; GD: hjq_grid or hjh_grid
+template <typename T, int MD, typename GD>
+static void fill_grid(const GD* g, RolloutArgs<T, MD>& A) {
+    long long total = 1;
+    for (int d = 0; d < MD; ++d) {
+        A.n[d] = 1; A.per[d] = 0; A.stride[d] = 0; A.xmin[d] = 0; A.xlast[d] = 0; A.dx[d] = 1;
+    }
+    for (int d = g->ndim - 1; d >= 0; --d) {
+        A.n[d] = (int)g->N[d];
+        A.per[d] = g->bc[d] == HJ_BC_PERIODIC;
+        A.stride[d] = total;
+        A.xmin[d] = g->xmin[d];
+        A.xlast[d] = g->xlast[d];
+        A.dx[d] = g->dx[d];
+        total *= g->N[d];
+    }
+    for (int d = 0; d < MD; ++d) {
+        A.km[d] = (d < g->ndim && g->toward_zero[d]) ? T(-1) : T(1);
+        hj::fill_stencil_constants<T>(A.dx[d], A.K[d]);
+    }
+}
+
+template <typename GD>
+static int check_grid(const GD* g, int mind, int maxd, long long& total) {
+    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
+    if (g->ndim < mind || g->ndim > maxd) return fail(HJ_EINVAL, "ndim %d outside %d..%d", (int)g->ndim, mind, maxd);
+    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
+    total = 1;
+    for (int d = g->ndim - 1; d >= 0; --d) {
+        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
+        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
+        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
+            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
+        total *= g->N[d];
+        if (total > (1ll << 40)) return fail(HJ_EINVAL, "grid too large");
+    }
+    return HJ_OK;
+}
+
+template <typename T, int MD, typename GD>
+static int launch(UserPlant& u, const GD* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t M,
+                  int sub_samples, double dt_small, const hjp_plant& P, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
+                  hipStream_t stream) {
+    unsigned blocks;
+    int rc = blocks_for((long long)M * (1ll << g->ndim), "too many trajectories for one launch", blocks);
+    if (rc) return rc;
+    const bool f32 = sizeof(T) == 4;
+    hipFunction_t fn = nullptr;
+    if ((rc = user_kernel(u, f32, scheme, fn))) return rc;      // a plant that does not compile has launched nothing
+    RolloutArgs<T, MD> A;
+    memset(&A, 0, sizeof(A));
+    A.data = (const T*)data;
+    A.field_stride = field_stride;
+    A.x0 = x0;
+    A.M = M;
+    A.ntimes = (int)ntimes;
+    A.sub_samples = sub_samples;
+    A.dt_small = dt_small;
+    fill_grid<T, MD>(g, A);
+    A.P = P;
+    for (int k = u.nparams; k < HJP_PAR_SLOTS; ++k) A.P.params[k] = 0.0;
+    A.traj = traj;
+    A.length = length;
+    A.t_earliest = t_earliest;
+    A.status = status;
+    if ((rc = hj_rtc::module_launch(fn, blocks, 256, 0, stream, &A, sizeof(A)))) return rc;
+    const std::string name = std::string("user_rollout_kernel<") + (f32 ? "float" : "double") + ", " + std::to_string(scheme) + ", PlantUser:" + u.name + ">";
+    launched(name.c_str());
+    return HJ_OK;
+}
+
+template <int MD, typename GD>
+static int rollout(const GD* g, int mind, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t nstates,
+                   int sub_samples, double dt_small, const hjp_plant* plant, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
+                   void* stream) {
+    long long total;
+    int rc = check_grid(g, mind, MD, total);
+    if (rc) return rc;
+    if (!plant) return fail(HJ_EINVAL, "null plant descriptor");
+    if (nstates < 0) return fail(HJ_EINVAL, "nstates must not be negative");
+    if (ntimes < 2 || ntimes > 0x7fffffffll) return fail(HJ_EINVAL, "ntimes %lld: a rollout needs at least two stored sets", (long long)ntimes);
+    if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
+    if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
+    if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    if ((rc = check_point_scheme(scheme, "rollout"))) return rc;
+    HJ_RTC_LOCK;
+    UserPlant* u = plant_of(plant->id);
+    if (!u) return fail(HJ_EINVAL, "unknown plant id %d: nothing is registered under it (hjp_plant_register)", (int)plant->id);
+    if (u->ndim != g->ndim) return fail(HJ_EINVAL, "plant '%s' has %d states, the grid %d dimensions", u->name.c_str(), u->ndim, (int)g->ndim);
+    if (plant->nparams != u->nparams) return fail(HJ_EINVAL, "plant '%s' takes %d parameters, the descriptor has %d", u->name.c_str(), u->nparams, (int)plant->nparams);
+    if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
+        return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
+    for (int d = 0; d < g->ndim; ++d)
+        if (g->N[d] < HJ_STENCIL) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, (int)g->N[d], HJ_STENCIL);
+    if (nstates == 0) return HJ_OK;
+    if (!data || !x0 || !traj || !length || !status) return fail(HJ_EINVAL, "null argument");
+    if (g->dtype == HJ_F64)
+        return launch<double, MD>(*u, g, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest,
+                                  status, (hipStream_t)stream);
+    return launch<float, MD>(*u, g, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest, status,
+                             (hipStream_t)stream);
+}
+
+}  // namespace hjp
+
+using namespace hjp;
+
+extern "C" {
+
+int hjp_plant_register(const char* name, int ndim, int ncontrols, int ndisturbances, int nparams, const char* controls_src,
+                       const char* dynamics_src, const char* include_dir, const char* hiprtc_path, int* plant_id) {
+    if (!name || !controls_src || !dynamics_src || !include_dir || !plant_id) return fail(HJ_EINVAL, "null argument");
+    // the name goes into #line directives of the generated source (compiler messages then point into the caller's text)
+    for (const char* ch = name; *ch; ++ch)
+        if (*ch == '"' || *ch == '\'' || *ch == '\\' || (unsigned char)*ch < 32) return fail(HJ_EINVAL, "the name of a plant must not contain quotes, backslashes or control characters");
+    if (ndim < HJP_MIN_DIM || ndim > HJP_MAX_DIM) return fail(HJ_EUNSUPPORTED, "hjp_plant_register: a plant has %d..%d states, got %d", HJP_MIN_DIM, HJP_MAX_DIM, ndim);
+    if (nparams < 0 || nparams > HJP_PAR_SLOTS) return fail(HJ_EINVAL, "a plant takes 0..%d parameters (HJP_PAR_SLOTS), got %d", HJP_PAR_SLOTS, nparams);
+    if (ncontrols < 0 || ndisturbances < 0 || ncontrols + ndisturbances < 1 || ncontrols + ndisturbances > HJP_MAX_CONTROLS)
+        return fail(HJ_EINVAL, "a plant has 1..%d controls and disturbances together (HJP_MAX_CONTROLS), got %d + %d", HJP_MAX_CONTROLS, ncontrols, ndisturbances);
+    HJ_RTC_LOCK;
+    for (size_t i = 0; i < g_plants.size(); ++i) {
+        const UserPlant& v = g_plants[i];
+        if (v.name == name && v.ndim == ndim && v.nu == ncontrols && v.nd == ndisturbances && v.nparams == nparams && v.controls == controls_src &&
+            v.dynamics == dynamics_src) {
+            *plant_id = HJP_PLANT_BASE + (int)i;        // registering the same text again: the same id, nothing recompiled
+            return HJ_OK;
+        }
+    }
+    UserPlant u;
+    u.name = name;
+    u.controls = controls_src;
+    u.dynamics = dynamics_src;
+    u.include_dir = include_dir;
+    u.rtc_path = hiprtc_path ? hiprtc_path : "";
+    u.ndim = ndim;
+    u.nu = ncontrols;
+    u.nd = ndisturbances;
+    u.nparams = nparams;
+    g_plants.push_back(u);
+    *plant_id = HJP_PLANT_BASE + (int)g_plants.size() - 1;
+    return HJ_OK;
+}
+
+int hjp_plant_info(int plant_id, int* ndim, int* ncontrols, int* ndisturbances, int* nparams, int* kernels_built) {
+    HJ_RTC_LOCK;
+    const UserPlant* u = plant_of(plant_id);
+    if (!u) return fail(HJ_EINVAL, "unknown plant id %d", plant_id);
+    if (ndim) *ndim = u->ndim;
+    if (ncontrols) *ncontrols = u->nu;
+    if (ndisturbances) *ndisturbances = u->nd;
+    if (nparams) *nparams = u->nparams;
+    if (kernels_built) {
+        int n = 0;
+        for (const auto& kv : u->kernels) n += kv.second.fn ? 1 : 0;
+        *kernels_built = n;
+    }
+    return HJ_OK;
+}
+
+int hjp_plant_source(int plant_id, char* buf, int64_t n) {
+    HJ_RTC_LOCK;
+    const UserPlant* u = plant_of(plant_id);
+    if (!u) return fail(HJ_EINVAL, "unknown plant id %d", plant_id);
+    const std::string src = plant_source(*u);
+    if (!buf || n < (int64_t)src.size() + 1) return fail(HJ_EINVAL, "the generated source needs a buffer of %zu bytes", src.size() + 1);
+    memcpy(buf, src.c_str(), src.size() + 1);
+    return HJ_OK;
+}
+
+int hjp_plant_cache_stats(int* compiled, int* loaded_from_cache) {
+    HJ_RTC_LOCK;
+    if (compiled) *compiled = hj_rtc::g_rtc_compiles;
+    if (loaded_from_cache) *loaded_from_cache = hj_rtc::g_rtc_cache_hits;
+    return HJ_OK;
+}
+
+int hjp_plant_compile_check(int plant_id, int scheme, int dtype) {
+    HJ_RTC_LOCK;
+    const UserPlant* u = plant_of(plant_id);
+    if (!u) return fail(HJ_EINVAL, "unknown plant id %d", plant_id);
+    int rc = check_point_scheme(scheme, "rollout");
+    if (rc) return rc;
+    if (dtype != HJ_F64 && dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", dtype);
+    return hj_rtc::rtc_compile_check(plant_source(*u), {kernel_expr(dtype == HJ_F32 ? "float" : "double", scheme)}, u->name, u->include_dir, u->rtc_path);
+}
+
+int hjp_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t nstates,
+                int sub_samples, double dt_small, const hjp_plant* plant, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
+                void* stream) {
+    return rollout<HJ_MAX_DIM>(g, HJP_MIN_DIM, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, plant, traj, length, t_earliest,
+                               status, stream);
+}
+
+int hjp_rollout_hi(const hjh_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t nstates,
+                   int sub_samples, double dt_small, const hjp_plant* plant, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
+                   void* stream) {
+    return rollout<HJH_MAX_DIM>(g, HJH_MIN_DIM, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, plant, traj, length,
+                                t_earliest, status, stream);
+}
+
+HJ_TOOL_LAST_SYMBOLS(hjp)
+
+}  // extern "C"

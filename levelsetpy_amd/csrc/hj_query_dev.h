@@ -5,8 +5,10 @@
 // costate_points_kernel give for the same state.  At the end, the host function that fills the grid from the descriptor.
 #ifndef HJ_QUERY_DEV_H
 #define HJ_QUERY_DEV_H
+#ifndef __HIPCC_RTC__      // hipRTC (libhj_plant.so's run-time kernels, hj_plant.hip) brings the HIP device declarations itself
 #include <hip/hip_runtime.h>
 #include <cmath>
+#endif
 #include "hj_device.h"
 #include "../../include/hj_query.h"
 
@@ -199,7 +201,9 @@ __device__ __forceinline__ long long proj_base(const ProjArgs& A, long long o) {
 
 // ---------------------------------------------------------------------------------------------- host side
 // The descriptor as the kernels see it, with the checks both libraries make on it; total = the number of nodes.  Refusals go to
-// the including library's own error record: hj_tool_host.h comes before this header.
+// the including library's own error record: hj_tool_host.h comes before this header.  A translation unit generated for hipRTC
+// (HJ_RTC) is device code only and has no host side.
+#ifndef HJ_RTC
 #ifndef HJ_TOOL_HOST_H
 #error "include hj_tool_host.h before hj_query_dev.h"
 #endif
@@ -248,6 +252,7 @@ static int check_points(const GD* g, const QGrid& G, long long total, const void
 }
 
 static const char TOO_MANY[] = "too many (field, state) pairs for one launch";
+#endif  // HJ_RTC
 
 }  // namespace hjq
 #endif

@@ -1,7 +1,9 @@
 // Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip) and libhj_hiquery.so (hj_hiquery.hip): what does
 // not depend on the plant -- sgn, the RK4 step, and a trajectory from its first state to its last (the bisection over the stored
 // sets, the costate, the sub-steps).  One source, so a 5-D / 6-D trajectory is stepped by the statements a 2-D .. 4-D one is.
-// A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).
+// A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).  A plant with
+// more than two held values names a type of its own, Control, and takes it whole: controls(P, p, x, Control&), f(P, x, const
+// Control&, k) -- libhj_plant.so's PlantUser, compiled at run time (hj_plant.hip); its descriptor is whatever type the kernel hands on.
 // Include after hj_query_dev.h.
 #ifndef HJ_ROLLOUT_DEV_H
 #define HJ_ROLLOUT_DEV_H
@@ -20,23 +22,38 @@ __device__ __forceinline__ double sgn(double s) { return s >= 0.0 ? 1.0 : (s < 0
 // ---- the plants: controls(costate p, state x) -> (c0, c1), f(x; c0, c1) -> xdot.  One operation per statement.
 template <int ID> struct Plant;
 
+// What a step holds fixed: two scalars (the built-in plants), or the plant's own Control type.
+struct Control2 { double c0, c1; };
+template <typename...> struct void_of { using type = void; };
+template <typename PL, typename = void> struct control_of { using type = Control2; };
+template <typename PL> struct control_of<PL, typename void_of<typename PL::Control>::type> { using type = typename PL::Control; };
+
+template <typename PL, typename PD>
+__device__ __forceinline__ void plant_controls(const PD& P, const double* p, const double* x, Control2& c) { PL::controls(P, p, x, c.c0, c.c1); }
+template <typename PL, typename PD, typename CT>
+__device__ __forceinline__ void plant_controls(const PD& P, const double* p, const double* x, CT& c) { PL::controls(P, p, x, c); }
+template <typename PL, typename PD>
+__device__ __forceinline__ void plant_f(const PD& P, const double* x, const Control2& c, double* k) { PL::f(P, x, c.c0, c.c1, k); }
+template <typename PL, typename PD, typename CT>
+__device__ __forceinline__ void plant_f(const PD& P, const double* x, const CT& c, double* k) { PL::f(P, x, c, k); }
+
 // one classical RK4 step with the controls held, in the expression order of the Python systems' update_state
-template <typename PL>
-__device__ __forceinline__ void rk4(const hjr_plant& P, double* x, double dt, double c0, double c1) {
+template <typename PL, typename PD, typename CT>
+__device__ __forceinline__ void rk4(const PD& P, double* x, double dt, const CT& c) {
 #pragma clang fp contract(off)
     constexpr int N = PL::ND;
     double k1[N], k2[N], k3[N], k4[N], xa[N];
     const double h = 0.5 * dt;
-    PL::f(P, x, c0, c1, k1);
+    plant_f<PL>(P, x, c, k1);
 #pragma unroll
     for (int d = 0; d < N; ++d) { const double t = h * k1[d]; xa[d] = x[d] + t; }
-    PL::f(P, xa, c0, c1, k2);
+    plant_f<PL>(P, xa, c, k2);
 #pragma unroll
     for (int d = 0; d < N; ++d) { const double t = h * k2[d]; xa[d] = x[d] + t; }
-    PL::f(P, xa, c0, c1, k3);
+    plant_f<PL>(P, xa, c, k3);
 #pragma unroll
     for (int d = 0; d < N; ++d) { const double t = dt * k3[d]; xa[d] = x[d] + t; }
-    PL::f(P, xa, c0, c1, k4);
+    plant_f<PL>(P, xa, c, k4);
     const double sixth = dt / 6.0;
 #pragma unroll
     for (int d = 0; d < N; ++d) {
@@ -57,19 +74,24 @@ struct RolloutOut {
     int* status;
 };
 
-// The one-sided derivatives of a corner's stencil.  UpwindSolver: hj_device.h's upwind<>, what computeGradients runs up to 4-D;
-// hj_hiquery.hip has the 5-D / 6-D one.
+// The one-sided derivatives of a corner's stencil.  UpwindSolver: hj_device.h's upwind<>, what computeGradients runs up to 4-D.
 struct UpwindSolver {
     template <int SCHEME, typename T>
     __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind<SCHEME, T>(v, K, T(0), L, R); }
 };
+// UpwindHidim: computeGradients' at 5-D / 6-D (hidim_upwind_kernel), so that a corner costate has the bits it gives that node --
+// ENO2 / ENO3 with every operation rounded on its own, the as-shipped WENO5 by upwind<>.
+struct UpwindHidim {
+    template <int SCHEME, typename T>
+    __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind_lr_hidim<SCHEME, T>(v, K, L, R); }
+};
 
 // The body of a rollout kernel: the thread's trajectory (2^ND lanes per trajectory, this thread one corner of its cell).
 // Control flow is uniform inside a group and predicated across groups: see hj_rollout.hip.
-template <typename T, int SCHEME, typename PL, typename UP>
+template <typename T, int SCHEME, typename PL, typename UP, typename PD = hjr_plant>
 __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long long field_stride, int ntimes,
                                              const double* __restrict__ x0, long long M, const QGrid& G, const QStencil<T>& S,
-                                             int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O) {
+                                             int sub_samples, double dt_small, const PD& P, const RolloutOut& O) {
     constexpr int ND = PL::ND;                     // == G.ndim (checked by the host)
     constexpr int lanes = 1 << ND;                 // 4 .. 64: divides the wavefront, groups never straddle one
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -169,10 +191,11 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
         if (te_row && c == 0) te_row[it] = active ? tE : -1;
         if (!done) {
             for (int s = 0; s < sub_samples; ++s) {
-                double p[ND], c0, c1;
+                double p[ND];
+                typename control_of<PL>::type ctl;
                 costate_at(tE, p);
-                PL::controls(P, p, x, c0, c1);
-                rk4<PL>(P, x, dt_small, c0, c1);
+                plant_controls<PL>(P, p, x, ctl);
+                rk4<PL>(P, x, dt_small, ctl);
                 find();
             }
             len = it + 2;

@@ -3,7 +3,8 @@
 // compile step, the code-object cache on disk, the module launch and the lock.  Host code only; nothing here knows a kernel's argument block
 // or launch shape.  Everything is `static`: each library compiles a copy of its own (own loader handle, own counters, own lock).
 //
-// The includer defines HJ_RTC_FAIL (its library's  int fail(int code, const char* fmt, ...)) and HIP_TRY before the #include.
+// The includer defines HJ_RTC_FAIL (its library's  int fail(int code, const char* fmt, ...)) and HIP_TRY before the #include, and may
+// define HJ_RTC_WHAT, the noun its messages use for a registration (default "Hamiltonian").
 //
 // ---- code-object cache on disk: a registered expression is compiled once per (source, kernel headers, options), not once per
 // process.  Directory: $HJ_RTC_CACHE ("0" / "off" disables), else $XDG_CACHE_HOME/levelsetpy_amd, else $HOME/.cache/levelsetpy_amd;
@@ -28,6 +29,10 @@
 #include <string>
 #include <vector>
 #include <hip/hip_runtime.h>
+
+#ifndef HJ_RTC_WHAT
+#define HJ_RTC_WHAT "Hamiltonian"
+#endif
 
 namespace hj_rtc {
 
@@ -220,7 +225,7 @@ static int rtc_build(const Unit& unit, const std::string& src, const std::string
     if (e) {
         const std::string log = program_log(prog);
         (void)g_rtc.DestroyProgram(&prog);
-        return HJ_RTC_FAIL(HJ_EINVAL, "the Hamiltonian '%s' does not compile (%s):\n%s", what.c_str(), g_rtc.GetErrorString(e), log.c_str());
+        return HJ_RTC_FAIL(HJ_EINVAL, "the " HJ_RTC_WHAT " '%s' does not compile (%s):\n%s", what.c_str(), g_rtc.GetErrorString(e), log.c_str());
     }
     const char* lowered = nullptr;
     e = g_rtc.GetLoweredName(prog, name_expr.c_str(), &lowered);
@@ -269,7 +274,7 @@ static int rtc_compile_check(const std::string& src, const std::vector<std::stri
     std::string log;
     if (e) log = program_log(prog);
     (void)g_rtc.DestroyProgram(&prog);
-    if (e) return HJ_RTC_FAIL(HJ_EINVAL, "the Hamiltonian '%s' does not compile (%s):\n%s", what.c_str(), g_rtc.GetErrorString(e), log.c_str());
+    if (e) return HJ_RTC_FAIL(HJ_EINVAL, "the " HJ_RTC_WHAT " '%s' does not compile (%s):\n%s", what.c_str(), g_rtc.GetErrorString(e), log.c_str());
     return HJ_OK;
 }
 

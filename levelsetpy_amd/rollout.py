@@ -18,9 +18,10 @@ trajectory -- the bisection over the stored sets, the costates, the controls, th
 rollout_kernel (libhj_rollout.so, include/hj_rollout.h), and the result equals computeOptTraj's with that system's own
 methods bit for bit up to the device's sin / cos.  Plane5D and DubinsPair6D on a 5-D / 6-D grid take the same path in
 hi_rollout_kernel (libhj_hiquery.so, include/hj_hiquery.h), which compiles the trajectory's source at six axes; uMode and dMode
-are resolved as computeOptTraj resolves them.  Any other dynSys -- a foreign class, a subclass that overrides a
-protocol method, non-scalar bounds -- or derivative function takes a host loop: computeOptTraj on copy.copy(dynSys) once
-per state, padded the same way.
+are resolved as computeOptTraj resolves them.  A dynSys with a registered plant (plant.register_plant) runs in user_rollout_kernel
+(libhj_plant.so, include/hj_plant.h), the same trajectory compiled at run time around the user's controls and dynamics.  Any other
+dynSys -- a foreign class, a subclass that overrides a protocol method, non-scalar bounds -- or derivative function takes a
+host loop: computeOptTraj on copy.copy(dynSys) once per state, padded the same way.
 
 Parity UNPINNED: the reference's computeOptTraj cannot run (opt_traj.py), and it has no batched form.
 """
@@ -29,7 +30,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _ffi, _hffi, _rffi, _xffi
+from . import _ffi, _hffi, _pffi, _rffi, _xffi
 from .context import grid_bc, is_tensor, require_gpu
 from .dynamics import native_plant, native_plant_hi
 from .opt_traj import computeOptTraj, find_earliest_BRS_ind
@@ -61,7 +62,15 @@ def _why_host(dynSys, derivFunc, g):
     """None when the kernel covers this call, else the reason for the host loop."""
     nat = native_plant(dynSys) or native_plant_hi(dynSys)
     if nat is None:
-        return None, "%s has no native plant" % type(dynSys).__name__
+        from .plant import plant_of
+        user = plant_of(dynSys)                          # (registration, parameters): a plant registered at run time
+        if user is None:
+            return None, "%s has no native plant" % type(dynSys).__name__
+        if user[0].dim != g.dim:
+            return None, "%s has no native plant on a %d-D grid" % (type(dynSys).__name__, g.dim)
+        if point_scheme(derivFunc) is None:
+            return None, "derivFunc %s has no point kernel" % getattr(derivFunc, "__name__", derivFunc)
+        return user, None
     if (_hffi.HAM_DIMS if nat[0] in _hffi.HAM_DIMS else _rffi.PLANT_DIMS).get(nat[0]) != g.dim:
         return None, "%s has no native plant on a %d-D grid" % (type(dynSys).__name__, g.dim)
     if point_scheme(derivFunc) is None:
@@ -71,11 +80,15 @@ def _why_host(dynSys, derivFunc, g):
 
 def rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, want_te=False):
     """hjr_rollout on device tensors: `data` a contiguous (T,) + g.shape stack, `xs` an (M, dim) fp64 tensor, `plant` an
-    _rffi.Plant.  -> (traj (M, dim, T) fp64, length (M,) int32, tEarliest (M, T) int32 or None, status (M,) int32)."""
+    _rffi.Plant, or a _pffi.Plant for hjp_rollout / hjp_rollout_hi.
+    -> (traj (M, dim, T) fp64, length (M,) int32, tEarliest (M, T) int32 or None, status (M,) int32)."""
     torch = require_gpu()
     hi = _is_hi(g)                                   # 5-D / 6-D: hjx_rollout (libhj_hiquery.so), the same call on hjh_grid
     desc, N = (_descriptor_hi if hi else _descriptor)(g, _dtype_name(data))
-    ffi, call = (_xffi, _xffi.lib().hjx_rollout) if hi else (_rffi, _rffi.lib().hjr_rollout)
+    if isinstance(plant, _pffi.Plant):
+        ffi, call = _pffi, (_pffi.lib().hjp_rollout_hi if hi else _pffi.lib().hjp_rollout)
+    else:
+        ffi, call = (_xffi, _xffi.lib().hjx_rollout) if hi else (_rffi, _rffi.lib().hjr_rollout)
     T, stride = _fields(data, N)
     if xs.dim() != 2 or xs.shape[1] != g.dim:
         error('states must be an (M, %d) array' % g.dim)
@@ -152,10 +165,14 @@ def computeOptTrajs(g, data, tau, dynSys, x0s, extraArgs=None):
             error("uMode / dMode must be 'min' or 'max'")
         t = _device_data(data)
         xs = _device_states(x0, t.device)
-        plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
+        user = not isinstance(nat[0], int)
+        if user:
+            plant = _pffi.plant_descriptor(nat[0].plant_id, _MODES[uMode], _MODES[dMode or 'min'], nat[1])
+        else:
+            plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
         dtSmall = (tau[1] - tau[0]) / subSamples                 # exactly as computeOptTraj forms it
         trajs, lengths, te, status = rollout_states(g, t, xs, point_scheme(derivFunc), subSamples, dtSmall, plant, want_te)
-        _last_path = (_xffi if _is_hi(g) else _rffi).last_kernel()
+        _last_path = (_pffi if user else (_xffi if _is_hi(g) else _rffi)).last_kernel()
         if not tensors:
             trajs, lengths, status = (a.cpu().numpy() for a in (trajs, lengths, status))
             te = te.cpu().numpy() if te is not None else None
