@@ -160,3 +160,19 @@ LIB_PATH, lib, check, _ = bind("HJ_LIB", "libhj_mi355x.so", "hj", "hj_mi355x err
 def darr(values):
     values = [float(v) for v in values]
     return (C.c_double * max(1, len(values)))(*values)
+
+
+def grid_descriptor(cls, width, ndim, N, xmin, xlast, dx, bc, tz, dtype_name):
+    """A grid descriptor of struct class `cls` with room for `width` axes (hjq_grid: 4, hjh_grid: 6), unused axes neutral."""
+    g = cls()
+    g.ndim = int(ndim)
+    g.dtype = F64 if dtype_name == "float64" else F32
+    for d in range(width):
+        inside = d < ndim
+        g.N[d] = int(N[d]) if inside else 1
+        g.xmin[d] = float(xmin[d]) if inside else 0.0
+        g.xlast[d] = float(xlast[d]) if inside else 0.0
+        g.dx[d] = float(dx[d]) if inside else 1.0
+        g.bc[d] = int(bc[d]) if inside else 0
+        g.toward_zero[d] = int(tz[d]) if inside else 0
+    return g

@@ -53,18 +53,7 @@ LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_HIDIM_LIB", "libhj_hidim.so", 
 
 
 def grid_descriptor(ndim, N, xmin, xlast, dx, bc, tz, dtype_name):
-    g = Grid()
-    g.ndim = int(ndim)
-    g.dtype = _ffi.F64 if dtype_name == "float64" else _ffi.F32
-    for d in range(MAX_DIM):
-        inside = d < ndim
-        g.N[d] = int(N[d]) if inside else 1
-        g.xmin[d] = float(xmin[d]) if inside else 0.0
-        g.xlast[d] = float(xlast[d]) if inside else 0.0
-        g.dx[d] = float(dx[d]) if inside else 1.0
-        g.bc[d] = int(bc[d]) if inside else 0
-        g.toward_zero[d] = int(tz[d]) if inside else 0
-    return g
+    return _ffi.grid_descriptor(Grid, MAX_DIM, ndim, N, xmin, xlast, dx, bc, tz, dtype_name)
 
 
 def params(values):

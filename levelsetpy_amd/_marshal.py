@@ -68,15 +68,19 @@ def fields(t, N):
     error('data parameter does not agree in array size with grid')
 
 
-def descriptor(g, dtype_name):
-    """(hjq_grid of grid g for data of `dtype_name` ('float64' / 'float32', see dtype_name(t)), g's shape as a tuple)."""
+def _descriptor(ffi, g, dtype_name):
     N = [int(v) for v in np.asarray(g.N).ravel()]
     dx = [float(v) for v in np.asarray(g.dx).ravel()]
     vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
     bc, tz = grid_bc(g)
+    return ffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)
+
+
+def descriptor(g, dtype_name):
+    """(hjq_grid of grid g for data of `dtype_name` ('float64' / 'float32', see dtype_name(t)), g's shape as a tuple)."""
     if g.dim > _qffi.MAX_DIM:
         error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
-    return _qffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)
+    return _descriptor(_qffi, g, dtype_name)
 
 
 def descriptor_hi(g, dtype_name):
@@ -84,11 +88,7 @@ def descriptor_hi(g, dtype_name):
     if not _hffi.MIN_DIM <= g.dim <= _hffi.MAX_DIM:
         error('grid.dim must be %d..%d for the 5-D / 6-D queries (got %d): grids of more than %d dimensions have no device implementation'
               % (_hffi.MIN_DIM, _hffi.MAX_DIM, g.dim, _hffi.MAX_DIM))
-    N = [int(v) for v in np.asarray(g.N).ravel()]
-    dx = [float(v) for v in np.asarray(g.dx).ravel()]
-    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
-    bc, tz = grid_bc(g)
-    return _hffi.grid_descriptor(g.dim, N, [float(v[0]) for v in vs], [float(v[-1]) for v in vs], dx, bc, tz, dtype_name), tuple(N)
+    return _descriptor(_hffi, g, dtype_name)
 
 
 def is_hi(g):

@@ -4,8 +4,9 @@
 // This file holds NO kernel.  It keeps the table of registered plants, generates a translation unit per plant (plant_source:
 // HJ_QUERY_MAXD for the plant's dimension, hj_query_dev.h, hj_rollout_dev.h, PlantUser, the kernel), has hipRTC compile the
 // instantiation a launch needs -- lazily per (plant, element type, scheme, device), under hj_rtc_host.h's lock, through its disk
-// cache -- and launches it through the module API with one argument block (hj_plant_dev.h's RolloutArgs).  The library links
-// nothing of the other eleven.
+// cache -- and launches it through the module API with one argument block (hj_plant_dev.h's RolloutArgs).  The descriptor's and
+// the call's checks are the other rollout libraries': make_grid and fill_stencil of hj_query_dev.h at either width, check_rollout
+// of hj_rollout_dev.h.  The library links nothing of the other eleven.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstring>
@@ -112,51 +113,12 @@ static int user_kernel(UserPlant& u, bool f32, int scheme, hipFunction_t& fn) {
     return HJ_OK;
 }
 
-// the descriptor's checks (hj_query_dev.h's make_grid) and the block's grid and stencil fields; GD: hjq_grid or hjh_grid
 template <typename T, int MD, typename GD>
-static void fill_grid(const GD* g, RolloutArgs<T, MD>& A) {
-    long long total = 1;
-    for (int d = 0; d < MD; ++d) {
-        A.n[d] = 1; A.per[d] = 0; A.stride[d] = 0; A.xmin[d] = 0; A.xlast[d] = 0; A.dx[d] = 1;
-    }
-    for (int d = g->ndim - 1; d >= 0; --d) {
-        A.n[d] = (int)g->N[d];
-        A.per[d] = g->bc[d] == HJ_BC_PERIODIC;
-        A.stride[d] = total;
-        A.xmin[d] = g->xmin[d];
-        A.xlast[d] = g->xlast[d];
-        A.dx[d] = g->dx[d];
-        total *= g->N[d];
-    }
-    for (int d = 0; d < MD; ++d) {
-        A.km[d] = (d < g->ndim && g->toward_zero[d]) ? T(-1) : T(1);
-        hj::fill_stencil_constants<T>(A.dx[d], A.K[d]);
-    }
-}
-
-template <typename GD>
-static int check_grid(const GD* g, int mind, int maxd, long long& total) {
-    if (!g) return fail(HJ_EINVAL, "null grid descriptor");
-    if (g->ndim < mind || g->ndim > maxd) return fail(HJ_EINVAL, "ndim %d outside %d..%d", (int)g->ndim, mind, maxd);
-    if (g->dtype != HJ_F64 && g->dtype != HJ_F32) return fail(HJ_EINVAL, "unknown dtype %d", (int)g->dtype);
-    total = 1;
-    for (int d = g->ndim - 1; d >= 0; --d) {
-        if (g->N[d] < 1 || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range", d, (long long)g->N[d]);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d]) || !std::isfinite(g->xmin[d]) || !std::isfinite(g->xlast[d]))
-            return fail(HJ_EINVAL, "axis %d: dx must be positive, xmin / xlast finite", d);
-        total *= g->N[d];
-        if (total > (1ll << 40)) return fail(HJ_EINVAL, "grid too large");
-    }
-    return HJ_OK;
-}
-
-template <typename T, int MD, typename GD>
-static int launch(UserPlant& u, const GD* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t M,
+static int launch(UserPlant& u, const GD* g, const hjq::QGridT<MD>& G, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t M,
                   int sub_samples, double dt_small, const hjp_plant& P, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
                   hipStream_t stream) {
     unsigned blocks;
-    int rc = blocks_for((long long)M * (1ll << g->ndim), "too many trajectories for one launch", blocks);
+    int rc = blocks_for((long long)M * (1ll << G.ndim), hjr::TOO_MANY_TRAJ, blocks);
     if (rc) return rc;
     const bool f32 = sizeof(T) == 4;
     hipFunction_t fn = nullptr;
@@ -170,7 +132,8 @@ static int launch(UserPlant& u, const GD* g, int scheme, const void* data, int64
     A.ntimes = (int)ntimes;
     A.sub_samples = sub_samples;
     A.dt_small = dt_small;
-    fill_grid<T, MD>(g, A);
+    A.G = G;
+    hjq::fill_stencil(g, G, A.S);
     A.P = P;
     for (int k = u.nparams; k < HJP_PAR_SLOTS; ++k) A.P.params[k] = 0.0;
     A.traj = traj;
@@ -178,8 +141,7 @@ static int launch(UserPlant& u, const GD* g, int scheme, const void* data, int64
     A.t_earliest = t_earliest;
     A.status = status;
     if ((rc = hj_rtc::module_launch(fn, blocks, 256, 0, stream, &A, sizeof(A)))) return rc;
-    const std::string name = std::string("user_rollout_kernel<") + (f32 ? "float" : "double") + ", " + std::to_string(scheme) + ", PlantUser:" + u.name + ">";
-    launched(name.c_str());
+    launched(kernel_name("user_rollout_kernel", type_tag<T>::name(), {scheme}, (", PlantUser:" + u.name).c_str()).c_str());
     return HJ_OK;
 }
 
@@ -187,31 +149,25 @@ template <int MD, typename GD>
 static int rollout(const GD* g, int mind, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0, int64_t nstates,
                    int sub_samples, double dt_small, const hjp_plant* plant, double* traj, int32_t* length, int32_t* t_earliest, int32_t* status,
                    void* stream) {
+    hjq::QGridT<MD> G;
     long long total;
-    int rc = check_grid(g, mind, MD, total);
+    int rc = hjq::make_grid(g, G, total, mind);
     if (rc) return rc;
-    if (!plant) return fail(HJ_EINVAL, "null plant descriptor");
-    if (nstates < 0) return fail(HJ_EINVAL, "nstates must not be negative");
-    if (ntimes < 2 || ntimes > 0x7fffffffll) return fail(HJ_EINVAL, "ntimes %lld: a rollout needs at least two stored sets", (long long)ntimes);
-    if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
-    if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
-    if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
-    if ((rc = check_point_scheme(scheme, "rollout"))) return rc;
-    HJ_RTC_LOCK;
-    UserPlant* u = plant_of(plant->id);
-    if (!u) return fail(HJ_EINVAL, "unknown plant id %d: nothing is registered under it (hjp_plant_register)", (int)plant->id);
-    if (u->ndim != g->ndim) return fail(HJ_EINVAL, "plant '%s' has %d states, the grid %d dimensions", u->name.c_str(), u->ndim, (int)g->ndim);
-    if (plant->nparams != u->nparams) return fail(HJ_EINVAL, "plant '%s' takes %d parameters, the descriptor has %d", u->name.c_str(), u->nparams, (int)plant->nparams);
-    if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
-        return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
-    for (int d = 0; d < g->ndim; ++d)
-        if (g->N[d] < HJ_STENCIL) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, (int)g->N[d], HJ_STENCIL);
-    if (nstates == 0) return HJ_OK;
-    if (!data || !x0 || !traj || !length || !status) return fail(HJ_EINVAL, "null argument");
+    HJ_RTC_LOCK;                    // from the look at the registry (inside check_rollout) to the launch
+    UserPlant* u = nullptr;
+    bool go;
+    rc = hjr::check_rollout(G, total, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, plant, traj, length, status, [&]() {
+        u = plant_of(plant->id);
+        if (!u) return fail(HJ_EINVAL, "unknown plant id %d: nothing is registered under it (hjp_plant_register)", (int)plant->id);
+        if (u->ndim != G.ndim) return fail(HJ_EINVAL, "plant '%s' has %d states, the grid %d dimensions", u->name.c_str(), u->ndim, G.ndim);
+        if (plant->nparams != u->nparams) return fail(HJ_EINVAL, "plant '%s' takes %d parameters, the descriptor has %d", u->name.c_str(), u->nparams, (int)plant->nparams);
+        return (int)HJ_OK;
+    }, go);
+    if (rc || !go) return rc;
     if (g->dtype == HJ_F64)
-        return launch<double, MD>(*u, g, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest,
+        return launch<double, MD>(*u, g, G, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest,
                                   status, (hipStream_t)stream);
-    return launch<float, MD>(*u, g, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest, status,
+    return launch<float, MD>(*u, g, G, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, traj, length, t_earliest, status,
                              (hipStream_t)stream);
 }
 

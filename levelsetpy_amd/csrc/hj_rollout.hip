@@ -18,9 +18,11 @@
 namespace hjr {
 
 using hjq::make_grid;
+using hjq::fill_stencil;
 using namespace hj_tool;
 
-// sgn, rk4, RolloutOut and the trajectory itself (rollout_body): hj_rollout_dev.h, shared with libhj_hiquery.so
+// sgn, rk4, RolloutOut, the trajectory itself (rollout_body) and the entry point's checks (check_rollout): hj_rollout_dev.h, shared
+// with libhj_hiquery.so and libhj_plant.so
 
 template <> struct Plant<HJ_HAM_DUBINS_REL> {
     static constexpr int ND = 3;
@@ -118,19 +120,15 @@ __global__ __launch_bounds__(256) void rollout_kernel(const T* __restrict__ data
 // ---------------------------------------------------------------------------------------------- host side
 template <typename T, int SCHEME, int PLANT>
 static int launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
-                  int64_t M, int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O, hipStream_t stream,
-                  const char* name) {
+                  int64_t M, int sub_samples, double dt_small, const hjr_plant& P, const RolloutOut& O, hipStream_t stream) {
     QStencil<T> S;
-    for (int d = 0; d < MAXD; ++d) {
-        S.km[d] = (d < G.ndim && g->toward_zero[d]) ? T(-1) : T(1);
-        hj::fill_stencil_constants<T>(G.dx[d], S.K[d]);
-    }
+    fill_stencil(g, G, S);
     unsigned blocks;
-    int rc = blocks_for((long long)M * (1ll << G.ndim), "too many trajectories for one launch", blocks);
+    int rc = blocks_for((long long)M * (1ll << G.ndim), TOO_MANY_TRAJ, blocks);
     if (rc) return rc;
     hipLaunchKernelGGL((rollout_kernel<T, SCHEME, PLANT>), dim3(blocks), dim3(256), 0, stream, (const T*)data,
                        (long long)field_stride, (int)ntimes, x0, (long long)M, G, S, sub_samples, dt_small, P, O);
-    return launch_done(name);
+    return launch_done(kernel_name("rollout_kernel", type_tag<T>::name(), {SCHEME, PLANT}).c_str());
 }
 
 }  // namespace hjr
@@ -146,43 +144,24 @@ int hjr_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes,
     long long total;
     int rc = make_grid(g, G, total);
     if (rc) return rc;
-    if (!plant) return fail(HJ_EINVAL, "null plant descriptor");
-    if (nstates < 0) return fail(HJ_EINVAL, "nstates must not be negative");
-    if (ntimes < 2 || ntimes > 0x7fffffffll) return fail(HJ_EINVAL, "ntimes %lld: a rollout needs at least two stored sets", (long long)ntimes);
-    if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
-    if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
-    if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
-    if ((rc = check_point_scheme(scheme, "rollout"))) return rc;
-    const int nd = ham_ndim(plant->id);
-    if (nd == 0) return fail(HJ_EUNSUPPORTED, "plant %d has no rollout kernel", (int)plant->id);
-    if (nd != G.ndim) return fail(HJ_EINVAL, "plant %d has %d states, the grid %d dimensions", (int)plant->id, nd, G.ndim);
-    if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
-        return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
-    for (int d = 0; d < G.ndim; ++d)
-        if (G.n[d] < HJ_STENCIL) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], HJ_STENCIL);
-    if (nstates == 0) return HJ_OK;
-    if (!data || !x0 || !traj || !length || !status) return fail(HJ_EINVAL, "null argument");
+    bool go;
+    rc = check_rollout(G, total, scheme, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, plant, traj, length, status, [&]() {
+        const int nd = ham_ndim(plant->id);
+        if (nd == 0) return fail(HJ_EUNSUPPORTED, "plant %d has no rollout kernel", (int)plant->id);
+        if (nd != G.ndim) return fail(HJ_EINVAL, "plant %d has %d states, the grid %d dimensions", (int)plant->id, nd, G.ndim);
+        return (int)HJ_OK;
+    }, go);
+    if (rc || !go) return rc;
     const RolloutOut O{traj, length, t_earliest, status};
-    hipStream_t s = (hipStream_t)stream;
-#define HJR_GO(T, SCH, PL) \
-    return launch<T, SCH, PL>(g, G, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, O, s, "rollout_kernel<" #T ", " #SCH ", " #PL ">")
-#define HJR_PLANTS(T, SCH)                     \
-    do {                                       \
-        if (plant->id == 0) HJR_GO(T, SCH, 0); \
-        if (plant->id == 1) HJR_GO(T, SCH, 1); \
-        HJR_GO(T, SCH, 2);                     \
-    } while (0)
     static_assert(HJ_HAM_DUBINS_REL == 0 && HJ_HAM_DOUBLE_INTEGRATOR == 1 && HJ_HAM_DOUBLE_PENDULUM == 2, "plant ids name the kernels");
-    if (g->dtype == HJ_F64) {
-        if (scheme == HJ_ENO2) HJR_PLANTS(double, 0);
-        if (scheme == HJ_ENO3) HJR_PLANTS(double, 1);
-        HJR_PLANTS(double, 3);
-    }
-    if (scheme == HJ_ENO2) HJR_PLANTS(float, 0);
-    if (scheme == HJ_ENO3) HJR_PLANTS(float, 1);
-    HJR_PLANTS(float, 3);
-#undef HJR_PLANTS
-#undef HJR_GO
+    return dispatch(g->dtype, scheme, [&](auto t, auto sch) {
+        using T = typename decltype(t)::type;
+        constexpr int SCH = decltype(sch)::value;
+        hipStream_t s = (hipStream_t)stream;
+        if (plant->id == 0) return launch<T, SCH, 0>(g, G, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, O, s);
+        if (plant->id == 1) return launch<T, SCH, 1>(g, G, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, O, s);
+        return launch<T, SCH, 2>(g, G, data, ntimes, field_stride, x0, nstates, sub_samples, dt_small, *plant, O, s);
+    });
 }
 
 HJ_TOOL_LAST_SYMBOLS(hjr)

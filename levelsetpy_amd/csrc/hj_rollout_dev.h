@@ -1,6 +1,7 @@
-// Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip) and libhj_hiquery.so (hj_hiquery.hip): what does
-// not depend on the plant -- sgn, the RK4 step, and a trajectory from its first state to its last (the bisection over the stored
-// sets, the costate, the sub-steps).  One source, so a 5-D / 6-D trajectory is stepped by the statements a 2-D .. 4-D one is.
+// Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip), libhj_hiquery.so (hj_hiquery.hip) and the ones
+// libhj_plant.so has hipRTC compile (hj_plant.hip): what does not depend on the plant -- sgn, the RK4 step, and a trajectory from
+// its first state to its last (the bisection over the stored sets, the costate, the sub-steps).  One source, so a 5-D / 6-D
+// trajectory is stepped by the statements a 2-D .. 4-D one is.  At the end, the host side the three share: check_rollout.
 // A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).  A plant with
 // more than two held values names a type of its own, Control, and takes it whole: controls(P, p, x, Control&), f(P, x, const
 // Control&, k) -- libhj_plant.so's PlantUser, compiled at run time (hj_plant.hip); its descriptor is whatever type the kernel hands on.
@@ -15,6 +16,8 @@ namespace hjr {
 using hjq::MAXD;
 using hjq::QGrid;
 using hjq::QStencil;
+using hjq::UpwindSolver;      // the one-sided derivatives of a corner's stencil up to 4-D, and
+using hjq::UpwindHidim;       // at 5-D / 6-D: hj_query_dev.h
 
 // +1 for s >= 0, -1 for s < 0, NaN for NaN: an exact zero is deterministic, a NaN costate poisons the state
 __device__ __forceinline__ double sgn(double s) { return s >= 0.0 ? 1.0 : (s < 0.0 ? -1.0 : __builtin_nan("")); }
@@ -74,18 +77,6 @@ struct RolloutOut {
     int* status;
 };
 
-// The one-sided derivatives of a corner's stencil.  UpwindSolver: hj_device.h's upwind<>, what computeGradients runs up to 4-D.
-struct UpwindSolver {
-    template <int SCHEME, typename T>
-    __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind<SCHEME, T>(v, K, T(0), L, R); }
-};
-// UpwindHidim: computeGradients' at 5-D / 6-D (hidim_upwind_kernel), so that a corner costate has the bits it gives that node --
-// ENO2 / ENO3 with every operation rounded on its own, the as-shipped WENO5 by upwind<>.
-struct UpwindHidim {
-    template <int SCHEME, typename T>
-    __device__ static __forceinline__ void lr(const T* v, const T* K, T& L, T& R) { hj::upwind_lr_hidim<SCHEME, T>(v, K, L, R); }
-};
-
 // The body of a rollout kernel: the thread's trajectory (2^ND lanes per trajectory, this thread one corner of its cell).
 // Control flow is uniform inside a group and predicated across groups: see hj_rollout.hip.
 template <typename T, int SCHEME, typename PL, typename UP, typename PD = hjr_plant>
@@ -128,7 +119,8 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
         const double v = hjq::group_sum(p, used, lanes);
         return inside ? v : nan;
     };
-    // grad V[f](x) in fp64: costate_points_kernel's `costate`
+    // grad V[f](x) in fp64: costate_points_kernel's `costate`.  The middle block is hjq::corner_derivs' statements, written out: calling it
+    // here costs the 4-D kernels two VGPRs and 36 bytes of scratch (profiles/refactor_query_rollout.txt).
     auto costate_at = [&](int f, double* p) {
         T cC[ND];
 #pragma unroll
@@ -212,6 +204,38 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
         O.status[m] = left ? HJR_LEFT_GRID : (reached ? HJR_REACHED : HJR_EXHAUSTED);
     }
 }
+
+// ---------------------------------------------------------------------------------------------- host side
+#ifndef HJ_RTC
+// The checks of a rollout entry point (hjr_rollout, hjx_rollout, hjp_rollout / hjp_rollout_hi) after make_grid, in the order the
+// refusals are documented in.  plant_checks(): what the library asks of its own plants, between the scheme and the modes.
+// go: false where the call is in order and there is nothing to launch (no state).
+template <int MD, typename PD, typename F>
+static int check_rollout(const hjq::QGridT<MD>& G, long long total, int scheme, const void* data, int64_t ntimes, int64_t field_stride,
+                         const double* x0, int64_t nstates, int sub_samples, double dt_small, const PD* plant, const void* traj,
+                         const void* length, const void* status, F&& plant_checks, bool& go) {
+    using hj_tool::fail;
+    go = false;
+    if (!plant) return fail(HJ_EINVAL, "null plant descriptor");
+    if (nstates < 0) return fail(HJ_EINVAL, "nstates must not be negative");
+    if (ntimes < 2 || ntimes > 0x7fffffffll) return fail(HJ_EINVAL, "ntimes %lld: a rollout needs at least two stored sets", (long long)ntimes);
+    if (sub_samples < 1) return fail(HJ_EINVAL, "sub_samples must be positive");
+    if (!std::isfinite(dt_small)) return fail(HJ_EINVAL, "dt_small must be finite");
+    if (field_stride < total) return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    int rc = hj_tool::check_point_scheme(scheme, "rollout");
+    if (rc || (rc = plant_checks())) return rc;
+    if ((plant->u_mode != HJR_MODE_MIN && plant->u_mode != HJR_MODE_MAX) || (plant->d_mode != HJR_MODE_MIN && plant->d_mode != HJR_MODE_MAX))
+        return fail(HJ_EINVAL, "u_mode / d_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
+    for (int d = 0; d < G.ndim; ++d)
+        if (G.n[d] < HJ_STENCIL) return fail(HJ_EINVAL, "grid too small along dim %d (N=%d, need %d)", d, G.n[d], HJ_STENCIL);
+    if (nstates == 0) return HJ_OK;
+    if (!data || !x0 || !traj || !length || !status) return fail(HJ_EINVAL, "null argument");
+    go = true;
+    return HJ_OK;
+}
+
+static const char TOO_MANY_TRAJ[] = "too many trajectories for one launch";
+#endif  // HJ_RTC
 
 }  // namespace hjr
 #endif

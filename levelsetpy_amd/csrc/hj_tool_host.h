@@ -1,5 +1,6 @@
-// Host layer of the stateless libraries (libhj_query.so, libhj_surface.so, libhj_ttr.so, libhj_rollout.so, libhj_batch.so, libhj_shapes.so, libhj_decomp.so, libhj_eikonal.so, libhj_hidim.so, libhj_hiquery.so): the
-// error text, the record of the kernels the last successful call launched, and the argument checks more than one of them makes.
+// Host layer of the stateless libraries (libhj_query.so, libhj_surface.so, libhj_ttr.so, libhj_rollout.so, libhj_batch.so, libhj_shapes.so, libhj_decomp.so, libhj_eikonal.so, libhj_hidim.so, libhj_hiquery.so, libhj_plant.so): the
+// error text, the record of the kernels the last successful call launched, the argument checks more than one of them makes, and the
+// (dtype, scheme) dispatch of the point and rollout kernels.
 // Host code only.  Every one of these libraries is ONE translation unit that includes this header once, so the `static
 // thread_local` records below are that library's own: a refusal in libhj_query.so leaves hjt_last_error() as it was.
 // (libhj_mi355x.so has a record of its own, shared by its objects: hj_host.h.)
@@ -11,7 +12,9 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/hj_mi355x.h"
 
@@ -70,6 +73,30 @@ static int check_point_scheme(int scheme, const char* kind) {
     if (scheme != HJ_ENO2 && scheme != HJ_ENO3 && scheme != HJ_WENO5_ASSHIPPED)
         return fail(HJ_EUNSUPPORTED, "scheme %d has no %s kernel (ENO2, ENO3, as-shipped WENO5 only)", scheme, kind);
     return HJ_OK;
+}
+
+// ---- (dtype, scheme) -> the template arguments of a point or rollout kernel.  `f` is a generic lambda: f(type_tag<T>,
+// std::integral_constant<int, SCHEME>) for the element type of a checked dtype and a scheme check_point_scheme let through.
+template <typename T> struct type_tag {
+    using type = T;
+    static const char* name() { return sizeof(T) == 8 ? "double" : "float"; }
+};
+template <int V> using int_c = std::integral_constant<int, V>;
+
+template <typename F> static int dispatch(int dtype, int scheme, F&& f) {
+    auto schemes = [&](auto t) {
+        if (scheme == HJ_ENO2) return f(t, int_c<HJ_ENO2>{});
+        if (scheme == HJ_ENO3) return f(t, int_c<HJ_ENO3>{});
+        return f(t, int_c<HJ_WENO5_ASSHIPPED>{});
+    };
+    return dtype == HJ_F64 ? schemes(type_tag<double>{}) : schemes(type_tag<float>{});
+}
+
+// what launch_done records: "kernel<double, 0, 2>" from the kernel's name, its element type and its integer arguments
+static std::string kernel_name(const char* kernel, const char* type, std::initializer_list<int> ints, const char* tail = "") {
+    std::string s = std::string(kernel) + "<" + type;
+    for (int v : ints) s += ", " + std::to_string(v);
+    return s + tail + ">";
 }
 
 // state dimension of a built-in system, 0 for any other id

@@ -104,12 +104,14 @@ def test_the_makefile_builds_and_cleans_the_library():
 
 
 def test_one_source_for_the_arithmetic():
-    """locate, corner, interp_value, gather_axis, group_sum, the RK4 step, sgn and the trajectory are defined once, in the two
-    shared headers, and restated by none of the translation units that use them."""
+    """locate, corner, interp_value, gather_axis, group_sum, a corner's derivatives, the bodies of the costate and projection
+    kernels, the RK4 step, sgn and the trajectory are defined once, in the two shared headers, and restated by none of the
+    translation units that use them; so are the host side's make_grid, fill_stencil and the rollout checks."""
     src = lambda n: open(os.path.join(ROOT, "levelsetpy_amd", "csrc", n)).read()      # noqa: E731
     qdev, rdev = src("hj_query_dev.h"), src("hj_rollout_dev.h")
-    users = [src(n) for n in ("hj_query.hip", "hj_rollout.hip", "hj_decomp.hip", "hj_hiquery.hip")]
-    for fn in ("locate", "corner", "interp_value", "gather_axis", "group_sum", "proj_base"):
+    users = [src(n) for n in ("hj_query.hip", "hj_rollout.hip", "hj_decomp.hip", "hj_hiquery.hip", "hj_plant.hip")]
+    for fn in ("locate", "corner", "interp_value", "gather_axis", "group_sum", "proj_base", "corner_derivs", "costate_body", "proj_loops",
+               "project_body"):
         pat = r"^__device__ __forceinline__ \w[\w ]* %s\(" % fn
         assert len(re.findall(pat, qdev, re.M)) == 1, fn
         assert not any(re.search(pat, u, re.M) for u in users), fn
@@ -117,6 +119,16 @@ def test_one_source_for_the_arithmetic():
         pat = r"^__device__ __forceinline__ \w+ %s\(" % fn
         assert len(re.findall(pat, rdev, re.M)) == 1, fn
         assert not any(re.search(pat, u, re.M) for u in users), fn
+    for fn, home in (("make_grid", qdev), ("fill_stencil", qdev), ("check_rollout", rdev)):
+        pat = r"^static \w+ %s\(" % fn
+        assert len(re.findall(pat, home, re.M)) == 1 and len(re.findall(pat, qdev + rdev, re.M)) == 1, fn
+        assert not any(re.search(pat, u, re.M) for u in users), fn
+    # the checks' texts, too: each stands once, and in none of the five files
+    for text in ("out of range", "grid too large", "a rollout needs at least two stored sets", "u_mode / d_mode must be", "unknown projection"):
+        assert (qdev + rdev).count(text) == 1 and not any(text in u for u in users), text
+    # no costate or projection loop outside hj_query_dev.h: the kernels of the two libraries are frames around the bodies
+    for u in users:
+        assert "gather_axis<" not in u and "acc.take(" not in u and "static_assert(MAXD ==" not in u
     hi = src("hj_hiquery.hip")
     assert "#define HJ_QUERY_MAXD 6" in hi and '#include "hj_query_dev.h"' in hi and '#include "hj_rollout_dev.h"' in hi
     assert "HJ_QUERY_MAXD HJ_MAX_DIM" in qdev                                       # every other library compiles it at 4

@@ -1,4 +1,4 @@
-"""CPU-only: the host layer the five stateless libraries share (levelsetpy_amd/csrc/hj_tool_host.h, levelsetpy_amd/_ffi.bind).
+"""CPU-only: the host layer the stateless libraries share (levelsetpy_amd/csrc/hj_tool_host.h, levelsetpy_amd/_ffi.bind).
 
   * every argument check of tests/tool_lib_cases.py: the return code and a word of <prefix>_last_error().  Every data pointer
     is null and every check comes before the first HIP call, so no device is touched;
@@ -86,7 +86,9 @@ REQUIRED = {"query": ["hjq_interp_points", "hjq_costate_points", "hjq_project_mi
             "surface": ["hjs_workspace_size", "hjs_count", "hjs_emit"],
             "ttr": ["hjt_ttr_init", "hjt_ttr_update", "hjt_ttr_from_stack"],
             "rollout": ["hjr_rollout"],
-            "batch": ["hjb_step_bounds", "hjb_substep", "hjb_integrate"]}
+            "batch": ["hjb_step_bounds", "hjb_substep", "hjb_integrate"],
+            "hiquery": ["hjx_interp_points", "hjx_costate_points", "hjx_project_minmax", "hjx_rollout"],
+            "plant": ["hjp_plant_register", "hjp_rollout", "hjp_rollout_hi"]}
 
 
 def header_code(lib_name):

@@ -1,9 +1,9 @@
-"""The argument checks of the five stateless libraries (libhj_query / surface / ttr / rollout / batch .so) as data: calls that
-are refused, or accepted as "nothing to do", before the first HIP call -- so they run on a machine without a GPU.
+"""The argument checks of seven stateless libraries (libhj_query / surface / ttr / rollout / batch / hiquery / plant .so) as data:
+calls that are refused, or accepted as "nothing to do", before the first HIP call -- so they run on a machine without a GPU.
 
 Every case is (library, id, function, arguments, return code, word of <prefix>_last_error()).  An argument is an int, a float,
 None (a null pointer: every data pointer is null, so no case can reach a launch), FAKE (a non-null address where a check wants
-one: it is only compared with null, never read) or a Grid / Plant / Tables spec below, passed by address.
+one: it is only compared with null, never read) or a Grid / Plant / UserPlant / Tables spec below, passed by address.
 tests/test_tool_libs_host.py asserts the cases through ctypes; tools/tool_lib_refusals.py dumps code and whole message of every
 call (to compare two builds of the libraries) and writes the same calls as a stand-alone C++ program (for the host sanitizers)."""
 import ctypes as C
@@ -12,20 +12,23 @@ import math
 OK, EINVAL, EUNSUPPORTED = 0, -1, -3
 ENO2, WENO5 = 0, 2
 DUBINS, INTEGRATOR, USER = 0, 1, 100
+PLANE5D, PAIR6D = 50, 51
 NAN = float("nan")
 FAKE = "fake"                     # (void*)0x1000
 
-LIBS = {"query": "hjq", "surface": "hjs", "ttr": "hjt", "rollout": "hjr", "batch": "hjb"}
+LIBS = {"query": "hjq", "surface": "hjs", "ttr": "hjt", "rollout": "hjr", "batch": "hjb", "hiquery": "hjx", "plant": "hjp"}
 
 
 class Grid:
-    """hjq_grid by value: n nodes per axis from 0 with spacing 0.1, extrapolated; `put` overwrites (field, axis 0) entries."""
-    def __init__(self, ndim, n=8, dtype=0, **put):
-        self.ndim, self.dtype = ndim, dtype
-        self.N, self.xmin, self.xlast = [n] * 4, [0.0] * 4, [0.1 * (n - 1)] * 4
-        self.dx, self.bc, self.toward_zero = [0.1] * 4, [0] * 4, [0] * 4
+    """hjq_grid (width 4) or hjh_grid (width 6) by value: n nodes per axis from 0 with spacing 0.1, extrapolated; `put` overwrites
+    (field, axis 0) entries, or with a list the leading ones."""
+    def __init__(self, ndim, n=8, dtype=0, width=4, **put):
+        self.ndim, self.dtype, self.width = ndim, dtype, width
+        self.N, self.xmin, self.xlast = [n] * width, [0.0] * width, [0.1 * (n - 1)] * width
+        self.dx, self.bc, self.toward_zero = [0.1] * width, [0] * width, [0] * width
         for k, v in put.items():
-            getattr(self, k)[0] = v
+            v = v if isinstance(v, list) else [v]
+            getattr(self, k)[:len(v)] = v
 
 
 class Plant:
@@ -34,15 +37,23 @@ class Plant:
         self.id = id
 
 
+class UserPlant(Plant):
+    """hjp_plant: both modes min, no parameter."""
+
+
 class Tables:
     """hjb_tables with every coordinate and aux table at FAKE."""
 
 
-def grid_variants(ndim, too_few):
-    """(id, Grid or None, word of the refusal the table of descriptor cases expects from query / rollout / surface)."""
-    return [("null", None, "null"), ("ndim0", Grid(0), "ndim"), ("ndim5", Grid(5), "ndim"), ("dtype7", Grid(ndim, dtype=7), "dtype"),
-            ("N0", Grid(ndim, N=0), "N[0]")] + [("N%d" % n, Grid(ndim, N=n), "N[0]") for n in too_few] + [
-            ("bc9", Grid(ndim, bc=9), "boundary"), ("dx0", Grid(ndim, dx=0.0), "dx"), ("dxnan", Grid(ndim, dx=NAN), "dx")]
+def grid_variants(ndim, too_few, width=4, bad_ndim=(0, 5)):
+    """(id, Grid or None, word of the refusal the table of descriptor cases expects from query / rollout / surface / hiquery / plant).
+    toolarge: 2^30 nodes on each of three axes, whose product does not fit 64 bits (only ndim >= 3 has three axes)."""
+    def G(nd, **kw):
+        return Grid(nd, width=width, **kw)
+    return [("null", None, "null")] + [("ndim%d" % nd, G(nd), "ndim") for nd in bad_ndim] + [
+            ("dtype7", G(ndim, dtype=7), "dtype"), ("N0", G(ndim, N=0), "N[0]")] + [("N%d" % n, G(ndim, N=n), "N[0]") for n in too_few] + [
+            ("bc9", G(ndim, bc=9), "boundary"), ("dx0", G(ndim, dx=0.0), "dx"), ("dxnan", G(ndim, dx=NAN), "dx"),
+            ("toolarge", G(max(ndim, 3), N=[1 << 30] * 3), "too large")]
 
 
 def cases():
@@ -70,7 +81,10 @@ def cases():
                 ("emit", [g, None, 1, 0, 0.0, None, 0, None, None, None, None])]
     for cid, g, word in grid_variants(2, (1,)):
         for fn, args in surface(g):
-            add("surface", "%s-%s" % (fn, cid), fn, args, EINVAL, "null" if cid == "bc9" else word)
+            if cid == "toolarge":         # the library's own cap, tested axis by axis: more than 2^32 - 256 nodes have no kernel
+                add("surface", "%s-%s" % (fn, cid), fn, args, EUNSUPPORTED, "more than 2^32")
+            else:
+                add("surface", "%s-%s" % (fn, cid), fn, args, EINVAL, "null" if cid == "bc9" else word)
     for nd in (1, 4):
         for fn, args in surface(Grid(nd)):
             add("surface", "%s-ndim%d" % (fn, nd), fn, args, EUNSUPPORTED, "2-D and 3-D")
@@ -125,6 +139,48 @@ def cases():
     for fn, args in batch(Grid(3)):
         add("batch", "%s-nulldata" % fn, fn, args, EINVAL, "null argument")
     add("batch", "nan_flags-dtype7", "nan_flags", [7, None, 1, 1, None, None], EINVAL, "dtype")
+
+    # ---- hiquery: the entry points of query and rollout on a 5-D grid of six-axis descriptors; the plane on it
+    def G5(**kw):
+        return Grid(5, width=6, **kw)
+
+    def hiquery(g, scheme=ENO2, costate=None):
+        return [(fn, args) for fn, args in query(g, scheme, costate)]
+
+    def hirollout(g, scheme=ENO2, plant=Plant(PLANE5D), nstates=1):
+        return ["rollout", [g, scheme, None, 2, 8 ** 5, None, nstates, 4, 0.01, plant, None, None, None, None, None]]
+    for cid, g, word in grid_variants(5, (), 6, (4, 7)):
+        for fn, args in hiquery(g) + [tuple(hirollout(g))]:
+            add("hiquery", "%s-%s" % (fn, cid), fn, args, EINVAL, word)
+    for fn, args in hiquery(G5()):
+        add("hiquery", "%s-nulldata" % fn, fn, args, EINVAL, "null")
+    for sch in (WENO5, 9):
+        add("hiquery", "costate_points-scheme%d" % sch, *hiquery(G5(), sch, FAKE)[1], EUNSUPPORTED, "scheme")
+        add("hiquery", "rollout-scheme%d" % sch, *hirollout(G5(), sch), EUNSUPPORTED, "scheme")
+    add("hiquery", "rollout-nullplant", *hirollout(G5(), plant=None), EINVAL, "null plant")
+    add("hiquery", "rollout-plant6d", *hirollout(G5(), plant=Plant(PAIR6D)), EINVAL, "6 states")
+    add("hiquery", "rollout-solverplant", *hirollout(G5(), plant=Plant(DUBINS)), EUNSUPPORTED, "plant 0")
+    add("hiquery", "rollout-N2", *hirollout(G5(N=2)), EINVAL, "too small")
+    add("hiquery", "rollout-nulldata", *hirollout(G5()), EINVAL, "null argument")
+    add("hiquery", "rollout-nostates", *hirollout(G5(), nstates=0), OK)
+
+    # ---- plant: both entry points up to the look at the registry -- id 5 is below HJP_PLANT_BASE, so nothing answers to it
+    # whatever else the process has registered
+    def plant(hi, g, scheme=ENO2, p=UserPlant(5), nstates=1, ntimes=2, sub=4, dt=0.01, stride=None):
+        stride = (8 ** 5 if hi else 64) if stride is None else stride
+        return ["rollout_hi" if hi else "rollout", [g, scheme, None, ntimes, stride, None, nstates, sub, dt, p, None, None, None, None, None]]
+    for hi, nd, width, bad in ((False, 2, 4, (1, 5)), (True, 5, 6, (4, 7))):
+        def G(**kw):
+            return Grid(nd, width=width, **kw)
+        fn = plant(hi, None)[0]
+        for cid, g, word in grid_variants(nd, (), width, bad):
+            add("plant", "%s-%s" % (fn, cid), *plant(hi, g), EINVAL, word)
+        for cid, kw, rc, word in (("nullplant", dict(p=None), EINVAL, "null plant"), ("negative", dict(nstates=-1), EINVAL, "negative"),
+                                  ("oneset", dict(ntimes=1), EINVAL, "two stored sets"), ("sub0", dict(sub=0), EINVAL, "sub_samples"),
+                                  ("dtnan", dict(dt=NAN), EINVAL, "dt_small"), ("stride", dict(stride=10), EINVAL, "field_stride"),
+                                  ("scheme2", dict(scheme=WENO5), EUNSUPPORTED, "scheme"), ("scheme9", dict(scheme=9), EUNSUPPORTED, "scheme"),
+                                  ("unknownplant", {}, EINVAL, "unknown plant id 5")):
+            add("plant", "%s-%s" % (fn, cid), *plant(hi, G(), **kw), rc, word)
     return out
 
 
@@ -133,24 +189,26 @@ CASES = cases()
 
 # ------------------------------------------------------------------------------------------ through ctypes
 def modules():
-    from levelsetpy_amd import _bffi, _qffi, _rffi, _sffi, _tffi
-    return {"query": _qffi, "surface": _sffi, "ttr": _tffi, "rollout": _rffi, "batch": _bffi}
+    from levelsetpy_amd import _bffi, _pffi, _qffi, _rffi, _sffi, _tffi, _xffi
+    return {"query": _qffi, "surface": _sffi, "ttr": _tffi, "rollout": _rffi, "batch": _bffi, "hiquery": _xffi, "plant": _pffi}
 
 
 def _ctypes_arg(a, keep):
-    from levelsetpy_amd import _bffi, _qffi, _rffi
+    from levelsetpy_amd import _bffi, _hffi, _pffi, _qffi, _rffi
     if a is FAKE:
         return 0x1000
     if isinstance(a, list):
         keep.append((C.c_int64 * len(a))(*a))
         return keep[-1]
     if isinstance(a, Grid):
-        g = _qffi.Grid()
+        g = (_qffi if a.width == 4 else _hffi).Grid()
         g.ndim, g.dtype = a.ndim, a.dtype
         for k in ("N", "xmin", "xlast", "dx", "bc", "toward_zero"):
-            for d in range(4):
+            for d in range(a.width):
                 getattr(g, k)[d] = getattr(a, k)[d]
         keep.append(g)
+    elif isinstance(a, UserPlant):
+        keep.append(_pffi.plant_descriptor(a.id, 0, 0, []))
     elif isinstance(a, Plant):
         keep.append(_rffi.plant_descriptor(a.id, 0, 0, [1.0] * 4))
     elif isinstance(a, Tables):
@@ -201,7 +259,10 @@ def cxx_program(lib_name):
                 call.append(v)
             elif isinstance(a, Grid):
                 rows = ", ".join("{%s}" % ", ".join(_cxx_num(x) for x in getattr(a, f)) for f in ("N", "xmin", "xlast", "dx", "bc", "toward_zero"))
-                decl.append("hjq_grid %s = {%d, %d, %s};" % (v, a.ndim, a.dtype, rows))
+                decl.append("%s %s = {%d, %d, %s};" % ("hjq_grid" if a.width == 4 else "hjh_grid", v, a.ndim, a.dtype, rows))
+                call.append("&" + v)
+            elif isinstance(a, UserPlant):
+                decl.append("hjp_plant %s = {%d, 0, 0, 0, {0.0}};" % (v, a.id))
                 call.append("&" + v)
             elif isinstance(a, Plant):
                 decl.append("hjr_plant %s = {%d, 0, 0, 0, {1.0, 1.0, 1.0, 1.0}};" % (v, a.id))

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
 """Compare the gfx950 code of two builds, kernel by kernel, without a GPU.
 
-usage: codeobj_diff.py OLD NEW [--allow KERNEL_SUBSTRING ...]      (OLD / NEW: a .so, a host .o, or a bare gfx950 code object)
+usage: codeobj_diff.py OLD NEW [--allow KERNEL_SUBSTRING ...] [--by-name]      (OLD / NEW: a .so, a host .o, or a bare gfx950 code object)
 
 Every gfx950 code object of the two files is disassembled (llvm-objdump -d --no-show-raw-insn), split per kernel symbol,
 and compared instruction for instruction with addresses and `<symbol+off>` branch targets stripped; the four resource
 figures of every kernel (llvm-readelf --notes) are compared too.  Kernels that differ are listed with their instruction
 counts and the first differing line, every figure that moved as old -> new.  Exit status 1 on any difference;
 --allow limits which kernels MAY differ in instructions or figures (their differences are still listed).
+--by-name matches kernels by their demangled name and template arguments without the parameter list: for a change that renames
+a parameter's type (the mangled symbol carries it) and nothing else about the kernel.
 """
 import argparse, os, re, subprocess, sys, tempfile
 
@@ -53,14 +55,35 @@ def kernels(path, tmp):
     return out
 
 
+def by_name(ks):
+    """The same table keyed by "namespace::kernel<template arguments> [code object i]"."""
+    syms = [k.split(" [")[0] for k in ks]
+    names = subprocess.run(["c++filt"] + syms, check=True, capture_output=True, text=True).stdout.splitlines()
+    out = {}
+    for k, name in zip(ks, names):
+        depth = 0
+        for i, ch in enumerate(name):
+            depth += (ch == "<") - (ch == ">")
+            if ch == "(" and depth == 0 and i and name[i - 1] != "<":
+                name = name[:i]
+                break
+        key = re.sub(r"^void ", "", name) + " [" + k.split(" [")[1]
+        assert key not in out, key
+        out[key] = ks[k]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--allow", action="append", default=[], metavar="KERNEL_SUBSTRING")
+    ap.add_argument("--by-name", action="store_true")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory() as tmp:
         old, new = kernels(a.old, os.path.join(tmp, "old")), kernels(a.new, os.path.join(tmp, "new"))
+    if a.by_name:
+        old, new = by_name(old), by_name(new)
     bad = 0
     for k in sorted(set(old) ^ set(new)):
         print("only in %s: %s" % ("OLD" if k in old else "NEW", k))
