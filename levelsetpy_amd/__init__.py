@@ -38,7 +38,8 @@ from .rollout import computeOptTrajs                                            
 from .batch import HJIPDE_solve_batch                                           # noqa: F401
 from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCenter,   # noqa: F401
                      shapeHyperplane, shapeHyperplaneByPoints, shapeUnion, shapeIntersection,
-                     shapeDifference, shapeComplement)
+                     shapeDifference, shapeComplement, sphere_of, sphere_between, compile_program_hi,
+                     series, ShapeSeries)
 from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
 from .eikonal import signedDistance, addCRadius                                  # noqa: F401
 from . import hidim                                                              # noqa: F401

@@ -9,14 +9,17 @@
 // Stores are ONE element per lane, neighbouring lanes on neighbouring elements: a wave-instruction covers 512 contiguous bytes
 // of fp64 whatever the alignment -- with an odd node count every second member starts off 16-byte alignment, and callers pass
 // views at any element offset, so nothing here is wider than an element and no head or tail needs peeling.
-// Every device function is written one operation per statement with contraction off: the results are NumPy's, bit for bit.
+// The leaves are hj_shapes_dev.h's (shared with hj_hishapes.hip), written one operation per statement with contraction off: the
+// results are NumPy's, bit for bit.
 #include <hip/hip_runtime.h>
 #include "hj_tool_host.h"
+#include "hj_shapes_dev.h"
 #include "../../include/hj_shapes.h"
 
 namespace hjg {
 
 using namespace hj_tool;
+using namespace hjg_dev;        // nmin, nmax and the leaves: hj_shapes_dev.h, compiled here at HJ_MAX_DIM axes
 
 constexpr int BLOCK = 256;
 constexpr long long MAX_Y = 65535;      // gridDim.y of one launch
@@ -31,73 +34,6 @@ struct SceneArgs {
     int n[HJ_MAX_DIM];
     int ndim;
 };
-
-// NaN on either side gives NaN, as np.minimum / np.maximum (and array_op of hj_batch.hip)
-__device__ __forceinline__ double nmin(double a, double b) {
-    double r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else r = a < b ? a : b;
-    return r;
-}
-
-__device__ __forceinline__ double nmax(double a, double b) {
-    double r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else r = a > b ? a : b;
-    return r;
-}
-
-// sqrt(sum over the axes not in `ignore` of (x_d - c_d)(x_d - c_d)) - r;  p = c[ndim], r
-__device__ __forceinline__ double ball(const double (&x)[HJ_MAX_DIM], int ndim, int ignore, const double* __restrict__ p) {
-#pragma clang fp contract(off)
-    double s = 0.0;                     // 0 + first term is the first term: the terms are squares
-#pragma unroll
-    for (int d = 0; d < HJ_MAX_DIM; ++d) {
-        if (d < ndim && !((ignore >> d) & 1)) {
-            const double e = x[d] - p[d];
-            const double q = e * e;
-            s = s + q;
-        }
-    }
-    const double root = __builtin_sqrt(s);
-    return root - p[ndim];
-}
-
-// p = l[ndim], u[ndim]
-__device__ __forceinline__ double rect(const double (&x)[HJ_MAX_DIM], int ndim, const double* __restrict__ p) {
-#pragma clang fp contract(off)
-    const double a0 = x[0] - p[ndim];
-    const double b0 = p[0] - x[0];
-    double m = nmax(a0, b0);
-#pragma unroll
-    for (int d = 1; d < HJ_MAX_DIM; ++d) {
-        if (d < ndim) {
-            const double a = x[d] - p[ndim + d];
-            m = nmax(m, a);
-            const double b = p[d] - x[d];
-            m = nmax(m, b);
-        }
-    }
-    return m;
-}
-
-// p = n[ndim], point[ndim]
-__device__ __forceinline__ double halfspace(const double (&x)[HJ_MAX_DIM], int ndim, const double* __restrict__ p) {
-#pragma clang fp contract(off)
-    const double e0 = x[0] - p[ndim];
-    double s = p[0] * e0;
-#pragma unroll
-    for (int d = 1; d < HJ_MAX_DIM; ++d) {
-        if (d < ndim) {
-            const double e = x[d] - p[ndim + d];
-            const double q = p[d] * e;
-            s = s + q;
-        }
-    }
-    return s;
-}
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void scene_kernel(const SceneArgs A, T* __restrict__ out) {

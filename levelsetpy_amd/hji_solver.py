@@ -153,6 +153,11 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
     # ---- targets / obstacles (hji_solver.py:215-262)
     targets = _get(extraArgs, 'targetFunction')
     obstacles = _get(extraArgs, 'obstacleFunction')
+    from .shapes import ShapeSeries
+    for a, what in ((targets, 'targetFunction'), (obstacles, 'obstacleFunction')):
+        if isinstance(a, ShapeSeries):
+            error('extraArgs.%s is a ShapeSeries: HJIPDE_solve reads one member per interval on grids of 5 or 6 dimensions only; '
+                  'on a grid of %d dimensions pass its stack, series.materialize()' % (what, gDim))
     targ_tv = targets is not None and np.ndim(targets) == gDim + 1
     obs_tv = obstacles is not None and np.ndim(obstacles) == gDim + 1
     if targets is not None and np.ndim(targets) not in (gDim, gDim + 1):

@@ -20,6 +20,13 @@ fp32 result is the fp64 one rounded once.  What is prepared on the host, in NumP
 The only thing that crosses back to the host is one int32 of sign flags per member, which drives the reference's "single
 sign on grid" warning; last_info() returns them with the program and the kernel's name.
 
+Grids of 5 and 6 dimensions, and the leaf sphere_of (a sphere in J linear images of the coordinates; sphere_between builds
+the capture set of two vehicles from it), run in libhj_hishapes.so (include/hj_hishapes.h): `hi_scene_kernel`, the same
+interpreter and the same leaves over an index decode that divides by nothing.  evaluate_shape takes that library when
+g.dim > 4 or the tree holds a sphere_of, and scene_kernel otherwise, exactly as before.  series(g, node) is a time-varying
+target or obstacle WITHOUT its stack: a ShapeSeries evaluates member i alone when it is indexed, which is how
+HJIPDE_solve on a 5-D / 6-D grid reads it, one member per interval.
+
 Parity.  PINNED to the reference (tests/golden/shapes.npz): shapeRectangleByCorners, shapeRectangleByCenter, shapeUnion of
 three shapes, shapeIntersection, shapeDifference, shapeComplement.  HELD to the NumPy restatement tests/shapes_ref.py:
 both hyperplane shapes (the reference's hyperplane.py and hyper_pts.py do not run), shapeUnion of two shapes (the
@@ -27,7 +34,7 @@ reference raises IndexError), batching, array leaves and fp32.
 """
 import numpy as np
 
-from . import _ffi, _gffi
+from . import _ffi, _gffi, _hffi, _kffi
 from .context import is_tensor, require_gpu
 from .utilities import error, warn, eps
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, device_data as _device_data, stream as _stream,
@@ -36,6 +43,7 @@ from . import _qffi
 
 __all__ = ["sphere", "cylinder", "rectangle_by_corners", "rectangle_by_center", "hyperplane", "hyperplane_by_points",
            "array", "union", "intersection", "difference", "complement", "compile_program", "evaluate_shape", "last_info",
+           "sphere_of", "sphere_between", "compile_program_hi", "series", "ShapeSeries",
            "shapeRectangleByCorners", "shapeRectangleByCenter", "shapeHyperplane", "shapeHyperplaneByPoints",
            "shapeUnion", "shapeIntersection", "shapeDifference", "shapeComplement"]
 
@@ -83,6 +91,42 @@ def cylinder(axis_align, center=None, radius=1):
     """The sphere's formula over the axes NOT in axis_align (an axis or a list of axes the cylinder runs along)."""
     axes = list(axis_align) if isinstance(axis_align, (list, tuple, np.ndarray)) else [axis_align]
     return Leaf(_gffi.CYLINDER, [(center, 0.0)], [radius], axes=[int(a) for a in axes])
+
+
+class _Rows(object):
+    """The (J, dim) coefficient rows of sphere_of, or (K, J, dim) for K members."""
+
+    def __init__(self, rows):
+        self.rows = rows
+
+
+def sphere_of(rows, center=None, radius=1):
+    """A sphere in J linear images of the coordinates: sqrt(sum_j (rows[j] . x - center[j])^2) - radius, 1 <= J <= 6.
+    rows: (J, dim), or (K, J, dim) for K members; center: (J,), a scalar (times ones) or None (zeros), or (K, J); radius: a scalar
+    or (K,).  Every image takes all dim products, left to right, zero coefficients included (include/hj_hishapes.h)."""
+    if rows is None:
+        error('sphere_of needs its rows')
+    return Leaf(_kffi.SPHERE_OF, [(_Rows(rows), None), (center, 0.0)], [radius])
+
+
+def sphere_between(axes_a, axes_b, radius=1, offset=None):
+    """The sphere in the differences x[axes_a[j]] - x[axes_b[j]]: sphere_between((0, 1), (3, 4), r) is the capture set
+    sqrt((x0 - x3)^2 + (x1 - x4)^2) - r of two vehicles.  offset: the centre of the differences (default zeros).  The rows end
+    at the last axis named; the compiler gives them zero coefficients for the grid's further axes."""
+    a = [int(v) for v in (axes_a if isinstance(axes_a, (list, tuple, np.ndarray)) else [axes_a])]
+    b = [int(v) for v in (axes_b if isinstance(axes_b, (list, tuple, np.ndarray)) else [axes_b])]
+    if len(a) != len(b) or not a:
+        error('sphere_between pairs axes: axes_a and axes_b have the same length, at least 1 (got %d and %d)' % (len(a), len(b)))
+    if min(a + b) < 0:
+        error('sphere_between: axes are counted from 0')
+    if any(i == j for i, j in zip(a, b)):
+        error('sphere_between: the difference of an axis with itself is zero')
+    rows = np.zeros((len(a), max(a + b) + 1))
+    for j, (i, k) in enumerate(zip(a, b)):
+        rows[j, i], rows[j, k] = 1.0, -1.0
+    leaf = sphere_of(rows, offset, radius)
+    leaf.pad = True                             # rows shorter than the grid's dimension get zero coefficients for the further axes
+    return leaf
 
 
 def rectangle_by_corners(lower=None, upper=None):
@@ -262,16 +306,63 @@ def _scalar(value, what):
     error('%s of shape %s: a scalar, or (K,) for K members' % (what, a.shape))
 
 
+def _rows(value, dim, pad):
+    """-> (J, dim) or (K, J, dim) fp64, 1 <= J <= 6."""
+    a = _numeric(value, 'rows')
+    if np.any(np.isnan(a)):
+        error('rows holds NaN')
+    if a.ndim not in (2, 3):
+        error('rows of shape %s: (J, %d), or (K, J, %d) for K members' % (a.shape, dim, dim))
+    if pad and a.shape[-1] < dim:
+        a = np.concatenate([a, np.zeros(a.shape[:-1] + (dim - a.shape[-1],))], axis=-1)
+    if a.shape[-1] != dim:
+        error('rows of length %d fit no grid of %d dimensions: every row has %d coefficients' % (a.shape[-1], dim, dim))
+    J = a.shape[-2]
+    if J < 1 or J > _kffi.MAX_DIM:
+        error('sphere_of takes J = 1 .. %d rows (got %d)' % (_kffi.MAX_DIM, J))
+    if a.ndim == 3 and a.shape[0] < 1:
+        error('rows of shape %s: K is at least 1' % (a.shape,))
+    return a.copy()
+
+
+def _images(value, J):
+    """The centre of sphere_of -> (J,) or (K, J) fp64: None: zeros; one element: times ones; (J,); (K, J)."""
+    if value is None:
+        return np.zeros(J)
+    a = _numeric(value, 'center')
+    if np.any(np.isnan(a)):
+        error('center holds NaN')
+    if a.size == 1 and a.ndim < 2:
+        return a.item() * np.ones(J)
+    if a.ndim == 1 and a.size == J:
+        return a.copy()
+    if a.ndim == 2 and a.shape[1] == J and a.shape[0] >= 1:
+        return a.copy()
+    error('center of shape %s fits no sphere_of with %d rows: a scalar, %d values, or (K, %d) for K members' % (a.shape, J, J, J))
+
+
 def compile_program(node, dim):
     """The tree `node` as a postfix program for a grid of `dim` dimensions -> Compiled.  Pure Python: no GPU is touched.
     An n-ary union / intersection is folded left to right (a b op c op ...), so its own depth is that of its deepest
     operand plus one.  Raises ValueError for a tree beyond the limits, for parameters that fit no such grid and for
     batched parameters that disagree on K."""
+    return _compile(node, dim, False)
+
+
+def compile_program_hi(node, dim):
+    """compile_program for libhj_hishapes.so: grids of 1 .. 6 dimensions, and the leaf sphere_of."""
+    return _compile(node, dim, True)
+
+
+def _compile(node, dim, hi):
     dim = int(dim)
     if not isinstance(node, Node):
         error('evaluate a shape node (got %s): wrap a grid array in array(...)' % type(node).__name__)
-    if dim < 1 or dim > _qffi.MAX_DIM:
-        error('grids of more than %d dimensions have no device implementation' % _qffi.MAX_DIM)
+    limit = _kffi.MAX_DIM if hi else _qffi.MAX_DIM
+    if dim < 1:
+        error('grids have 1 .. %d dimensions (got %d)' % (limit, dim))
+    if dim > limit:
+        error('grids of more than %d dimensions have no device implementation' % limit)
     ops, columns, arrays, slots, ks = [], [], [], {}, []
     state = dict(off=0, depth=0, deepest=0)
 
@@ -296,6 +387,21 @@ def compile_program(node, dim):
                 slots[id(n.data)] = len(arrays)
                 arrays.append((n.data, len(shape) == dim + 1))
             ops.append((n.code, slots[id(n.data)], 0))
+            return
+        if n.code == _kffi.SPHERE_OF:
+            if not hi:
+                error('sphere_of runs in libhj_hishapes.so: compile it with compile_program_hi (evaluate_shape does)')
+            rows = _rows(n.vectors[0][0].rows, dim, getattr(n, 'pad', False))
+            J = rows.shape[-2]
+            center = _images(n.vectors[1][0], J)
+            radius = _scalar(n.scalars[0], 'radius')
+            ops.append((n.code, J, state['off']))
+            for v, batched, what in ((rows.reshape(rows.shape[:-2] + (J * dim,)), rows.ndim == 3, 'rows'),
+                                     (center, center.ndim == 2, 'center'), (radius[..., None], radius.ndim == 1, 'radius')):
+                if batched:
+                    member_axis(v.shape[0], what)
+                columns.append(v)
+                state['off'] += v.shape[-1]
             return
         arg = 0
         if n.code == _gffi.CYLINDER:
@@ -393,8 +499,9 @@ def _leaf_tensor(data):
     return _device_data(data)
 
 
-def _run(desc, N, coords, comp, dtype, device, member_note=True):
-    """Launch a compiled scene on a described grid -> tensor (members,) + N.  Sets last_info() and warns."""
+def _run(desc, N, coords, comp, dtype, device, member_note=True, hi=False):
+    """Launch a compiled scene on a described grid -> tensor (members,) + N.  Sets last_info() and warns.  hi: the program and the
+    descriptor are libhj_hishapes.so's (hjk_evaluate, hi_scene_kernel), otherwise libhj_shapes.so's (hjg_evaluate, scene_kernel)."""
     torch = require_gpu()
     if dtype not in ('float64', 'float32'):
         error('dtype must be \'float64\' or \'float32\' (got %r)' % (dtype,))
@@ -408,19 +515,49 @@ def _run(desc, N, coords, comp, dtype, device, member_note=True):
             error('data parameter does not agree in array size with grid')
         keep.append(t)
         arrs.append((t.data_ptr(), _ffi.F32 if t.dtype == torch.float32 else _ffi.F64, per_member))
-    prog = _gffi.program(comp.ops, arrs, [c.data_ptr() for c in coords])
+    ffi = _kffi if hi else _gffi
+    evaluate = ffi.lib().hjk_evaluate if hi else ffi.lib().hjg_evaluate
+    prog = ffi.program(comp.ops, arrs, [c.data_ptr() for c in coords])
     P = comp.params.shape[1]
     params = torch.from_numpy(comp.params).to(device) if P else None
     out = torch.empty((K,) + N, dtype=torch.float64 if dtype == 'float64' else torch.float32, device=device)
     flags = torch.zeros(K, dtype=torch.int32, device=device)
     with torch.cuda.device(device):
-        _gffi.check(_gffi.lib().hjg_evaluate(desc, prog, _ptr(params), K, P, _ptr(out), _ffi.F64 if dtype == 'float64' else _ffi.F32,
-                                             _ptr(flags), _stream(torch, device)))
+        ffi.check(evaluate(desc, prog, _ptr(params), K, P, _ptr(out), _ffi.F64 if dtype == 'float64' else _ffi.F32,
+                           _ptr(flags), _stream(torch, device)))
     seen = flags.cpu().numpy()
-    _LAST[0] = dict(flags=seen, program=list(comp.ops), kernel=_gffi.last_kernel(), K=K, P=P)
+    _LAST[0] = dict(flags=seen, program=list(comp.ops), kernel=ffi.last_kernel(), K=K, P=P)
     for k in np.nonzero((seen == _gffi.NEG) | (seen == _gffi.POS))[0]:
         warn(SINGLE_SIGN + (' (member %d)' % k if comp.K is not None and member_note else ''))
     return out
+
+
+def _takes_hi(g, node):
+    """Whether the tree runs in libhj_hishapes.so: a grid of more than 4 dimensions, or a sphere_of anywhere in the tree."""
+    if int(g.dim) > _qffi.MAX_DIM:
+        return True
+    pending = [node]
+    while pending:
+        n = pending.pop()
+        if isinstance(n, Operator):
+            pending.extend(n.children)
+        elif isinstance(n, Leaf) and n.code == _kffi.SPHERE_OF:
+            return True
+    return False
+
+
+def _hi_descriptor(g, dtype_name):
+    """(hjh_grid of a grid of 1 .. 6 dimensions, its shape): _hffi.grid_descriptor directly, descriptor_hi keeps to 5-D / 6-D."""
+    N = [int(v) for v in np.asarray(g.N).ravel()]
+    return _kffi.grid_descriptor(N, dtype_name), tuple(N)
+
+
+def _launch(g, comp, dtype, hi, member_note=True):
+    torch = require_gpu()
+    device = torch.device('cuda', torch.cuda.current_device())
+    name = dtype if dtype in ('float64', 'float32') else 'float64'
+    desc, N = _hi_descriptor(g, name) if hi else _descriptor(g, name)
+    return _run(desc, N, _coord_tables(g, torch, device), comp, dtype, device, member_note, hi)
 
 
 def evaluate_shape(g, node, dtype='float64', output='tensor'):
@@ -429,14 +566,66 @@ def evaluate_shape(g, node, dtype='float64', output='tensor'):
     rounded once); output='numpy' copies it to the host.  Warns once per member whose values have a single sign."""
     if output not in ('tensor', 'numpy'):
         error('output must be \'tensor\' or \'numpy\' (got %r)' % (output,))
-    comp = compile_program(node, g.dim)
-    torch = require_gpu()
-    device = torch.device('cuda', torch.cuda.current_device())
-    desc, N = _descriptor(g, dtype if dtype in ('float64', 'float32') else 'float64')
-    out = _run(desc, N, _coord_tables(g, torch, device), comp, dtype, device)
+    hi = _takes_hi(g, node)
+    comp = _compile(node, g.dim, hi)
+    out = _launch(g, comp, dtype, hi)
     if comp.K is None:
         out = out[0]
     return out if output == 'tensor' else out.cpu().numpy()
+
+
+# ------------------------------------------------------------------------------------------ a moving set without its stack
+class ShapeSeries(object):
+    """The K members of a batched shape on grid g, evaluated one at a time: series[i] is ONE launch with K = 1 -- parameter
+    row i, per-member array leaves sliced to member i, shared ones as they are -- and returns a fresh device tensor of g.shape.
+    It looks like the stack (K,) + g.shape to what asks for its shape (ndim, shape, dtype, len), so HJIPDE_solve on a 5-D / 6-D
+    grid takes it as a time-varying targetFunction / obstacleFunction and reads one member per interval; the stack itself
+    never exists.  materialize() is the whole stack from one launch, equal to evaluate_shape's.  `evaluated` lists the
+    members evaluated so far, in order."""
+
+    def __init__(self, g, node, dtype='float64'):
+        if dtype not in ('float64', 'float32'):
+            error('dtype must be \'float64\' or \'float32\' (got %r)' % (dtype,))
+        self.grid, self.node, self.dtype = g, node, dtype
+        self._hi = _takes_hi(g, node)
+        self._comp = _compile(node, g.dim, self._hi)
+        if self._comp.K is None:
+            error('a series needs a shape with K members: give a parameter or an array leaf a leading axis')
+        self.evaluated = []
+
+    @property
+    def shape(self):
+        return (self._comp.K,) + tuple(int(v) for v in np.asarray(self.grid.N).ravel())
+
+    @property
+    def ndim(self):
+        return int(self.grid.dim) + 1
+
+    def __len__(self):
+        return self._comp.K
+
+    def __getitem__(self, i):
+        if isinstance(i, slice) or not isinstance(i, (int, np.integer)):
+            raise TypeError('a ShapeSeries is indexed by one member at a time (got %s): materialize() gives the stack' % type(i).__name__)
+        K = self._comp.K
+        if not -K <= i < K:
+            raise IndexError('member %d of a series of %d' % (i, K))
+        i = int(i) % K
+        c = self._comp
+        arrays = [(_unlazy(data)[i], False) if per_member else (data, False) for data, per_member in c.arrays]
+        one = Compiled(c.ops, np.ascontiguousarray(c.params[i:i + 1]), arrays, None, c.depth)
+        out = _launch(self.grid, one, self.dtype, self._hi)[0]
+        self.evaluated.append(i)
+        return out
+
+    def materialize(self):
+        """The stack (K,) + g.shape as a device tensor, from one launch."""
+        return evaluate_shape(self.grid, self.node, self.dtype)
+
+
+def series(g, node, dtype='float64'):
+    """The batched shape `node` on grid g as a ShapeSeries: its K members on demand, one launch each, never the stack."""
+    return ShapeSeries(g, node, dtype)
 
 
 # ------------------------------------------------------------------------------------------ the reference's names

@@ -1,0 +1,321 @@
+"""CPU-only: libhj_hishapes.so (include/hj_hishapes.h) through ctypes, in the manner of tests/test_shapes_host.py.
+
+  * the argument checks of hjk_evaluate: every output pointer is null and every check comes before the first HIP call, so no
+    device is touched -- a bad program is a refusal with a message, never a launch;
+  * hjk_plan: the launches cover every node exactly once, on grids below and past 2^32 nodes and where one launch's gridDim.x
+    does not hold the grid;
+  * hjk_decode: the DEVICE decode function run on the host against np.unravel_index, on the nodes either side of 2^31, 2^32
+    and 2^33 and on random nodes -- the precedent of tests/test_large_plans.py: no device sees these grids;
+  * the binding, the header and the export table name the same functions; the Makefile keeps its old lines.
+"""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from levelsetpy_amd import _ffi, _gffi, _hffi, _kffi  # noqa: E402
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OK, EINVAL, EUNSUPPORTED = 0, -1, -3
+FAKE = 0x1000                       # a non-null address where a check wants one: only compared with null, never read
+G, K = _gffi, _kffi
+
+
+def grid(ndim=5, n=4, dtype="float64", N0=None):
+    N = [n] * ndim
+    if N0 is not None:
+        N[0] = N0
+    return K.grid_descriptor(N, dtype)
+
+
+def call(g, ops, arrays=(), coord=None, members=1, P=64, out=None, out_dtype=0, flags=None, params=None, n_ops=None, n_arrays=None,
+         null_program=False):
+    lib = K.lib()
+    prog = K.program(ops, arrays, [FAKE] * 6 if coord is None else coord)
+    if n_ops is not None:
+        prog.n_ops = n_ops
+    if n_arrays is not None:
+        prog.n_arrays = n_arrays
+    before = lib.hjk_last_kernel()
+    rc = lib.hjk_evaluate(None if g is None else C.byref(g), None if null_program else C.byref(prog), params, members, P, out, out_dtype, flags, None)
+    assert lib.hjk_last_kernel() == before                  # nothing was launched: the record stays
+    return rc, lib.hjk_last_error().decode()
+
+
+def with_ndim(g, ndim):
+    g.ndim = ndim
+    return g
+
+
+def with_dtype(g, dtype):
+    g.dtype = dtype
+    return g
+
+
+SPH, CYL, RECT, HALF, ARR = (G.SPHERE, 0, 0), (G.CYLINDER, 1, 0), (G.RECT, 0, 0), (G.HALFSPACE, 0, 0), (G.ARRAY, 0, 0)
+U, I, D, NOT = (G.UNION, 0, 0), (G.INTERSECT, 0, 0), (G.DIFFERENCE, 0, 0), (G.COMPLEMENT, 0, 0)
+OF = (K.SPHERE_OF, 2, 0)
+
+REFUSALS = [
+    # the descriptor
+    ("null-grid", dict(g=None, ops=[SPH]), EINVAL, "null grid"),
+    ("ndim0", dict(g=with_ndim(grid(1), 0), ops=[SPH]), EINVAL, "ndim 0"),
+    ("ndim7", dict(g=with_ndim(grid(6), 7), ops=[SPH]), EINVAL, "ndim 7"),
+    ("dtype7", dict(g=with_dtype(grid(), 7), ops=[SPH]), EINVAL, "dtype"),
+    ("N-negative", dict(g=grid(N0=-1), ops=[SPH]), EINVAL, "N[0]"),
+    ("N-2^31", dict(g=grid(2, N0=2 ** 31), ops=[SPH]), EINVAL, "N[0]"),
+    ("out-dtype7", dict(g=grid(), ops=[SPH], out_dtype=7), EUNSUPPORTED, "out_dtype"),
+    # the program as a whole
+    ("null-program", dict(g=grid(), ops=[SPH], null_program=True), EINVAL, "null program"),
+    ("K0", dict(g=grid(), ops=[SPH], members=0), EINVAL, "at least one member"),
+    ("K-negative", dict(g=grid(), ops=[SPH], members=-3), EINVAL, "at least one member"),
+    ("P-negative", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], P=-1), EINVAL, "negative"),
+    ("no-instructions", dict(g=grid(), ops=[]), EINVAL, "1 .. 64 instructions"),
+    ("65-instructions", dict(g=grid(), ops=[SPH] + [NOT] * 63, n_ops=65), EINVAL, "1 .. 64 instructions"),
+    ("9-arrays", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], n_arrays=9), EINVAL, "at most 8 array leaves"),
+    # opcodes
+    ("opcode0", dict(g=grid(), ops=[(0, 0, 0)]), EINVAL, "unknown opcode 0"),
+    ("opcode11", dict(g=grid(), ops=[SPH, (11, 0, 0)]), EINVAL, "unknown opcode 11"),
+    ("opcode-negative", dict(g=grid(), ops=[(-1, 0, 0)]), EINVAL, "unknown opcode -1"),
+    # the stack
+    ("underflow-union", dict(g=grid(), ops=[OF, U]), EINVAL, "stack underflow"),
+    ("underflow-first", dict(g=grid(), ops=[D, SPH]), EINVAL, "stack underflow"),
+    ("underflow-complement", dict(g=grid(), ops=[NOT]), EINVAL, "stack underflow"),
+    ("overflow", dict(g=grid(), ops=[SPH] * 8 + [OF] + [U] * 8), EINVAL, "stack overflow"),
+    ("two-left", dict(g=grid(), ops=[SPH, OF]), EINVAL, "leaves 2 values"),
+    ("three-left", dict(g=grid(), ops=[OF, SPH, SPH, I]), EINVAL, "leaves 2 values"),
+    # parameter offsets: a sphere needs ndim + 1 values, a rectangle and a halfspace 2 ndim, a sphere_of J ndim + J + 1
+    ("sphere-off", dict(g=grid(), ops=[(G.SPHERE, 0, 3)], P=8), EINVAL, "outside a row"),
+    ("sphere-off-negative", dict(g=grid(), ops=[(G.SPHERE, 0, -1)], P=8), EINVAL, "outside a row"),
+    ("rect-off", dict(g=grid(6), ops=[(G.RECT, 0, 1)], P=12), EINVAL, "outside a row"),
+    ("halfspace-off", dict(g=grid(), ops=[(G.HALFSPACE, 0, 0)], P=9), EINVAL, "outside a row"),
+    ("of-off", dict(g=grid(), ops=[(K.SPHERE_OF, 2, 0)], P=12), EINVAL, "outside a row"),
+    ("of-off-6x6", dict(g=grid(6), ops=[(K.SPHERE_OF, 6, 1)], P=43), EINVAL, "+ 43 values"),
+    ("of-off-negative", dict(g=grid(), ops=[(K.SPHERE_OF, 1, -1)]), EINVAL, "outside a row"),
+    ("sphere-P0", dict(g=grid(), ops=[SPH], P=0), EINVAL, "outside a row"),
+    # J of sphere_of
+    ("J0", dict(g=grid(), ops=[(K.SPHERE_OF, 0, 0)]), EINVAL, "J = 0"),
+    ("J7", dict(g=grid(), ops=[(K.SPHERE_OF, 7, 0)]), EINVAL, "J = 7"),
+    ("J-negative", dict(g=grid(), ops=[(K.SPHERE_OF, -1, 0)]), EINVAL, "J = -1"),
+    # cylinder masks
+    ("mask-axis5-of-5", dict(g=grid(), ops=[(G.CYLINDER, 32, 0)]), EINVAL, "mask"),
+    ("mask-negative", dict(g=grid(), ops=[(G.CYLINDER, -1, 0)]), EINVAL, "mask"),
+    ("mask-axis6-of-6", dict(g=grid(6), ops=[(G.CYLINDER, 64, 0)]), EINVAL, "mask"),
+    ("mask-axis2-of-2", dict(g=grid(2), ops=[(G.CYLINDER, 4, 0)]), EINVAL, "mask"),
+    # array leaves
+    ("array-null", dict(g=grid(), ops=[ARR], arrays=[(None, 0, 0)]), EINVAL, "array leaf 0 is null"),
+    ("array-second-null", dict(g=grid(), ops=[ARR, (G.ARRAY, 1, 0), U], arrays=[(FAKE, 0, 0), (None, 1, 1)]), EINVAL, "array leaf 1 is null"),
+    ("array-dtype", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 5, 0)]), EINVAL, "dtype 5"),
+    ("array-slot", dict(g=grid(), ops=[(G.ARRAY, 1, 0)], arrays=[(FAKE, 0, 0)]), EINVAL, "slot 1"),
+    ("array-none-declared", dict(g=grid(), ops=[ARR]), EINVAL, "slot 0 of 0"),
+    # tables and outputs: after the program
+    ("null-coord", dict(g=grid(), ops=[SPH], coord=[FAKE] * 4 + [None, FAKE]), EINVAL, "coordinate table of axis 4"),
+    ("null-out", dict(g=grid(), ops=[SPH], params=FAKE, flags=FAKE), EINVAL, "null argument"),
+    ("null-flags", dict(g=grid(), ops=[SPH], params=FAKE, out=FAKE), EINVAL, "null argument"),
+    ("null-params", dict(g=grid(), ops=[SPH], out=FAKE, flags=FAKE), EINVAL, "null argument"),
+]
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=[c[0] for c in REFUSALS])
+def test_refusals(case):
+    _, kw, code, word = case
+    rc, err = call(**kw)
+    assert rc == code and word in err, (rc, err)
+
+
+def test_valid_programs_pass_the_checks_and_stop_at_the_null_output():
+    """Everything the library validates is in order: the refusal is the null output, the last check before a launch."""
+    deepest = [OF] * 8 + [U, I, D, NOT, U, I, D, U]
+    longest = [OF] + [NOT] * 63
+    every = [(G.SPHERE, 0, 0), (G.CYLINDER, 31, 6), (G.RECT, 0, 12), (G.HALFSPACE, 0, 22), (K.SPHERE_OF, 6, 0), (G.ARRAY, 7, 0), U, I, D, NOT, U, U]
+    arrays = [(FAKE, i % 2, i % 2) for i in range(8)]
+    for ops, kw in ((deepest, {}), (longest, {}), (every, dict(arrays=arrays, P=37)), ([ARR], dict(arrays=arrays[:1], P=0))):
+        rc, err = call(grid(), ops, **kw)
+        assert rc == EINVAL and err == "null argument", err
+    for nd in range(1, 7):                                 # every dimension, the sixth coordinate table unused below 6
+        rc, err = call(grid(nd, n=3), [(G.RECT, 0, 0), (K.SPHERE_OF, nd, 0), D], P=nd * nd + nd + 1, coord=[FAKE] * nd + [None] * (6 - nd))
+        assert rc == EINVAL and err == "null argument", (nd, err)
+
+
+def test_an_empty_grid_launches_nothing():
+    for g in (grid(5, N0=0), grid(1, N0=0), grid(6, N0=0)):
+        rc, _ = call(g, [OF])
+        assert rc == OK
+    p = K.plan((4, 0, 3, 2, 2))
+    assert (p.total, p.tail, p.head, p.chunks, p.launches, p.blocks_full, p.blocks_last) == (0,) * 7
+
+
+def test_check_maps_the_codes():
+    rc, err = call(grid(), [SPH, U])
+    with pytest.raises(ValueError) as info:
+        K.check(rc)
+    assert str(info.value) == "%s (code %d)" % (err, EINVAL) and not isinstance(info.value, _ffi.Unsupported)
+    rc, err = call(grid(), [SPH], out_dtype=7)
+    with pytest.raises(_ffi.Unsupported):
+        K.check(rc)
+    K.check(0)
+
+
+def test_a_refusal_leaves_the_shape_librarys_record_alone():
+    rc = G.lib().hjg_evaluate(None, None, None, 1, 0, None, 0, None, None)
+    before = G.lib().hjg_last_error()
+    assert rc == EINVAL and b"null grid" in before
+    rc, err = call(grid(), [SPH, SPH])
+    assert rc == EINVAL and "leaves 2" in err and G.lib().hjg_last_error() == before
+
+
+# ------------------------------------------------------------------------------------------ the plan
+BIG = [(25,) * 6, (41,) * 6, (3, 2 ** 31 - 1), (65535, 65535, 2), (41, 41, 41, 41, 41, 80), (46341, 46341, 2 ** 31 - 1)]
+SMALL = [(7, 6, 8, 5, 9), (1, 1, 1, 1, 1, 1), (1, 2, 3, 25, 41, 70), (65535,), (37,), (5, 5, 6, 5, 70), (2, 2, 2, 2, 2), (3, 1, 4, 1, 5, 1)]
+
+
+def nodes_of(N):
+    total = 1
+    for n in N:
+        total *= int(n)
+    return total
+
+
+@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
+def test_the_plan_covers_every_node_exactly_once(N):
+    p = K.plan(N)
+    total = nodes_of(N)
+    assert p.total == total and p.head * p.tail == total and 1 <= p.tail < 2 ** 31
+    # the tail is the LONGEST suffix below 2^31: one more axis would pass it
+    assert p.tail == nodes_of(N[p.first_tail:]) and (p.first_tail == 0 or p.tail * N[p.first_tail - 1] >= 2 ** 31)
+    # a workgroup owns 256 consecutive tail nodes of one head index: the chunks of a head index cover its tail, the last one partly
+    assert (p.chunks - 1) * 256 < p.tail <= p.chunks * 256
+    # the launches split the head indices, none beyond gridDim.x
+    assert p.launches >= 1 and (p.launches - 1) * p.heads_per_launch < p.head <= p.launches * p.heads_per_launch
+    last_heads = p.head - (p.launches - 1) * p.heads_per_launch
+    assert p.blocks_last == last_heads * p.chunks and 1 <= p.blocks_last <= 2 ** 31 - 1
+    if p.launches > 1:
+        assert p.blocks_full == p.heads_per_launch * p.chunks <= 2 ** 31 - 1
+        assert (p.heads_per_launch + 1) * p.chunks > 2 ** 31 - 1           # a full launch is as large as gridDim.x lets it be
+    assert (p.launches - 1) * p.blocks_full + p.blocks_last == p.head * p.chunks
+    assert p.member_launches == 1
+
+
+def test_plan_of_the_named_grids():
+    p = K.plan((25,) * 6)
+    assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
+    p = K.plan((41,) * 6)
+    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.launches) == (1, 41, 41 ** 5, 1)
+    p = K.plan((3, 2 ** 31 - 1))
+    assert (p.first_tail, p.head, p.tail, p.chunks, p.launches) == (1, 3, 2 ** 31 - 1, 2 ** 23, 1)
+    p = K.plan((46341, 46341, 2 ** 31 - 1))
+    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 255 and p.launches == -(-46341 ** 2 // 255)
+    # members: gridDim.y ends at 65535
+    assert [K.plan((2, 1, 2, 1, 2), k).member_launches for k in (1, 65535, 65536, 65537, 131071)] == [1, 1, 2, 2, 3]
+
+
+def test_plan_refuses_what_the_grid_check_refuses():
+    """An axis of 2^31 nodes or more is outside the descriptor's contract (as in libhj_shapes.so): (2^31 + 5, 2) is refused, by name."""
+    for N, word in (((2 ** 31 + 5, 2), "N[0] = 2147483653"), ((2, 2 ** 31), "N[1]"), ((2 ** 31 - 1,) * 3, "2^63")):
+        p = K.LaunchPlan()
+        g = K.grid_descriptor(N)
+        rc = K.lib().hjk_plan(C.byref(g), 1, C.byref(p))
+        assert rc == EINVAL and word in K.lib().hjk_last_error().decode(), N
+        idx = (C.c_int32 * 6)()
+        assert K.lib().hjk_decode(C.byref(g), 0, C.byref(idx)) == EINVAL
+    g = K.grid_descriptor((4, 4))
+    assert K.lib().hjk_plan(C.byref(g), 0, C.byref(K.LaunchPlan())) == EINVAL and "at least one member" in K.lib().hjk_last_error().decode()
+    assert K.lib().hjk_plan(C.byref(g), 1, None) == EINVAL
+
+
+# ------------------------------------------------------------------------------------------ the decode
+def crossings(total):
+    out = [0, total - 1]
+    for b in (2 ** 31, 2 ** 32, 2 ** 33):
+        out += [n for n in (b - 2, b - 1, b, b + 1) if 0 <= n < total]
+    return out
+
+
+@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
+def test_decode_is_unravel_index(N):
+    total = nodes_of(N)
+    rng = np.random.default_rng(total % (2 ** 32))
+    nodes = crossings(total) + [int(v) for v in rng.integers(0, total, 10000, dtype=np.int64)]
+    # the ends of rows, of workgroups and of waves
+    nodes += [n for n in (63, 64, 255, 256, N[-1] - 1, N[-1], nodes_of(N[-2:]) - 1, nodes_of(N[-2:])) if 0 <= n < total]
+    lib, g, idx = K.lib(), K.grid_descriptor(N), (C.c_int32 * 6)()
+    arr = np.array(nodes, dtype=object)
+    want = np.empty((len(nodes), len(N)), dtype=np.int64)
+    rest = arr
+    for d in range(len(N) - 1, -1, -1):                   # np.unravel_index in Python integers: 2^62 nodes pass int64 products
+        want[:, d] = [int(r) % int(N[d]) for r in rest]
+        rest = [int(r) // int(N[d]) for r in rest]
+    small = total < 2 ** 62
+    if small:
+        assert np.array_equal(want, np.stack(np.unravel_index(np.array(nodes, dtype=np.int64), N), axis=1))
+    for n, w in zip(nodes, want):
+        assert lib.hjk_decode(C.byref(g), n, C.byref(idx)) == OK
+        assert tuple(idx[:len(N)]) == tuple(w) and all(v == 0 for v in idx[len(N):]), (N, n)
+
+
+def test_decode_past_the_crossings_exists_in_the_cases():
+    assert nodes_of((41,) * 6) > 2 ** 32 and nodes_of((41, 41, 41, 41, 41, 80)) > 2 ** 33 and nodes_of((3, 2 ** 31 - 1)) > 2 ** 32
+    assert K.decode((41,) * 6, 2 ** 32) == tuple(int(v) for v in np.unravel_index(2 ** 32, (41,) * 6))
+
+
+def test_decode_refuses_a_node_outside_the_grid():
+    g, idx = K.grid_descriptor((3, 4, 5)), (C.c_int32 * 6)()
+    for n in (-1, 60):
+        assert K.lib().hjk_decode(C.byref(g), n, C.byref(idx)) == EINVAL and "node" in K.lib().hjk_last_error().decode()
+    assert K.lib().hjk_decode(C.byref(g), 0, None) == EINVAL
+
+
+# ------------------------------------------------------------------------------------------ header, binding, export table
+def header_code():
+    txt = open(os.path.join(ROOT, "include", "hj_hishapes.h")).read()
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", txt, flags=re.S))
+
+
+def test_binding_header_and_exports_name_the_same_functions():
+    code = header_code()
+    declared = sorted(set(re.findall(r"\b(hjk_[a-z0-9_]+)\s*\(", code)))
+    assert declared == sorted(K.SIGNATURES) == ["hjk_decode", "hjk_evaluate", "hjk_last_error", "hjk_last_kernel", "hjk_plan"]
+    out = subprocess.check_output(["nm", "-D", K.LIB_PATH]).decode()
+    exported = sorted(set(re.findall(r" T (hjk_[a-z0-9_]+)", out)))
+    assert exported == declared, (exported, declared)
+    assert not re.findall(r" T (hj[a-jl-z]?_[a-z0-9_]+)", out)            # one translation unit: nothing of another library
+    kernels = sorted(set(re.findall(r"\b(_ZN3hjk15hi_scene_kernelI[df]E\w*)", out)))
+    stubs = sorted(set(n for n in kernels if not n.endswith(".kd")))
+    assert len(stubs) == 2 and "hi_scene_kernelIdE" in stubs[0] and "hi_scene_kernelIfE" in stubs[1], out
+    lib = K.lib()
+    for name, (_, args) in K.SIGNATURES.items():
+        assert hasattr(lib, name), name
+        decl = re.search(r"\b%s\s*\(([^)]*)\)" % name, code).group(1).strip()
+        count = 0 if decl in ("", "void") else decl.count(",") + 1
+        assert count == len(args), (name, count, len(args))
+
+
+def test_constants_and_structures_are_the_headers():
+    code = header_code()
+    for name, val in (("HJK_MAX_DIM", K.MAX_DIM), ("HJG_SPHERE_OF", K.SPHERE_OF)):
+        m = re.search(r"\b%s\s*=\s*(\d+)" % name, code)
+        assert m and int(m.group(1)) == val, name
+    assert K.SPHERE_OF == G.COMPLEMENT + 1 == 10 and (K.MAX_OPS, K.MAX_DEPTH, K.MAX_ARRAYS) == (G.MAX_OPS, G.MAX_DEPTH, G.MAX_ARRAYS)
+    assert C.sizeof(K.Program) == 8 + 64 * 8 + 8 * 16 + 6 * 8 == C.sizeof(G.Program) + 16
+    assert C.sizeof(K.LaunchPlan) == 8 + 8 * 8 and _hffi.MAX_DIM == K.MAX_DIM
+    import hishapes_ref as H
+    assert H.SPHERE_OF == K.SPHERE_OF
+
+
+def test_the_makefile_builds_the_library_beside_the_old_lines():
+    mk = open(os.path.join(ROOT, "levelsetpy_amd", "csrc", "Makefile")).read()
+    all_lines = re.findall(r"^all:(.*)$", mk, re.M)
+    assert len(re.findall(r"\blibhj_\w+\.so\b", " ".join(all_lines))) == 10 and "hishapes" not in " ".join(all_lines)
+    libs = re.findall(r"^libs:(.*)$", mk, re.M)
+    assert libs[0].split() == ["all", "libhj_hiquery.so", "libhj_plant.so"] and libs[1:] == [" libhj_hishapes.so"]
+    assert re.search(r"^libhj_hishapes\.so: hj_hishapes\.hip hj_tool_host\.h hj_shapes_dev\.h", mk, re.M)
+    assert re.search(r"^libhj_shapes\.so: hj_shapes\.hip hj_tool_host\.h hj_shapes_dev\.h", mk, re.M)
+    assert re.search(r"^resource-usage-hishapes:", mk, re.M) and re.search(r"^\trm -f .*\blibhj_hishapes\.so\b", mk, re.M)
+    assert "hj_hishapes.hip" in mk.split("HIPCC ?=")[0] and "hj_shapes_dev.h" in mk.split("HIPCC ?=")[0]
+    assert re.search(r"^\.DEFAULT_GOAL := libs$", mk, re.M)
