@@ -29,8 +29,8 @@
  * All arithmetic is fp64 whatever the output type, every operation rounded on its own, sums left to right from the
  * first term; sqrt is correctly rounded.  min / max give NaN when either side is NaN (np.minimum / np.maximum).  x_d is
  * coord[d][i_d], the grid's own coordinate vector: periodic axes get plain coordinates.  An fp32 output is the fp64
- * result rounded once at the store.  The leaves hj_shapes.h has are ONE source with libhj_shapes.so's (hj_shapes_dev.h):
- * a program without SPHERE_OF gives the bits hjg_evaluate gives.
+ * result rounded once at the store.  The interpreter and the leaves hj_shapes.h has are ONE source with
+ * libhj_shapes.so's (hj_shapes_dev.h): a program without SPHERE_OF gives the bits hjg_evaluate gives.
  *
  * flags[k] (int32, zeroed by the caller) receives the OR of what member k's STORED values showed: HJG_NEG a value < 0,
  * HJG_POS a value > 0, HJG_ZERO a zero or a NaN.  "No sign change on the grid" is flags[k] == HJG_NEG or == HJG_POS.

@@ -40,10 +40,10 @@ SIGNATURES = {
 LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_SHAPES_LIB", "libhj_shapes.so", "hjg", "hj_shapes error", SIGNATURES)
 
 
-def program(ops, arrays=(), coord=()):
-    """hjg_program from (code, arg, off) triples, (address, dtype id, per_member) triples and coordinate-table addresses.
-    Nothing is checked here: the library validates the program before it launches anything."""
-    p = Program()
+def program(ops, arrays=(), coord=(), cls=Program):
+    """hjg_program (or, with cls, _kffi's hjk_program) from (code, arg, off) triples, (address, dtype id, per_member) triples and
+    coordinate-table addresses.  Nothing is checked here: the library validates the program before it launches anything."""
+    p = cls()
     p.n_ops, p.n_arrays = len(ops), len(arrays)
     for i, (code, arg, off) in enumerate(ops[:MAX_OPS]):
         p.ops[i].code, p.ops[i].arg, p.ops[i].off = int(code), int(arg), int(off)
@@ -54,6 +54,6 @@ def program(ops, arrays=(), coord=()):
     return p
 
 
-def kernel_name(dtype_name):
-    """What hjg_last_kernel() reads after an evaluation into this output type."""
-    return "scene_kernel<%s>" % ("double" if dtype_name == "float64" else "float")
+def kernel_name(dtype_name, kernel="scene_kernel"):
+    """What hjg_last_kernel() (with _kffi's kernel, hjk_last_kernel()) reads after an evaluation into this output type."""
+    return "%s<%s>" % (kernel, "double" if dtype_name == "float64" else "float")

@@ -5,6 +5,7 @@ limits and flags are libhj_shapes.so's (_gffi.py) with one leaf more, SPHERE_OF.
 an error.
 """
 import ctypes as C
+import functools
 
 from . import _ffi, _gffi, _hffi
 
@@ -41,18 +42,8 @@ SIGNATURES = {
 LIB_PATH, lib, check, last_kernel = _ffi.bind("HJ_HISHAPES_LIB", "libhj_hishapes.so", "hjk", "hj_hishapes error", SIGNATURES)
 
 
-def program(ops, arrays=(), coord=()):
-    """hjk_program from (code, arg, off) triples, (address, dtype id, per_member) triples and coordinate-table addresses.
-    Nothing is checked here: the library validates the program before it launches anything."""
-    p = Program()
-    p.n_ops, p.n_arrays = len(ops), len(arrays)
-    for i, (code, arg, off) in enumerate(ops[:MAX_OPS]):
-        p.ops[i].code, p.ops[i].arg, p.ops[i].off = int(code), int(arg), int(off)
-    for s, (addr, dtype, per_member) in enumerate(arrays[:MAX_ARRAYS]):
-        p.arrays[s].data, p.arrays[s].dtype, p.arrays[s].per_member = addr, int(dtype), int(bool(per_member))
-    for d, addr in enumerate(coord):
-        p.coord[d] = addr
-    return p
+program = functools.partial(_gffi.program, cls=Program)                        # hjk_program, filled as hjg_program is
+kernel_name = functools.partial(_gffi.kernel_name, kernel="hi_scene_kernel")    # what hjk_last_kernel() reads after an evaluation
 
 
 def grid_descriptor(N, dtype_name="float64"):
@@ -75,8 +66,3 @@ def decode(N, node):
     g = grid_descriptor(N)
     check(lib().hjk_decode(C.byref(g), int(node), C.byref(idx)))
     return tuple(idx[:len(N)])
-
-
-def kernel_name(dtype_name):
-    """What hjk_last_kernel() reads after an evaluation into this output type."""
-    return "hi_scene_kernel<%s>" % ("double" if dtype_name == "float64" else "float")

@@ -1,4 +1,4 @@
-// Host layer of the stateless libraries (libhj_query.so, libhj_surface.so, libhj_ttr.so, libhj_rollout.so, libhj_batch.so, libhj_shapes.so, libhj_decomp.so, libhj_eikonal.so, libhj_hidim.so, libhj_hiquery.so, libhj_plant.so): the
+// Host layer of the stateless libraries (libhj_query.so, libhj_surface.so, libhj_ttr.so, libhj_rollout.so, libhj_batch.so, libhj_shapes.so, libhj_decomp.so, libhj_eikonal.so, libhj_hidim.so, libhj_hiquery.so, libhj_plant.so, libhj_hishapes.so): the
 // error text, the record of the kernels the last successful call launched, the argument checks more than one of them makes, and the
 // (dtype, scheme) dispatch of the point and rollout kernels.
 // Host code only.  Every one of these libraries is ONE translation unit that includes this header once, so the `static

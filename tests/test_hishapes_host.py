@@ -1,6 +1,7 @@
 """CPU-only: libhj_hishapes.so (include/hj_hishapes.h) through ctypes, in the manner of tests/test_shapes_host.py.
 
-  * the argument checks of hjk_evaluate: every output pointer is null and every check comes before the first HIP call, so no
+  * the argument checks of hjk_evaluate, hjk_plan and hjk_decode (the refusals of tests/tool_lib_cases.py, and valid programs up
+    to the null output): every output pointer is null and every check comes before the first HIP call, so no
     device is touched -- a bad program is a refusal with a message, never a launch;
   * hjk_plan: the launches cover every node exactly once, on grids below and past 2^32 nodes and where one launch's gridDim.x
     does not hold the grid;
@@ -18,11 +19,11 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
+import tool_lib_cases as T  # noqa: E402
 from levelsetpy_amd import _ffi, _gffi, _hffi, _kffi  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED = 0, -1, -3
+OK, EINVAL = 0, -1
 FAKE = 0x1000                       # a non-null address where a check wants one: only compared with null, never read
 G, K = _gffi, _kffi
 
@@ -34,99 +35,32 @@ def grid(ndim=5, n=4, dtype="float64", N0=None):
     return K.grid_descriptor(N, dtype)
 
 
-def call(g, ops, arrays=(), coord=None, members=1, P=64, out=None, out_dtype=0, flags=None, params=None, n_ops=None, n_arrays=None,
-         null_program=False):
+def call(g, ops, arrays=(), coord=None, P=64, out_dtype=0):
     lib = K.lib()
     prog = K.program(ops, arrays, [FAKE] * 6 if coord is None else coord)
-    if n_ops is not None:
-        prog.n_ops = n_ops
-    if n_arrays is not None:
-        prog.n_arrays = n_arrays
     before = lib.hjk_last_kernel()
-    rc = lib.hjk_evaluate(None if g is None else C.byref(g), None if null_program else C.byref(prog), params, members, P, out, out_dtype, flags, None)
+    rc = lib.hjk_evaluate(C.byref(g), C.byref(prog), None, 1, P, None, out_dtype, None, None)
     assert lib.hjk_last_kernel() == before                  # nothing was launched: the record stays
     return rc, lib.hjk_last_error().decode()
 
 
-def with_ndim(g, ndim):
-    g.ndim = ndim
-    return g
-
-
-def with_dtype(g, dtype):
-    g.dtype = dtype
-    return g
-
-
-SPH, CYL, RECT, HALF, ARR = (G.SPHERE, 0, 0), (G.CYLINDER, 1, 0), (G.RECT, 0, 0), (G.HALFSPACE, 0, 0), (G.ARRAY, 0, 0)
+SPH, ARR = (G.SPHERE, 0, 0), (G.ARRAY, 0, 0)
 U, I, D, NOT = (G.UNION, 0, 0), (G.INTERSECT, 0, 0), (G.DIFFERENCE, 0, 0), (G.COMPLEMENT, 0, 0)
 OF = (K.SPHERE_OF, 2, 0)
 
-REFUSALS = [
-    # the descriptor
-    ("null-grid", dict(g=None, ops=[SPH]), EINVAL, "null grid"),
-    ("ndim0", dict(g=with_ndim(grid(1), 0), ops=[SPH]), EINVAL, "ndim 0"),
-    ("ndim7", dict(g=with_ndim(grid(6), 7), ops=[SPH]), EINVAL, "ndim 7"),
-    ("dtype7", dict(g=with_dtype(grid(), 7), ops=[SPH]), EINVAL, "dtype"),
-    ("N-negative", dict(g=grid(N0=-1), ops=[SPH]), EINVAL, "N[0]"),
-    ("N-2^31", dict(g=grid(2, N0=2 ** 31), ops=[SPH]), EINVAL, "N[0]"),
-    ("out-dtype7", dict(g=grid(), ops=[SPH], out_dtype=7), EUNSUPPORTED, "out_dtype"),
-    # the program as a whole
-    ("null-program", dict(g=grid(), ops=[SPH], null_program=True), EINVAL, "null program"),
-    ("K0", dict(g=grid(), ops=[SPH], members=0), EINVAL, "at least one member"),
-    ("K-negative", dict(g=grid(), ops=[SPH], members=-3), EINVAL, "at least one member"),
-    ("P-negative", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], P=-1), EINVAL, "negative"),
-    ("no-instructions", dict(g=grid(), ops=[]), EINVAL, "1 .. 64 instructions"),
-    ("65-instructions", dict(g=grid(), ops=[SPH] + [NOT] * 63, n_ops=65), EINVAL, "1 .. 64 instructions"),
-    ("9-arrays", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], n_arrays=9), EINVAL, "at most 8 array leaves"),
-    # opcodes
-    ("opcode0", dict(g=grid(), ops=[(0, 0, 0)]), EINVAL, "unknown opcode 0"),
-    ("opcode11", dict(g=grid(), ops=[SPH, (11, 0, 0)]), EINVAL, "unknown opcode 11"),
-    ("opcode-negative", dict(g=grid(), ops=[(-1, 0, 0)]), EINVAL, "unknown opcode -1"),
-    # the stack
-    ("underflow-union", dict(g=grid(), ops=[OF, U]), EINVAL, "stack underflow"),
-    ("underflow-first", dict(g=grid(), ops=[D, SPH]), EINVAL, "stack underflow"),
-    ("underflow-complement", dict(g=grid(), ops=[NOT]), EINVAL, "stack underflow"),
-    ("overflow", dict(g=grid(), ops=[SPH] * 8 + [OF] + [U] * 8), EINVAL, "stack overflow"),
-    ("two-left", dict(g=grid(), ops=[SPH, OF]), EINVAL, "leaves 2 values"),
-    ("three-left", dict(g=grid(), ops=[OF, SPH, SPH, I]), EINVAL, "leaves 2 values"),
-    # parameter offsets: a sphere needs ndim + 1 values, a rectangle and a halfspace 2 ndim, a sphere_of J ndim + J + 1
-    ("sphere-off", dict(g=grid(), ops=[(G.SPHERE, 0, 3)], P=8), EINVAL, "outside a row"),
-    ("sphere-off-negative", dict(g=grid(), ops=[(G.SPHERE, 0, -1)], P=8), EINVAL, "outside a row"),
-    ("rect-off", dict(g=grid(6), ops=[(G.RECT, 0, 1)], P=12), EINVAL, "outside a row"),
-    ("halfspace-off", dict(g=grid(), ops=[(G.HALFSPACE, 0, 0)], P=9), EINVAL, "outside a row"),
-    ("of-off", dict(g=grid(), ops=[(K.SPHERE_OF, 2, 0)], P=12), EINVAL, "outside a row"),
-    ("of-off-6x6", dict(g=grid(6), ops=[(K.SPHERE_OF, 6, 1)], P=43), EINVAL, "+ 43 values"),
-    ("of-off-negative", dict(g=grid(), ops=[(K.SPHERE_OF, 1, -1)]), EINVAL, "outside a row"),
-    ("sphere-P0", dict(g=grid(), ops=[SPH], P=0), EINVAL, "outside a row"),
-    # J of sphere_of
-    ("J0", dict(g=grid(), ops=[(K.SPHERE_OF, 0, 0)]), EINVAL, "J = 0"),
-    ("J7", dict(g=grid(), ops=[(K.SPHERE_OF, 7, 0)]), EINVAL, "J = 7"),
-    ("J-negative", dict(g=grid(), ops=[(K.SPHERE_OF, -1, 0)]), EINVAL, "J = -1"),
-    # cylinder masks
-    ("mask-axis5-of-5", dict(g=grid(), ops=[(G.CYLINDER, 32, 0)]), EINVAL, "mask"),
-    ("mask-negative", dict(g=grid(), ops=[(G.CYLINDER, -1, 0)]), EINVAL, "mask"),
-    ("mask-axis6-of-6", dict(g=grid(6), ops=[(G.CYLINDER, 64, 0)]), EINVAL, "mask"),
-    ("mask-axis2-of-2", dict(g=grid(2), ops=[(G.CYLINDER, 4, 0)]), EINVAL, "mask"),
-    # array leaves
-    ("array-null", dict(g=grid(), ops=[ARR], arrays=[(None, 0, 0)]), EINVAL, "array leaf 0 is null"),
-    ("array-second-null", dict(g=grid(), ops=[ARR, (G.ARRAY, 1, 0), U], arrays=[(FAKE, 0, 0), (None, 1, 1)]), EINVAL, "array leaf 1 is null"),
-    ("array-dtype", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 5, 0)]), EINVAL, "dtype 5"),
-    ("array-slot", dict(g=grid(), ops=[(G.ARRAY, 1, 0)], arrays=[(FAKE, 0, 0)]), EINVAL, "slot 1"),
-    ("array-none-declared", dict(g=grid(), ops=[ARR]), EINVAL, "slot 0 of 0"),
-    # tables and outputs: after the program
-    ("null-coord", dict(g=grid(), ops=[SPH], coord=[FAKE] * 4 + [None, FAKE]), EINVAL, "coordinate table of axis 4"),
-    ("null-out", dict(g=grid(), ops=[SPH], params=FAKE, flags=FAKE), EINVAL, "null argument"),
-    ("null-flags", dict(g=grid(), ops=[SPH], params=FAKE, out=FAKE), EINVAL, "null argument"),
-    ("null-params", dict(g=grid(), ops=[SPH], out=FAKE, flags=FAKE), EINVAL, "null argument"),
-]
+# the refusals are rows of tests/tool_lib_cases.py, asserted for every library by tests/test_tool_libs_host.py; here one by one
+def refused(case):
+    before = K.last_kernel()
+    rc, err, kernel = T.run(case)
+    assert rc == case[4] and case[5] in err and kernel == before, T.line(case, rc, err, kernel)      # nothing was launched: the record stays
 
 
-@pytest.mark.parametrize("case", REFUSALS, ids=[c[0] for c in REFUSALS])
+REFUSALS = [c for c in T.CASES if c[0] == "hishapes" and c[2] == "hjk_evaluate"]
+
+
+@pytest.mark.parametrize("case", REFUSALS, ids=[c[1].split("-", 1)[1] for c in REFUSALS])
 def test_refusals(case):
-    _, kw, code, word = case
-    rc, err = call(**kw)
-    assert rc == code and word in err, (rc, err)
+    refused(case)
 
 
 def test_valid_programs_pass_the_checks_and_stop_at_the_null_output():
@@ -217,16 +151,10 @@ def test_plan_of_the_named_grids():
 
 def test_plan_refuses_what_the_grid_check_refuses():
     """An axis of 2^31 nodes or more is outside the descriptor's contract (as in libhj_shapes.so): (2^31 + 5, 2) is refused, by name."""
-    for N, word in (((2 ** 31 + 5, 2), "N[0] = 2147483653"), ((2, 2 ** 31), "N[1]"), ((2 ** 31 - 1,) * 3, "2^63")):
-        p = K.LaunchPlan()
-        g = K.grid_descriptor(N)
-        rc = K.lib().hjk_plan(C.byref(g), 1, C.byref(p))
-        assert rc == EINVAL and word in K.lib().hjk_last_error().decode(), N
-        idx = (C.c_int32 * 6)()
-        assert K.lib().hjk_decode(C.byref(g), 0, C.byref(idx)) == EINVAL
-    g = K.grid_descriptor((4, 4))
-    assert K.lib().hjk_plan(C.byref(g), 0, C.byref(K.LaunchPlan())) == EINVAL and "at least one member" in K.lib().hjk_last_error().decode()
-    assert K.lib().hjk_plan(C.byref(g), 1, None) == EINVAL
+    rows = [c for c in T.CASES if c[0] == "hishapes" and (c[2] == "hjk_plan" or c[5] in ("N[0] = 2147483653", "N[1]", "2^63"))]
+    assert len(rows) == 8
+    for case in rows:
+        refused(case)
 
 
 # ------------------------------------------------------------------------------------------ the decode
@@ -265,10 +193,23 @@ def test_decode_past_the_crossings_exists_in_the_cases():
 
 
 def test_decode_refuses_a_node_outside_the_grid():
-    g, idx = K.grid_descriptor((3, 4, 5)), (C.c_int32 * 6)()
-    for n in (-1, 60):
-        assert K.lib().hjk_decode(C.byref(g), n, C.byref(idx)) == EINVAL and "node" in K.lib().hjk_last_error().decode()
-    assert K.lib().hjk_decode(C.byref(g), 0, None) == EINVAL
+    rows = [c for c in T.CASES if c[1] in ("decode-node-1", "decode-node60", "decode-null")]
+    assert len(rows) == 3
+    for case in rows:
+        refused(case)
+
+
+def test_one_source_for_the_interpreter():
+    """The interpreter loop, the sign-flag vote and the program's checks stand once, in hj_shapes_dev.h: the two libraries' kernels
+    and entry points are frames around them."""
+    src = lambda n: open(os.path.join(ROOT, "levelsetpy_amd", "csrc", n)).read()      # noqa: E731
+    dev, users = src("hj_shapes_dev.h"), [src("hj_shapes.hip"), src("hj_hishapes.hip")]
+    for marker in ("below[sp - 1]", "atomicOr", "stack underflow", "unknown opcode", "outside a row"):
+        assert marker in dev and not any(marker in u for u in users), marker
+    for name in ("check_program", "OP_NAMES"):
+        assert len(re.findall(r"^static [^;=(]*\b%s\b" % name, dev, re.M)) == 1, name
+        assert not any(re.search(r"^static [^;=(]*\b%s\b" % name, u, re.M) for u in users), name
+    assert all('#include "hj_shapes_dev.h"' in u for u in users)
 
 
 # ------------------------------------------------------------------------------------------ header, binding, export table

@@ -1,7 +1,7 @@
-"""CPU-only: the argument checks of libhj_shapes.so (include/hj_shapes.h) through ctypes, in the manner of
-tests/test_tool_libs_host.py.  Every output pointer is null and every check comes before the first HIP call, so no device is
-touched: a bad program is a refusal with a message, never a launch.  Also: the binding, the header and the export table name
-the same functions, and the binding's constants and structures are the header's.
+"""CPU-only: the argument checks of libhj_shapes.so (include/hj_shapes.h) through ctypes: the refusals of
+tests/tool_lib_cases.py, and valid programs up to the null output.  Every output pointer is null and every check comes before
+the first HIP call, so no device is touched: a bad program is a refusal with a message, never a launch.  Also: the binding, the
+header and the export table name the same functions, and the binding's constants and structures are the header's.
 """
 import ctypes as C
 import os
@@ -12,107 +12,43 @@ import sys
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-
+import tool_lib_cases as T  # noqa: E402
 from levelsetpy_amd import _ffi, _gffi, _qffi  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OK, EINVAL, EUNSUPPORTED = 0, -1, -3
+OK, EINVAL = 0, -1
 FAKE = 0x1000                       # a non-null address where a check wants one: only compared with null, never read
 G = _gffi
 
 
-def grid(ndim=2, n=8, dtype=0, N0=None):
+def grid(ndim=2, n=8, N0=None):
     N = [n] * ndim
     if N0 is not None:
         N[0] = N0
-    return _qffi.grid_descriptor(ndim, N, [0.0] * ndim, [0.7] * ndim, [0.1] * ndim, [0] * ndim, [0] * ndim,
-                                 "float64" if dtype == 0 else "float32") if dtype in (0, 1) else _bad_dtype(ndim, N, dtype)
+    return _qffi.grid_descriptor(ndim, N, [0.0] * ndim, [0.7] * ndim, [0.1] * ndim, [0] * ndim, [0] * ndim, "float64")
 
 
-def _bad_dtype(ndim, N, dtype):
-    g = _qffi.grid_descriptor(ndim, N, [0.0] * ndim, [0.7] * ndim, [0.1] * ndim, [0] * ndim, [0] * ndim, "float64")
-    g.dtype = dtype
-    return g
-
-
-def call(g, ops, arrays=(), coord=None, K=1, P=8, out=None, out_dtype=0, flags=None, params=None, ndim=2, n_ops=None, n_arrays=None,
-         null_program=False):
+def call(g, ops, arrays=(), K=1, P=8, out_dtype=0, ndim=2):
     lib = G.lib()
-    prog = G.program(ops, arrays, [FAKE] * ndim if coord is None else coord)
-    if n_ops is not None:
-        prog.n_ops = n_ops
-    if n_arrays is not None:
-        prog.n_arrays = n_arrays
+    prog = G.program(ops, arrays, [FAKE] * ndim)
     before = lib.hjg_last_kernel()
-    rc = lib.hjg_evaluate(None if g is None else C.byref(g), None if null_program else C.byref(prog), params, K, P, out, out_dtype, flags, None)
+    rc = lib.hjg_evaluate(C.byref(g), C.byref(prog), None, K, P, None, out_dtype, None, None)
     assert lib.hjg_last_kernel() == before                  # nothing was launched: the record stays
     return rc, lib.hjg_last_error().decode()
 
 
-SPH, CYL, RECT, HALF, ARR = (G.SPHERE, 0, 0), (G.CYLINDER, 1, 0), (G.RECT, 0, 0), (G.HALFSPACE, 0, 0), (G.ARRAY, 0, 0)
+SPH, ARR = (G.SPHERE, 0, 0), (G.ARRAY, 0, 0)
 U, I, D, NOT = (G.UNION, 0, 0), (G.INTERSECT, 0, 0), (G.DIFFERENCE, 0, 0), (G.COMPLEMENT, 0, 0)
 
-REFUSALS = [
-    # the descriptor
-    ("null-grid", dict(g=None, ops=[SPH]), EINVAL, "null grid"),
-    ("ndim0", dict(g=grid(1), ops=[SPH], ndim=0, _ndim=0), EINVAL, "ndim"),
-    ("ndim5", dict(g=grid(1), ops=[SPH], _ndim=5), EINVAL, "ndim"),
-    ("dtype7", dict(g=grid(2, dtype=7), ops=[SPH]), EINVAL, "dtype"),
-    ("N-negative", dict(g=grid(2, N0=-1), ops=[SPH]), EINVAL, "N[0]"),
-    ("out-dtype7", dict(g=grid(), ops=[SPH], out_dtype=7), EUNSUPPORTED, "out_dtype"),
-    # the program as a whole
-    ("null-program", dict(g=grid(), ops=[SPH], null_program=True), EINVAL, "null program"),
-    ("K0", dict(g=grid(), ops=[SPH], K=0), EINVAL, "at least one member"),
-    ("K-negative", dict(g=grid(), ops=[SPH], K=-3), EINVAL, "at least one member"),
-    ("P-negative", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], P=-1), EINVAL, "negative"),
-    ("no-instructions", dict(g=grid(), ops=[]), EINVAL, "1 .. 64 instructions"),
-    ("65-instructions", dict(g=grid(), ops=[SPH] + [NOT] * 63, n_ops=65), EINVAL, "1 .. 64 instructions"),
-    ("9-arrays", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 0, 0)], n_arrays=9), EINVAL, "at most 8 array leaves"),
-    # opcodes
-    ("opcode0", dict(g=grid(), ops=[(0, 0, 0)]), EINVAL, "unknown opcode 0"),
-    ("opcode10", dict(g=grid(), ops=[SPH, (10, 0, 0)]), EINVAL, "unknown opcode 10"),
-    ("opcode-negative", dict(g=grid(), ops=[(-1, 0, 0)]), EINVAL, "unknown opcode -1"),
-    # the stack
-    ("underflow-union", dict(g=grid(), ops=[SPH, U]), EINVAL, "stack underflow"),
-    ("underflow-first", dict(g=grid(), ops=[D, SPH]), EINVAL, "stack underflow"),
-    ("underflow-complement", dict(g=grid(), ops=[NOT]), EINVAL, "stack underflow"),
-    ("overflow", dict(g=grid(), ops=[SPH] * 9 + [U] * 8), EINVAL, "stack overflow"),
-    ("two-left", dict(g=grid(), ops=[SPH, SPH]), EINVAL, "leaves 2 values"),
-    ("three-left", dict(g=grid(), ops=[SPH, SPH, SPH, I]), EINVAL, "leaves 2 values"),
-    # parameter offsets: a sphere needs ndim + 1 values, a rectangle and a halfspace 2 ndim
-    ("sphere-off", dict(g=grid(), ops=[(G.SPHERE, 0, 6)], P=8), EINVAL, "outside a row"),
-    ("sphere-off-negative", dict(g=grid(), ops=[(G.SPHERE, 0, -1)], P=8), EINVAL, "outside a row"),
-    ("cylinder-off", dict(g=grid(), ops=[(G.CYLINDER, 1, 0)], P=2), EINVAL, "outside a row"),
-    ("rect-off", dict(g=grid(), ops=[(G.RECT, 0, 5)], P=8), EINVAL, "outside a row"),
-    ("halfspace-off", dict(g=grid(3), ops=[(G.HALFSPACE, 0, 0)], P=5, ndim=3), EINVAL, "outside a row"),
-    ("sphere-P0", dict(g=grid(), ops=[SPH], P=0), EINVAL, "outside a row"),
-    # cylinder masks
-    ("mask-axis2-of-2", dict(g=grid(), ops=[(G.CYLINDER, 4, 0)]), EINVAL, "mask"),
-    ("mask-negative", dict(g=grid(), ops=[(G.CYLINDER, -1, 0)]), EINVAL, "mask"),
-    ("mask-axis3-of-3", dict(g=grid(3), ops=[(G.CYLINDER, 8, 0)], ndim=3), EINVAL, "mask"),
-    # array leaves
-    ("array-null", dict(g=grid(), ops=[ARR], arrays=[(None, 0, 0)]), EINVAL, "array leaf 0 is null"),
-    ("array-second-null", dict(g=grid(), ops=[ARR, (G.ARRAY, 1, 0), U], arrays=[(FAKE, 0, 0), (None, 1, 1)]), EINVAL, "array leaf 1 is null"),
-    ("array-dtype", dict(g=grid(), ops=[ARR], arrays=[(FAKE, 5, 0)]), EINVAL, "dtype 5"),
-    ("array-slot", dict(g=grid(), ops=[(G.ARRAY, 1, 0)], arrays=[(FAKE, 0, 0)]), EINVAL, "slot 1"),
-    ("array-slot-negative", dict(g=grid(), ops=[(G.ARRAY, -1, 0)], arrays=[(FAKE, 0, 0)]), EINVAL, "slot -1"),
-    ("array-none-declared", dict(g=grid(), ops=[ARR]), EINVAL, "slot 0 of 0"),
-    # tables and outputs: after the program
-    ("null-coord", dict(g=grid(), ops=[SPH], coord=[FAKE, None]), EINVAL, "coordinate table of axis 1"),
-    ("null-out", dict(g=grid(), ops=[SPH], params=FAKE, flags=FAKE), EINVAL, "null argument"),
-    ("null-flags", dict(g=grid(), ops=[SPH], params=FAKE, out=FAKE), EINVAL, "null argument"),
-    ("null-params", dict(g=grid(), ops=[SPH], out=FAKE, flags=FAKE), EINVAL, "null argument"),
-]
+# the refusals are rows of tests/tool_lib_cases.py, asserted for every library by tests/test_tool_libs_host.py; here one by one
+REFUSALS = [c for c in T.CASES if c[0] == "shapes"]
 
 
-@pytest.mark.parametrize("case", REFUSALS, ids=[c[0] for c in REFUSALS])
+@pytest.mark.parametrize("case", REFUSALS, ids=[c[1].split("-", 1)[1] for c in REFUSALS])
 def test_refusals(case):
-    _, kw, code, word = case
-    kw = dict(kw)
-    if "_ndim" in kw:
-        kw["g"].ndim = kw.pop("_ndim")
-    rc, err = call(**kw)
-    assert rc == code and word in err, (rc, err)
+    before = G.last_kernel()
+    rc, err, kernel = T.run(case)
+    assert rc == case[4] and case[5] in err and kernel == before, T.line(case, rc, err, kernel)      # nothing was launched: the record stays
 
 
 def test_valid_programs_pass_the_checks_and_stop_at_the_null_output():

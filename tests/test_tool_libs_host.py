@@ -88,7 +88,9 @@ REQUIRED = {"query": ["hjq_interp_points", "hjq_costate_points", "hjq_project_mi
             "rollout": ["hjr_rollout"],
             "batch": ["hjb_step_bounds", "hjb_substep", "hjb_integrate"],
             "hiquery": ["hjx_interp_points", "hjx_costate_points", "hjx_project_minmax", "hjx_rollout"],
-            "plant": ["hjp_plant_register", "hjp_rollout", "hjp_rollout_hi"]}
+            "plant": ["hjp_plant_register", "hjp_rollout", "hjp_rollout_hi"],
+            "shapes": ["hjg_evaluate"],
+            "hishapes": ["hjk_evaluate", "hjk_plan", "hjk_decode"]}
 
 
 def header_code(lib_name):
