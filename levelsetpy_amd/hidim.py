@@ -10,6 +10,8 @@ Two paths:
           system registered with hidim_ham.register_hidim_hamiltonian (its kernel is compiled at run time around the
           user's expression and reads the system's own tables): every Runge-Kutta stage is ONE launch of hidim_substep_kernel, a whole tau interval one native call
           (hjh_integrate), the compMethod minimum / maximum and the obstacle mask applied by the last stage of a step.
+          With set_hidim_trace(True) (trace_ham.py; off by default) foreign callbacks are traced into such a registration and, once
+          checked against the callbacks on the caller's data, run the same way.
   split   any other callbacks: hjh_upwind writes derivL[d], derivR[d] of every axis from one gather per cell, the
           callbacks run on device tensors, and the dissipation sum, -(ham - diss) and the stage expressions follow as
           torch expressions in the reference's order.  This path holds 2 * dim derivative arrays of the grid's size
@@ -330,9 +332,21 @@ def solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
     restrict = compMethod in ('minWithZero', 'zero')
     rs = -1 if restrict else 0                   # termRestrictUpdate with positive = 0 (hji_solver.py)
     nat = native_of(schemeData.hamFunc, schemeData.partialFunc) if (isfield(schemeData, 'hamFunc') and isfield(schemeData, 'partialFunc')) else None
-    why = None
+    why = not_traced = None
+    if nat is None and sid is not None and isfield(schemeData, 'hamFunc') and isfield(schemeData, 'partialFunc'):
+        from . import trace_ham
+        if trace_ham.hidim_enabled():
+            # foreign callbacks, traced (set_hidim_trace): a plan that has been checked against them on this data runs as a registered system does
+            from .term import native_plan, explain_plan
+            plan = native_plan(schemeData, y_init)
+            if plan is not None and plan.traced:
+                nat = (plan.system, plan[2], list(plan[3]))
+            else:
+                not_traced = explain_plan(schemeData).get('reason', 'no plan')
     if nat is None:
         why = 'hamFunc / partialFunc are not the methods of Plane5D / DubinsPair6D or of a system registered with register_hidim_hamiltonian'
+        if not_traced is not None:
+            why += ', and were not traced: %s' % not_traced
     elif _hffi.ham_dim(nat[1]) != gDim or nat[0].grid is not g:
         why = 'the system does not live on this grid'
     elif sid is None:

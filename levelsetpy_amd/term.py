@@ -125,10 +125,12 @@ def explain_plan(schemeData):
     plan = _plan_of(sd)
     if int(sd.grid.dim) > 4:
         # 5-D / 6-D grids (hidim.py): the two systems of libhj_hidim.so run fused, everything else through hjh_upwind and array expressions
-        if plan is not None and plan[2] >= _hffi.HAM_USER_BASE:      # hidim_ham.register_hidim_hamiltonian
+        if plan is not None and not plan.traced and plan[2] >= _hffi.HAM_USER_BASE:      # hidim_ham.register_hidim_hamiltonian
             return dict(path='registered', ham_id=plan[2], params=list(plan[3]), library='libhj_hidim.so')
-        if plan is not None:
+        if plan is not None and not plan.traced:
             return dict(path='built-in', ham_id=plan[2], params=list(plan[3]), library='libhj_hidim.so')
+        if _trace.hidim_enabled():
+            return _explain_hidim_trace(sd, plan)
         return dict(path='split', reason='on a grid of %d dimensions only Plane5D / DubinsPair6D with artificialDissipationGLF run fused; the '
                                          'tracer stops at 4-D' % int(sd.grid.dim), library='libhj_hidim.so')
     if plan is not None and not plan.traced:
@@ -147,6 +149,25 @@ def explain_plan(schemeData):
                 uses_range=tr.uses_range, verified=bool(done), verified_dtypes=done, unchecked=list(tr.unchecked))
 
 
+def _explain_hidim_trace(sd, plan):
+    """explain_plan on a 5-D / 6-D grid under set_hidim_trace(True), for callbacks the package has no kernel for."""
+    lib = 'libhj_hidim.so'
+    if sd.dissFunc is not artificialDissipationGLF:
+        return dict(path='split', reason='on a grid of %d dimensions only artificialDissipationGLF runs fused' % int(sd.grid.dim), library=lib)
+    if not (callable(sd.hamFunc) and callable(sd.partialFunc)):
+        return dict(path='split', reason='hamFunc / partialFunc are not callable', library=lib)
+    try:
+        tr = _trace.trace_callbacks(sd.grid, sd.hamFunc, sd.partialFunc, sd)
+    except _trace.TraceError as e:
+        return dict(path='split', reason='the callbacks cannot be traced: %s' % e, library=lib)
+    if plan is None:
+        return dict(path='split', reason='the traced kernel disagreed with the callbacks on first use, the expression keeps changing, or the library '
+                                         'refused the registration (HJ_TRACE_VERBOSE=1 says which)', source=tr.source, library=lib)
+    done = sorted(getattr(plan.system.reg, "verified_dtypes", ()))
+    return dict(path='traced', library=lib, ham_id=plan[2], params=list(plan[3]), source=tr.source, aux_axes=tuple(tr.aux_axes),
+                hoisted=list(tr.hoisted), verified=bool(done), verified_dtypes=done, unchecked=list(tr.unchecked))
+
+
 def _plan_of(sd):
     d = sd.__dict__
     fn = d['CoStateCalc'] if 'CoStateCalc' in d else d.get('derivFunc')
@@ -162,6 +183,8 @@ def _plan_of(sd):
                 if src[5] == _attach_epoch():
                     return None
                 # (an object was attach()ed to a run-time Hamiltonian since: this schemeData may have become native)
+            elif plan.traced and int(plan[0].dim) > 4 and not _trace.hidim_enabled():
+                pass                # (traced under set_hidim_trace(True), which has been taken back since)
             else:
                 nat = native_again(plan.system)
                 if nat is not None and nat[0] == plan[2] and nat[1] == plan[3] and scheme_id_of(fn) == plan[1]:
@@ -196,8 +219,9 @@ def _classify(sd, fn):
         grid_bc(sd.grid)
     except ValueError:
         return None
-    if nat is None and 2 <= int(sd.grid.dim) <= 4 and callable(sd.hamFunc) and callable(sd.partialFunc):
-        # callbacks nobody has written a kernel for: record what they compute (trace_ham.py)
+    if nat is None and callable(sd.hamFunc) and callable(sd.partialFunc) \
+            and (2 <= int(sd.grid.dim) <= 4 or (int(sd.grid.dim) in (5, 6) and _trace.hidim_enabled())):
+        # callbacks nobody has written a kernel for: record what they compute (trace_ham.py; on 5-D / 6-D grids behind set_hidim_trace)
         nat = _trace.traced_native(sd)
         traced = nat is not None
     if nat is None or nat[0].grid is not sd.grid:
@@ -226,7 +250,9 @@ def _verify_traced(plan, sd, y):
     the registration verified for that type (once per process, expression and type); anything else drops the trace with a warning and the
     split path stays.  Agreement: with a WENO scheme every node within rounding of the callbacks' result; with an ENO scheme a stencil choice
     may flip where the two arithmetics differ in the last bit, so a few nodes may differ more -- but only ISOLATED ones (no two face
-    neighbours): a wrong plane, row or region is an expression error however few nodes it holds."""
+    neighbours): a wrong plane, row or region is an expression error however few nodes it holds.
+    On a 5-D / 6-D grid the same rule: the fused term is hidim.fused_term (dg is the HiGrid), the split term takes its derivatives from
+    hjh_upwind -- which holds the 2 * dim derivative arrays of the grid's size for this one call."""
     if y is None:
         return None
     reg = plan.system.reg

@@ -27,6 +27,14 @@ schemeData, closure cells, partial arguments, module globals they name -- and re
 (_Consumed); it re-traces only when one has changed; HJ_TRACE_RECHECK=1 re-traces always.)
 
     HJ_TRACE=0 switches the tracer off; HJ_TRACE_VERBOSE=1 says why a schemeData was not traced.
+
+5-D and 6-D grids (opt-in: set_hidim_trace(True) or HJ_TRACE_HIDIM=1): the same graph is written out for hidim_ham.register_hidim_hamiltonian
+instead -- x[d], p[d], par[k] and aux[j], no col[] and no march.  A stored table becomes a run-time table aux[j] of its axis (its values are
+data, not source text), and so does every maximal subexpression of ONE coordinate that holds a transcendental or a division: it is evaluated
+once on the host by NumPy over grid.vs[d], so np.cos(grid.xs[4]) inside a callback is the same number in the kernel as under NumPy and the
+kernel does no trigonometry per cell.  Four slots in all (hjh_tables), stored tables first, then the heaviest hoisted values; the rest stays
+device math (HJ_TRACE_HOIST=off, a debug knob for measurements: nothing is hoisted).  An alpha that reads the costate range has no
+5-D / 6-D kernel and keeps the split path.
 """
 import os
 import struct
@@ -36,7 +44,34 @@ from types import ModuleType as _ModuleType
 
 import numpy as np
 
-__all__ = ["TraceError", "trace_callbacks", "traced_native", "Traced", "fingerprint"]
+__all__ = ["TraceError", "trace_callbacks", "traced_native", "Traced", "fingerprint", "set_hidim_trace", "get_hidim_trace"]
+
+MAX_AUX = 4              # the aux slots of hjh_tables (include/hj_hidim.h): tables a 5-D / 6-D expression can read
+_HIDIM = [os.environ.get("HJ_TRACE_HIDIM", "0") in ("1", "on", "yes")]
+
+
+def set_hidim_trace(on):
+    """Trace foreign hamFunc / partialFunc on 5-D and 6-D grids into hidim_substep_kernel (off by default; HJ_TRACE_HIDIM=1 sets the initial
+    value, HJ_TRACE=0 still disables all tracing).  Returns the previous setting.  Off, every call behaves as before: such callbacks take
+    the split path.  On, a traceable pair with artificialDissipationGLF runs as a registered system does -- one launch per Runge-Kutta
+    stage, a whole tau interval in one native call, no derivative arrays.
+
+    Known cost: the first use of a traced kernel (once per process, expression and floating type) is checked against the callbacks by
+    running the SPLIT path once on the caller's data, which holds the 2 * dim derivative arrays of the grid's size for that one call."""
+    from .user_ham import ATTACH_EPOCH
+    prev = _HIDIM[0]
+    _HIDIM[0] = bool(on)
+    ATTACH_EPOCH[0] += 1         # schemeData classified "no plan" under the other setting are looked at again (term._plan_of)
+    return prev
+
+
+def get_hidim_trace():
+    """The switch set_hidim_trace sets."""
+    return _HIDIM[0]
+
+
+def hidim_enabled():
+    return _HIDIM[0] and enabled()
 
 
 class TraceError(Exception):
@@ -830,8 +865,37 @@ def _literal(v):
     return "T(%s)" % float(v).hex()             # exact
 
 
+def _expression(s, a):
+    """The device expression of one node of the graph from the texts of its arguments (tables apart: each back end has its own)."""
+    if s.op in _NUM_UNARY:
+        return _NUM_UNARY[s.op].format(*a)
+    if s.op in _NUM_BINARY:
+        return _NUM_BINARY[s.op].format(*a)
+    if s.op in _CMP:
+        return "(%s %s %s)" % (a[0], _CMP[s.op], a[1])
+    if s.op in _BOOL_BINARY:
+        return _BOOL_BINARY[s.op].format(*a)
+    if s.op == "not":
+        return "(!%s)" % a[0]
+    if s.op == "where":
+        return "(%s ? %s : %s)" % (a[0], a[1], a[2])
+    raise TraceError("no device expression for '%s'" % s.op)
+
+
+def _np_apply(s, a):
+    """One node of the graph in NumPy from the values of its arguments."""
+    if s.op == "cast":
+        return np.asarray(a[0], dtype=np.float64)
+    if s.op == "where":
+        return np.where(a[0], a[1], a[2])
+    return _NP_EVAL[s.op](*a)
+
+
 class Traced(object):
-    """source, column_source, ncol, params, uses_range of a traced callback pair; evaluate() runs the same graph in NumPy."""
+    """source, column_source, ncol, params, uses_range of a traced callback pair; evaluate() runs the same graph in NumPy.
+    On a 5-D / 6-D grid: source is a body for register_hidim_hamiltonian (no column_source, ncol 0), aux_axes the axis of each table it reads
+    as aux[j], aux_tables their values (fp64 vectors: run-time data), hoisted (axis, expression) of the tables the trace made itself, in
+    the order of hoisted_slots."""
 
     def __init__(self, tr, H, alpha):
         self.dim = tr.dim
@@ -881,6 +945,10 @@ class Traced(object):
             if s.uid in live:
                 for a in s.args:
                     parents.setdefault(a.uid, []).append(s)
+        self.aux_axes, self.aux_tables, self.hoisted, self.hoisted_slots, self._aux_of = (), [], [], [], {}
+        if self.dim > 4:
+            self._hidim(tr, H, alpha, live, parents)
+            return
         # candidates: the MAXIMAL column-only values (a parent that is not column-only reads them) that contain a transcendental, a division or
         # a table.  HJ_TRACE_HOIST=all adds plain arithmetic of two operations or more (alpha_0 = |a - b cos x2| + |w x1| of a Dubins car, five
         # flops per node and plane, as the built-in kernel's Cell keeps it): measured at 201^3, no difference (0.1168-0.1189 ms either way) --
@@ -925,25 +993,13 @@ class Traced(object):
                 for a in s.args:
                     visit(a)
                 a = [ref(q) for q in s.args]
-                if s.op in _NUM_UNARY:
-                    e = _NUM_UNARY[s.op].format(*a)
-                elif s.op in _NUM_BINARY:
-                    e = _NUM_BINARY[s.op].format(*a)
-                elif s.op in _CMP:
-                    e = "(%s %s %s)" % (a[0], _CMP[s.op], a[1])
-                elif s.op in _BOOL_BINARY:
-                    e = _BOOL_BINARY[s.op].format(*a)
-                elif s.op == "not":
-                    e = "(!%s)" % a[0]
-                elif s.op == "where":
-                    e = "(%s ? %s : %s)" % (a[0], a[1], a[2])
-                elif s.op.startswith("tab"):
+                if s.op.startswith("tab"):
                     k = int(s.op[3:])
                     x0, inv, n = self._tab_geo[k]
                     used_tables.add(k)
                     e = "hjtab%d[min(max((int)rint((double)(%s - %s) * %r), 0), %d)]" % (k, a[0], _literal(x0), inv, n - 1)
                 else:
-                    raise TraceError("no device expression for '%s'" % s.op)
+                    e = _expression(s, a)
                 nm = "v%d" % s.uid
                 lines.append("const %s %s = %s;" % ("bool" if s.kind == "bool" else "T", nm, e))
                 names[s.uid] = nm
@@ -975,8 +1031,136 @@ class Traced(object):
             lines.append("alpha[%d] = %s;" % (d, names[a.uid]))
         self.source = "\n".join(lines)
 
+    def _hidim(self, tr, H, alpha, live, parents):
+        """The 5-D / 6-D back end: a body for register_hidim_hamiltonian over x[d], p[d], par[k] and aux[j] (module docstring)."""
+        if self.uses_range:
+            raise TraceError("partialFunc reads the costate range (derivMin / derivMax): the 5-D / 6-D kernel has none -- its step bound is a "
+                             "property of the grid")
+        vs = tr.real_vs
+        order = [s for s in tr.order if s.uid in live]
+        roots = set(s.uid for s in [H] + list(alpha))
+        slots, slot_key, aux_of = [], {}, {}
+
+        def slot_for(axis, vals):
+            key = (axis, vals.tobytes())          # tables equal in axis and bytes share a slot
+            j = slot_key.get(key)
+            if j is None:
+                if len(slots) >= MAX_AUX:
+                    return None
+                j = slot_key[key] = len(slots)
+                slots.append((axis, vals))
+            return j
+        # ---- stored tables first: run-time data of their axis, not source text
+        stored = [s for s in order if s.op.startswith("tab")]
+        for s in stored:
+            d, vals = self.tables[int(s.op[3:])]
+            j = slot_for(d, np.ascontiguousarray(vals, dtype=np.float64))
+            if j is None:
+                raise TraceError("the callbacks read %d stored tables: the 5-D / 6-D kernel has four table slots (aux[0..3] of hjh_tables); "
+                                 "more than four stored tables cannot be traced" % len(set(t.op for t in stored)))
+            aux_of[s.uid] = j
+        nstored = len(slots)
+        # ---- values of ONE coordinate and constants: axis_of[uid] = that axis (-1: constants only)
+        axis_of = {}
+        for s in order:
+            if s.op == "x":
+                axis_of[s.uid] = s.value
+            elif s.op == "const":
+                axis_of[s.uid] = -1
+            elif s.args and not s.op.startswith("tab"):
+                ax = set(axis_of.get(a.uid) for a in s.args)
+                if None not in ax:
+                    ax.discard(-1)
+                    if len(ax) <= 1:
+                        axis_of[s.uid] = ax.pop() if ax else -1
+        # candidates: the MAXIMAL such values (a parent that is not one, or H / alpha itself, reads them) that hold an _EXPENSIVE operation
+        # outside the candidates below them; evaluated now by the NumPy graph over grid.vs[d], as the built-in systems' tables are made
+        cand = {}
+
+        def cost(s, seen, top):
+            if s.uid in seen or (not top and s.uid in cand):
+                return 0, 0
+            seen.add(s.uid)
+            e, w = (1 if s.op in _EXPENSIVE else 0), (1 if s.args else 0)
+            for a in s.args:
+                e2, w2 = cost(a, seen, False)
+                e, w = e + e2, w + w2
+            return e, w
+
+        def host(s, d, memo):
+            if s.uid not in memo:
+                if s.op == "x":
+                    memo[s.uid] = vs[d]
+                elif s.op == "const":
+                    memo[s.uid] = np.float64(s.value)
+                else:
+                    memo[s.uid] = _np_apply(s, [host(q, d, memo) for q in s.args])
+            return memo[s.uid]
+
+        def text(s):
+            if s.op == "x":
+                return "x[%d]" % s.value
+            if s.op == "const":
+                return "%r" % s.value
+            return _expression(s, [text(q) for q in s.args])
+        if os.environ.get("HJ_TRACE_HOIST", "costly") != "off":
+            for s in order:
+                d = axis_of.get(s.uid)
+                if d is None or d < 0 or s.kind != "num" or not s.args:
+                    continue
+                ps = parents.get(s.uid, [])
+                if s.uid in roots or not ps or any(axis_of.get(q.uid) is None for q in ps):
+                    e, w = cost(s, set(), True)
+                    if e == 0:
+                        continue
+                    with np.errstate(all="ignore"):
+                        vals = np.ascontiguousarray(np.broadcast_to(np.asarray(host(s, d, {}), dtype=np.float64), vs[d].shape))
+                    if bool(np.all(np.isfinite(vals))):
+                        cand[s.uid] = (-e, -w, s.uid, s, d, vals)
+        self.hoisted, self.hoisted_slots = [], []
+        for _, _, _, s, d, vals in sorted(cand.values(), key=lambda c: c[:3]):          # heaviest first; what is left over stays device math
+            n = len(slots)
+            j = slot_for(d, vals)
+            if j is None:
+                continue
+            aux_of[s.uid] = j
+            if j == n:
+                self.hoisted.append((d, text(s)))
+                self.hoisted_slots.append(j)
+        # ---- source text, in the order the callbacks computed: one operation per statement
+        names, lines = {}, []
+
+        def visit(s):
+            if s.uid in names:
+                return
+            if s.op in ("x", "p", "par"):
+                names[s.uid] = "%s[%d]" % (s.op, s.value)
+            elif s.op == "const":
+                names[s.uid] = _literal(s.value)
+            elif s.uid in aux_of:
+                names[s.uid] = "aux[%d]" % aux_of[s.uid]
+            else:
+                for a in s.args:
+                    visit(a)
+                nm = "v%d" % s.uid
+                lines.append("const %s %s = %s;" % ("bool" if s.kind == "bool" else "T", nm, _expression(s, [names[q.uid] for q in s.args])))
+                names[s.uid] = nm
+        for s in [H] + list(alpha):
+            visit(s)
+        lines.append("H = %s;" % names[H.uid])
+        for d, a in enumerate(alpha):
+            lines.append("alpha[%d] = %s;" % (d, names[a.uid]))
+        self.source = "\n".join(lines)
+        self.column_source, self.ncol, self._cols = None, 0, []
+        self.nstored = nstored
+        self.aux_axes = tuple(d for d, _ in slots)
+        self.aux_tables = [v for _, v in slots]
+        self._aux_of = aux_of
+        self._aux_geo = [(float(vs[d][0]), (len(vs[d]) - 1) / float(vs[d][-1] - vs[d][0]) if len(vs[d]) > 1 else 0.0, len(vs[d])) for d, _ in slots]
+
     def evaluate(self, x, p, dmin=None, dmax=None, params=None):
-        """The traced graph in NumPy: (H, [alpha_d]) for coordinate arrays x[d], costates p[d] (broadcastable), ranges dmin / dmax."""
+        """The traced graph in NumPy: (H, [alpha_d]) for coordinate arrays x[d], costates p[d] (broadcastable), ranges dmin / dmax.  On a
+        5-D / 6-D grid every aux[j] is read from aux_tables at the node's index along its axis, as the kernel reads it."""
         par = self.params if params is None else params
         val = {}
         need = [self._H] + list(self._alpha)
@@ -984,7 +1168,12 @@ class Traced(object):
         def ev(s):
             if s.uid in val:
                 return val[s.uid]
-            if s.op == "x":
+            if s.uid in self._aux_of:
+                j = self._aux_of[s.uid]
+                x0, inv, n = self._aux_geo[j]
+                idx = np.clip(np.rint((np.asarray(x[self.aux_axes[j]], dtype=np.float64) - x0) * inv).astype(np.int64), 0, n - 1)
+                r = self.aux_tables[j][idx]
+            elif s.op == "x":
                 r = np.asarray(x[s.value])
             elif s.op == "p":
                 r = np.asarray(p[s.value])
@@ -1003,12 +1192,8 @@ class Traced(object):
                     x0, inv, n = self._tab_geo[k]
                     idx = np.clip(np.rint((np.asarray(a[0], dtype=np.float64) - x0) * inv).astype(np.int64), 0, n - 1)
                     r = self.tables[k][1][idx]
-                elif s.op == "cast":
-                    r = np.asarray(a[0], dtype=np.float64)
-                elif s.op == "where":
-                    r = np.where(a[0], a[1], a[2])
                 else:
-                    r = _NP_EVAL[s.op](*a)
+                    r = _np_apply(s, a)
             val[s.uid] = r
             return r
         with np.errstate(all="ignore"):
@@ -1471,6 +1656,7 @@ class _TracedSystem(object):
         self.traced = traced
         self._key = _key_of(traced)
         self._params = list(traced.params)
+        self.tables = list(traced.aux_tables)          # 5-D / 6-D: what hidim.HiGrid.tables_of uploads for this system (refreshed by a re-trace)
         self._print = fingerprint(sd)
 
     def params(self, _obj=None):
@@ -1494,6 +1680,7 @@ class _TracedSystem(object):
             self.reg = reg if reg is not None else _NoReg
             self._key = _key_of(tr)
         self._params = list(tr.params)
+        self.tables = list(tr.aux_tables)
         return list(tr.params)
 
 
@@ -1508,7 +1695,9 @@ _NoReg = _NoRegType()
 
 
 def _key_of(tr):
-    return (tr.dim, tr.source, tr.column_source, tr.uses_range, len(tr.params))
+    key = (tr.dim, tr.source, tr.column_source, tr.uses_range, len(tr.params))
+    # 5-D / 6-D: the axes of the tables are part of the kernel, their values are not -- a changed table is uploaded again, not recompiled
+    return key + (tuple(tr.aux_axes),) if tr.dim > 4 else key
 
 
 # A callback pair whose EXPRESSION keeps changing (a fifth float that varies per step, a table rebuilt every call) would compile a kernel per
@@ -1538,8 +1727,12 @@ def _registration(tr, ident=None, owner=None):
         import hashlib
         # (the name is part of the generated source, hence of the on-disk kernel cache's key: derived from the text, not from a counter)
         tag = hashlib.sha1(repr(key).encode()).hexdigest()[:12]
-        reg = NativeRegistration("traced_%s" % tag, tr.dim, tr.source, nparams=len(tr.params), column_src=tr.column_source, ncol=tr.ncol,
-                                 uses_range=tr.uses_range)
+        if tr.dim > 4:
+            from .hidim_ham import HidimRegistration
+            reg = HidimRegistration("traced_%s" % tag, tr.dim, tr.source, nparams=len(tr.params), aux_axes=tr.aux_axes)
+        else:
+            reg = NativeRegistration("traced_%s" % tag, tr.dim, tr.source, nparams=len(tr.params), column_src=tr.column_source, ncol=tr.ncol,
+                                     uses_range=tr.uses_range)
         reg.traced_key = key
         _REG_BY_SOURCE[key] = reg
     return reg
