@@ -18,7 +18,8 @@
  *     dtype    g->dtype, HJ_F64 | HJ_F32: the element type of every state array and of the tables
  *
  * params: B x HJB_PAR_SLOTS fp64 on the device, row b the parameters of problem b as hj_mi355x.h lists them for `ham`
- * (unused slots 0); rounded to the grid's dtype where they are used.
+ * (unused slots 0); rounded to the grid's dtype where they are used (once each); an entry's dt is converted once, (float)dt.
+ * The HJ_F32 rounding points are the solver's (hj_mi355x.h, "what an HJ_F32 context computes").
  *
  * A problem whose entry has active == 0 costs nothing: its workgroups return before they read or write anything of it.
  */

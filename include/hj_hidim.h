@@ -28,6 +28,11 @@
  *                             alpha = { |v_e cos x2|, |v_e sin x2|, w_e, |v_p cos x5|, |v_p sin x5|, w_p }
  *                             aux0 = cos(vs[2]), aux1 = sin(vs[2]), aux2 = cos(vs[5]), aux3 = sin(vs[5])
  * Sums run left to right.  With HJ_ENO2 / HJ_ENO3 every operation is rounded on its own, in that order.
+ * HJ_F32 (contract, as hj_mi355x.h states it for the solver; tests/test_gpu_fp32_exact.py): the tables (coordinates, cos / sin)
+ * are the caller's, of the grid's dtype -- the package forms them in fp64 and rounds once --; each parameter is rounded once and
+ * an alpha that is a parameter (a_max, alpha_max, w_e, w_p) enters hjh_step_bound as that rounded value, widened exactly; dt is
+ * converted once per launch, (float)dt; the bound 1 / sum_d (max alpha_d / dx_d) is formed in fp64 in axis order.  With HJ_ENO2 /
+ * HJ_ENO3 a float substep and hjh_upwind are then bit for bit the float32 mode of oracle/hj_oracle.py.
  *
  * Any other system: hjh_ham_register (below) compiles the caller's H / alpha expression into these kernels at run time; its
  * id (>= HJH_HAM_USER_BASE) is a `ham` like the two above.

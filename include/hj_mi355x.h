@@ -71,6 +71,26 @@ enum {
 
 enum { HJ_F64 = 0, HJ_F32 = 1 };
 
+/* ---- what an HJ_F32 context computes (contract; tests/test_gpu_fp32_exact.py holds the kernels to it) ----
+ * With HJ_ENO2 / HJ_ENO3 a substep (hj_lf_term, hj_rk_substep, hj_rk_step, hj_rk_integrate) of the Dubins car and the double
+ * integrator is the reference's array expressions evaluated in IEEE binary32, one rounding per operation, no contraction:
+ * bit for bit the float32 mode of oracle/hj_oracle.py, stencil ties included.  The rounding points are fixed as follows.
+ *   stencil constants  1/dx, 0.5/dx, (1/3)/dx, dx, dx*dx, 2*(dx*dx) are formed in double and rounded once.
+ *   coordinates, aux   every entry of hj_ctx_set_coords / hj_ctx_set_aux (doubles) is rounded once; the package forms the cos / sin
+ *                      tables in double from the double coordinates.
+ *   parameters         each of the doubles handed over (v_e, v_p, w, w_e+w_p; u_bound; u_max) is rounded once.  An alpha that is
+ *                      a parameter enters the step bound as that rounded value.
+ *   dt, t              stay double on the host; each launch converts its dt once, (float)dt.
+ *   stage expressions  y + dt*ydot, 0.25*(3*y0 + e), (1.0f/3.0f)*(y0 + 2*e), 0.5*(y0 + e): one rounding per operation.
+ *   step bound         max alpha_d per axis is a float, widened exactly; 1 / sum_d (max alpha_d / dx_d) is formed in double in
+ *                      axis order.  The as-shipped and the intended WENO5 hand over costates scaled by 1/(60 dx), 1/(12 dx):
+ *                      their maxima are fl(s * alpha) / s, one rounding away.
+ * Not bitwise in either precision: both WENO5 arithmetics (contracted, refactored); the build-defined double pendulum (its drift is
+ * evaluated in factored form); the array-level derivative entry points (hj_upwind, hj_lf_split_begin, and the point
+ * queries of include/hj_query.h that must give their bits: the divided-
+ * difference tables and the stencil choice are the reference's bit for bit, the chosen candidate D1 + dx*D2 (+ c*D3) is formed with
+ * fused multiply-adds); HJ_ENO2_FAST / HJ_ENO3_FAST. */
+
 /* how one fused substep combines its result (ExplicitIntegration/Integration/ode_cfl_{1,2,3}.py) */
 enum {
     HJ_STAGE_YDOT = 0,   /* out = ydot                         termLaxFriedrichs (term_lax_friedrich.py:124-128) */

@@ -5,7 +5,8 @@ Every case: a random system (Dubins 3-D, double integrator 2-D, double pendulum 
 at and above the tile sizes), random periodic axes, a random scheme, a random KERNEL forced through the environment knobs the library
 reads when a context is created (tiled one-cell, pair, 4-D compile-time tile k, direct), random noisy initial data; two odeCFL3 /
 odeCFL2 / odeCFL1 steps (or one termLaxFriedrichs with termRestrictUpdate) against the oracle at the tolerances of the suite
-(ENO bit for bit on the native path; WENO5 1e-11; fp32 1e-4 of the fp64 oracle).  Prints one line per case and a summary;
+(ENO bit for bit on the native path; WENO5 1e-11; fp32 1e-4 of the fp64 oracle -- and, the fp32 leg: ENO2 / ENO3 on the Dubins car and the
+double integrator in float32 bit for bit the oracle's float32 mode, t ==, whichever kernel ran).  Prints one line per case and a summary;
 exit code 1 on the first mismatch (with the case's seed, so that it can be replayed)."""
 import os
 import sys
@@ -163,9 +164,23 @@ def case(rng, k):
         def oterm(tt, yy):
             return O.term_lax_friedrichs(og, syso, scheme, tt, yy)
     yo, t, to = d0.reshape(-1, 1), 0., 0.
+    # the fp32 leg: the same steps in the oracle's float32 mode, on the data as the float kernels see it
+    exact32 = dtype == "float32" and scheme.startswith("ENO") and which != "pend"
+    if exact32:
+        og32 = O.Grid(gmin, gmax, [int(n) for n in N], list(pd) if pd else [], dtype=np.float32)
+        syso32 = mko(og32)
+        y32, t32 = d0.astype(np.float32).reshape(-1, 1), 0.
+
+        def oterm32(tt, yy):
+            yd, sb = O.term_lax_friedrichs(og32, syso32, scheme, tt, yy)
+            if restrict:
+                yd = np.maximum(yd, 0) if sdr.positive else np.minimum(yd, 0)
+            return yd, sb
     for _ in range(2):
         t, y, _ = ode(func, [t, 10.], y, op, data)
         to, yo = oode(oterm, [to, 10.], yo, 0.8, single_step=True)
+        if exact32:
+            t32, y32 = oode(oterm32, [t32, 10.], y32, 0.8, single_step=True, dtype=np.float32)
     dg = device_grid(g, dtype)
     used = dg.lib.hj_last_kernel(dg.ctx).decode()
     if kern == "split" and dtype == "float64":
@@ -178,6 +193,8 @@ def case(rng, k):
         # masked, as SURVEY 8(c) allows -- at most 1 % of the cells beyond the fp32 tolerance, none by more than a few per cent
         bad = np.abs(got - yo) > 3e-4 * scale
         ok = float(bad.mean()) <= 0.01 and err <= 0.05 and abs(t - to) <= 1e-5 * to
+        if exact32:
+            ok = ok and y32.dtype == np.float32 and np.array_equal(y.cpu().numpy().reshape(-1, 1), y32) and t == t32
     elif dtype == "float32":
         ok = err <= 3e-4 and abs(t - to) <= 1e-5 * to
     elif scheme.startswith("ENO") and which != "pend" and used != "split":
@@ -189,8 +206,9 @@ def case(rng, k):
         ok = float(bad.mean()) <= 2e-3 and err <= 1e-3 and abs(t - to) <= 1e-13 * to
     else:
         ok = err <= 1e-11 and abs(t - to) <= 1e-13 * to
-    print("%4d %-6s N=%-18s pd=%-12s %-16s %-7s order %d%s kernel %-22s err %.2e %s" % (
-        k, which, "x".join(map(str, N)), pd, scheme, dtype, order, " clamp" if restrict else "      ", used, err, "ok" if ok else "MISMATCH"), flush=True)
+    print("%4d %-6s N=%-18s pd=%-12s %-16s %-8s order %d%s kernel %-22s err %.2e %s" % (
+        k, which, "x".join(map(str, N)), pd, scheme, dtype + ("=" if exact32 else " "), order, " clamp" if restrict else "      ", used, err,
+        "ok" if ok else "MISMATCH"), flush=True)
     return ok, used
 
 

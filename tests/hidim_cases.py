@@ -1,5 +1,6 @@
 """What tests/test_hidim_host.py and tests/test_gpu_hidim.py share: the two 5-D / 6-D systems restated in the oracle's style
-(NumPy, the expressions of include/hj_hidim.h in its order), the grids and the data.
+(NumPy, the expressions of include/hj_hidim.h in its order), the grids and the data.  The trig factors are the grid's tables
+(O.Grid.cos / sin: np.cos(xs[d]) in fp64, rounded once in the oracle's float32 mode, as hidim.py builds them).
 
 Shapes: the smallest that still catch a wrong stride or decode -- distinct extents, more than one workgroup, a total that is no
 multiple of 256, a last axis shorter than a wave; and one whose last axis holds a whole wave inside one row.  Each periodic
@@ -30,15 +31,15 @@ class Plane5D(object):
 
     def hamiltonian(self, t, data, p, sd=None):
         x = self.grid.xs
-        return (p[0] * (x[3] * np.cos(x[2])) + p[1] * (x[3] * np.sin(x[2])) + p[2] * x[4] + self.s * (self.a_max * np.abs(p[3]))
+        return (p[0] * (x[3] * self.grid.cos(2)) + p[1] * (x[3] * self.grid.sin(2)) + p[2] * x[4] + self.s * (self.a_max * np.abs(p[3]))
                 + self.s * (self.alpha_max * np.abs(p[4])))
 
     def dissipation(self, t, data, derivMin, derivMax, sd, dim):
         x = self.grid.xs
         if dim == 0:
-            return np.abs(x[3] * np.cos(x[2]))
+            return np.abs(x[3] * self.grid.cos(2))
         if dim == 1:
-            return np.abs(x[3] * np.sin(x[2]))
+            return np.abs(x[3] * self.grid.sin(2))
         if dim == 2:
             return np.abs(x[4])
         return self.a_max if dim == 3 else self.alpha_max
@@ -52,19 +53,19 @@ class DubinsPair6D(object):
 
     def hamiltonian(self, t, data, p, sd=None):
         x = self.grid.xs
-        return -(p[0] * (self.v_e * np.cos(x[2])) + p[1] * (self.v_e * np.sin(x[2])) + p[3] * (self.v_p * np.cos(x[5]))
-                 + p[4] * (self.v_p * np.sin(x[5])) + self.w_e * np.abs(p[2]) - self.w_p * np.abs(p[5]))
+        return -(p[0] * (self.v_e * self.grid.cos(2)) + p[1] * (self.v_e * self.grid.sin(2)) + p[3] * (self.v_p * self.grid.cos(5))
+                 + p[4] * (self.v_p * self.grid.sin(5)) + self.w_e * np.abs(p[2]) - self.w_p * np.abs(p[5]))
 
     def dissipation(self, t, data, derivMin, derivMax, sd, dim):
         x = self.grid.xs
         if dim == 0:
-            return np.abs(self.v_e * np.cos(x[2]))
+            return np.abs(self.v_e * self.grid.cos(2))
         if dim == 1:
-            return np.abs(self.v_e * np.sin(x[2]))
+            return np.abs(self.v_e * self.grid.sin(2))
         if dim == 3:
-            return np.abs(self.v_p * np.cos(x[5]))
+            return np.abs(self.v_p * self.grid.cos(5))
         if dim == 4:
-            return np.abs(self.v_p * np.sin(x[5]))
+            return np.abs(self.v_p * self.grid.sin(5))
         return self.w_e if dim == 2 else self.w_p
 
 

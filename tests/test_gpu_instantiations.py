@@ -7,9 +7,11 @@ References and tolerances are the suite's own:
   fp64 built-in systems against oracle.term_lax_friedrichs -- ENO2 / ENO3 on the Dubins car and the double integrator bit for bit, the two
     WENO5 arithmetics 1e-11 of max(1, |ref|), the 4-D pendulum's ENO and the lean ENO ids 4 / 5 by the masked rules of tests/fuzz_parity.py
     and test_fast_eno_mode_masked_parity_with_the_reference_golden;
-  fp32: direct_substep_kernel<float> against the fp64 oracle on the same fp32-rounded data (test_gpu_fp32._fp32_close and that file's
-    state rule); every other fp32 substep instantiation against that direct kernel on the same data, bit for bit (the same per-cell
-    arithmetic: what the suite asserts between the fp64 families);
+  fp32: direct_substep_kernel<float> against the oracle's FLOAT32 mode on the same data -- ENO2 / ENO3 on the Dubins car and the double
+    integrator bit for bit, step bound == (tests/test_gpu_fp32_exact.py holds the other stages, data sets and libraries to it) -- and,
+    beside it, against the fp64 oracle on the same fp32-rounded data (test_gpu_fp32._fp32_close and that file's state rule); every other
+    fp32 substep instantiation against that direct kernel on the same data, bit for bit (the same per-cell arithmetic: what the suite
+    asserts between the fp64 families);
   term_kernel against oracle.term_normal / term_reinit / term_convection (tests/fuzz_terms.py; fp32 by the rule of
     test_fp32_split_path_terms_and_gradients), the tiled TermOp launches also bit for bit against term_kernel;
   curv_kernel against tests/curvature_ref.py and tests/trace_hess_ref.py with the tolerances of their GPU tests;
@@ -56,6 +58,8 @@ class Problem(object):
         self.g = L.createGrid(np.asarray(lo).reshape(-1, 1), np.asarray(hi).reshape(-1, 1), np.asarray(N, dtype=np.int64).reshape(-1, 1),
                               list(periodic) if periodic else None)
         self.og = og = O.Grid(lo, hi, [int(n) for n in N], list(periodic))
+        self.og32 = og32 = O.Grid(lo, hi, [int(n) for n in N], list(periodic), dtype=np.float32)
+        self.osys32 = {0: lambda: O.DubinsRel(og32, 1, 1), 1: lambda: O.DoubleIntegrator(og32, 1.25), 2: lambda: O.DoublePendulum4D(og32, 1.0)}[ham]()
         self.osys = {0: lambda: O.DubinsRel(og, 1, 1), 1: lambda: O.DoubleIntegrator(og, 1.25), 2: lambda: O.DoublePendulum4D(og, 1.0)}[ham]()
         rng = np.random.default_rng(1000 * len(N) + int(np.sum(N)))
         base = {0: lambda: O.shape_cylinder(og, 2, None, .5), 1: lambda: O.shape_sphere(og, None, .45), 2: lambda: O.shape_sphere(og, None, 1.5)}[ham]()
@@ -81,6 +85,14 @@ class Problem(object):
         if key not in self.refs:
             yd, sb = O.term_lax_friedrichs(self.og, self.osys, ORACLE_SCHEME[scheme], 0., self.arr("data", dtype).reshape(-1, 1))
             self.refs[key] = (np.asarray(yd).reshape(self.N), float(sb))
+        return self.refs[key]
+
+    def oracle32(self, scheme):
+        """(ydot, stepBound) of the oracle's float32 mode on the data as the float kernels see it."""
+        key = ("lf32", ORACLE_SCHEME[scheme])
+        if key not in self.refs:
+            yd, sb = O.term_lax_friedrichs(self.og32, self.osys32, ORACLE_SCHEME[scheme], 0., self.data.astype(np.float32).reshape(-1, 1))
+            self.refs[key] = (yd.reshape(self.N), sb)
         return self.refs[key]
 
     def taint(self, scheme, dtype):
@@ -241,6 +253,13 @@ def test_substep_instantiation_against_its_reference(r):
             compare_fp64(r, P, out.cpu().numpy(), ref, "stage %d" % stage)
             compare_bound(r, sb, ref_sb)
         elif is_direct:
+            if r.ham in (0, 1) and name in ("ENO2", "ENO3"):
+                # the float32 oracle, bit for bit (dt as the kernel converts it); the looser fp64 comparison stays beside it
+                yd32, sb32 = P.oracle32(r.scheme)
+                ref32 = stage_of(stage, yd32, P.data.astype(np.float32), P.start.astype(np.float32), np.float32(dt))
+                got32 = out.cpu().numpy()
+                assert ref32.dtype == np.float32 and np.array_equal(got32, ref32), (stage, int((got32 != ref32).sum()), r.describe())
+                assert sb == sb32, (sb, sb32, r.describe())
             if stage == _ffi.STAGE_YDOT:
                 fp32_close(out.cpu().numpy(), ref, name, "ydot")
             else:       # the state rule of test_fp32_builtin_systems_every_scheme_and_size_class
