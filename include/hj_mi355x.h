@@ -113,6 +113,15 @@ int hj_ctx_create(hj_ctx** out, int ndim, const int64_t* N, const double* xmin, 
                   const int* bc, const int* toward_zero, int dtype, int device);
 void hj_ctx_destroy(hj_ctx* ctx);
 
+/* ---- what a call's result may depend on (contract; spelled out at the top of tests/ctx_history_cases.py, held by
+ * tests/test_gpu_ctx_history.py).  The outputs of a call on a context are a function of the call's arguments, the contents of the
+ * arrays it reads, and the context's STICKY SETTINGS: what the setters last wrote -- hj_ctx_set_stream, _coords, _aux, _slab,
+ * _dissipation, _post_step, _post_arrays, _weno_eps_source, _range_source, _axis0_pad -- and the switch of hj_launch_record.
+ * Nothing else a context remembers (key rings, cached step bounds, tuner and launch-form trials, epsilon rows ...) ever shows in a
+ * result.  A bound slot holds its result until the same slot is written again, whatever else is launched in between; slots
+ * HJ_BOUND_SLOTS-4 .. HJ_BOUND_SLOTS-1 are also written by the library itself (hj_lf_term, steps and bound passes of an HJ_HAM_RANGE
+ * Hamiltonian).  A call that returns non-zero changes neither the settings nor anything a later result depends on. */
+
 /* HIP stream (hipStream_t) all later calls are ordered on; NULL = the default stream. */
 int hj_ctx_set_stream(hj_ctx* ctx, void* hip_stream);
 

@@ -719,6 +719,55 @@ def _agree3(dist, ok, device):
     return "all" if not any_failed else ("some" if any_ok else "none")
 
 
+def slab_diagnostic_legs(slab):
+    """The launch legs bench_slab's diagnostics time on this rank: the ordered list (name, plane_begin, plane_end).
+
+    Every leg ends in a barrier and an all-reduce, so the names and their order depend on (world, periodic0, counts) only,
+    never on the rank: a rank that has no planes for a leg (no halo on that side; fewer than 2*HALO + 1 planes between two
+    halos) gets the empty range (name, p, p) and times a no-op.  One rank alone has its low / high edge legs only where
+    its own ring closes through the transport."""
+    n = slab.n_local
+    lo_e = HALO if slab.halo_lo else 0
+    hi_b = n - HALO if slab.halo_hi else n
+    edges = slab.world > 1 or slab.halo_lo or slab.halo_hi
+    legs = [("interior_launch_only", lo_e, max(lo_e, hi_b))]
+    if edges:
+        legs.append(("low_edge_launch_only", 0, lo_e))
+        legs.append(("high_edge_launch_only", hi_b, n))
+    legs.append(("whole_slab_launch_only", 0, n))
+    return legs
+
+
+def run_slab_diagnostic_legs(legs, timed, sub, extra=None):
+    """Time every leg of slab_diagnostic_legs: timed(fn) -> dict is the collective stopwatch, sub(p0, p1) -> fn the launch over a
+    plane range, extra(name) -> dict what else to record right after a leg that launched.  An empty leg goes through timed() all
+    the same (with a no-op) and records planes: []."""
+    out = {}
+    for name, p0, p1 in legs:
+        if p1 > p0:
+            out[name] = dict(timed(sub(p0, p1)), planes=[p0, p1])
+            if extra is not None:
+                out[name].update(extra(name))
+        else:
+            out[name] = dict(timed(lambda: None), planes=[])
+    return out
+
+
+def _timed_collectively(dist, torch, device, sync, fn, iters=20):
+    """Mean wall time of fn() over `iters` calls on this rank, and its max / min over the ranks: ONE barrier and ONE all-reduce."""
+    import time
+    sync()
+    dist.barrier()
+    t0d = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    sync()
+    ms = 1e3 * (time.perf_counter() - t0d) / iters
+    both = torch.tensor([ms, -ms], dtype=torch.float64, device=device)
+    dist.all_reduce(both, op=dist.ReduceOp.MAX)
+    return {"this_rank_ms": round(ms, 4), "max_over_ranks_ms": round(float(both[0]), 4), "min_over_ranks_ms": round(-float(both[1]), 4)}
+
+
 def bench_slab(args, rank, world, global_n=513, workload="C4", transport=None, diagnostics=True):
     """bench.py's slab leg.  Workload C4 (default) -- global_n > 0: STRONG scaling of the global_n^3 Dubins grid (BASELINE
     C4: 513^3, slabs of 65/64 planes at 8 ranks); global_n == 0: weak scaling, every rank owns an n^3 slab.  Workload C5:
@@ -842,32 +891,22 @@ def bench_slab(args, rank, world, global_n=513, workload="C4", transport=None, d
     if diagnostics and isinstance(integ, NativeSlabStepper) and integ.external is None:
         diag = {}
         try:
-            lib, ctx, nloc = integ.dg.lib, integ.dg.ctx, integ.n
+            lib, ctx = integ.dg.lib, integ.dg.ctx
             _ffi.check(lib.hj_slab_join(ctx))
             torch.cuda.synchronize()
 
             def timed(fn, iters=20):
-                torch.cuda.synchronize()
-                dist.barrier()
-                t0d = time.perf_counter()
-                for _ in range(iters):
-                    fn()
-                torch.cuda.synchronize()
-                ms = 1e3 * (time.perf_counter() - t0d) / iters
-                both = torch.tensor([ms, -ms], dtype=torch.float64, device=device)
-                dist.all_reduce(both, op=dist.ReduceOp.MAX)
-                return {"this_rank_ms": round(ms, 4), "max_over_ranks_ms": round(float(both[0]), 4), "min_over_ranks_ms": round(-float(both[1]), 4)}
+                return _timed_collectively(dist, torch, device, torch.cuda.synchronize, fn, iters)
 
             def exch():
                 integ._exchange(integ.buf["cur"])
                 _ffi.check(lib.hj_slab_join(ctx))
+            # (with two ranks or more every rank has a neighbour, with one there is one rank: the same on all ranks)
             if slab.halo_lo or slab.halo_hi:
                 planes = integ.pad
                 diag["exchange_only"] = dict(timed(exch), planes_each_way=planes, bytes_each_way=planes * plane_cells(wl) * (8 if dtype == "float64" else 4),
                                              what="the halo exchange of one %s, alone (send + receive to each neighbour, then the join)"
                                                   % ("RK3 step (deep halo)" if integ.deep else "substep"))
-            lo_e = 3 if slab.halo_lo else 0
-            hi_b = nloc - 3 if slab.halo_hi else nloc
             b = integ.buf
 
             def sub(p0, p1):
@@ -875,14 +914,15 @@ def bench_slab(args, rank, world, global_n=513, workload="C4", transport=None, d
                     _ffi.check(lib.hj_rk_substep(ctx, sid, ham, integ.par, 0.0, _ffi.STAGE_RK3_FULL, 1e-4, 0, integ._ip(b["cur"]),
                                                  integ._ip(b["cur"]), integ._ip(b["w1"]), 5, int(p0), int(p1)))
                 return f
-            if hi_b > lo_e:
-                diag["interior_launch_only"] = dict(timed(sub(lo_e, hi_b)), planes=[lo_e, hi_b], kernel=(lib.hj_last_kernel(ctx) or b"?").decode(),
-                                                    what="one substep over the planes that need no pad, alone")
-            if lo_e > 0:
-                diag["low_edge_launch_only"] = dict(timed(sub(0, lo_e)), planes=[0, lo_e])
-            if hi_b < nloc:
-                diag["high_edge_launch_only"] = dict(timed(sub(hi_b, nloc)), planes=[hi_b, nloc])
-            diag["whole_slab_launch_only"] = dict(timed(sub(0, nloc)), planes=[0, nloc], kernel=(lib.hj_last_kernel(ctx) or b"?").decode())
+
+            def extra(name):
+                e = {}
+                if name in ("interior_launch_only", "whole_slab_launch_only"):
+                    e["kernel"] = (lib.hj_last_kernel(ctx) or b"?").decode()
+                if name == "interior_launch_only":
+                    e["what"] = "one substep over the planes that need no pad, alone"
+                return e
+            diag.update(run_slab_diagnostic_legs(slab_diagnostic_legs(slab), timed, sub, extra))
         except Exception as e:  # noqa: BLE001
             diag["error"] = repr(e)
     ok = bool(torch.isfinite(integ.state()).all())
