@@ -43,6 +43,7 @@ from .shapes import (evaluate_shape, shapeRectangleByCorners, shapeRectangleByCe
 from .decomp import sepGrid, backProject, Decomposition                          # noqa: F401
 from .eikonal import signedDistance, addCRadius                                  # noqa: F401
 from .resample import transformData, migrateGrid, shiftData, rotateData         # noqa: F401
+from .measure import setVolume, setCompare, setBounds, truncateGrid             # noqa: F401
 from . import hidim                                                              # noqa: F401
 from .hidim_ham import register_hidim_hamiltonian, HidimRegistration, HidimSystem, hidim_kernel_cache_stats   # noqa: F401
 from .plant import register_plant, PlantRegistration, PlantSystem, plant_kernel_cache_stats   # noqa: F401
