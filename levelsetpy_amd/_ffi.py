@@ -2,7 +2,7 @@
 
 The product path is HIP only: if the shared library is missing or cannot be
 loaded, every compute entry point raises.  bind() below is the one loader: the bindings of
-the stateless libraries (_qffi, _sffi, _tffi, _rffi, _bffi, _gffi, _dffi, _effi) go through it too.
+the stateless libraries (the other _?ffi modules) go through it too.
 """
 import ctypes as C
 import os

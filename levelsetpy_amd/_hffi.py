@@ -56,6 +56,14 @@ def grid_descriptor(ndim, N, xmin, xlast, dx, bc, tz, dtype_name):
     return _ffi.grid_descriptor(Grid, MAX_DIM, ndim, N, xmin, xlast, dx, bc, tz, dtype_name)
 
 
+def decode(bound, check, g, ndim, node):
+    """<prefix>_decode of the 1-D to 6-D libraries (`bound`, with the library's `check`): the multi-index their kernels' decode
+    gives flat node `node` of the grid of descriptor g."""
+    idx = (C.c_int32 * MAX_DIM)()
+    check(bound(C.byref(g), int(node), C.byref(idx)))
+    return tuple(idx[:ndim])
+
+
 def params(values):
     """HJH_PAR_SLOTS doubles on the host, unused slots 0."""
     v = [float(x) for x in values]

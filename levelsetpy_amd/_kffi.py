@@ -62,7 +62,4 @@ def plan(N, K=1):
 
 def decode(N, node):
     """hjk_decode: the multi-index the kernel's decode gives flat node `node` of a grid of extents N."""
-    idx = (C.c_int32 * MAX_DIM)()
-    g = grid_descriptor(N)
-    check(lib().hjk_decode(C.byref(g), int(node), C.byref(idx)))
-    return tuple(idx[:len(N)])
+    return _hffi.decode(lib().hjk_decode, check, grid_descriptor(N), len(N), node)

@@ -1,4 +1,4 @@
-"""Marshalling shared by the front ends of the stateless libraries (query.py, surface.py, ttr.py, rollout.py, batch.py, shapes.py, decomp.py, eikonal.py): what
+"""Marshalling shared by the front ends of the stateless libraries (every module that imports it): what
 array type a result takes, how NumPy arrays, HostViews and tensors become contiguous device tensors, raw pointers and streams
 for ctypes, and how a grid becomes the hjq_grid descriptor."""
 import ctypes as C

@@ -64,7 +64,4 @@ def plan(N, nfields=1, K=1, reduce=REDUCE_NONE):
 
 def decode(N, node):
     """hjm_decode: the multi-index the kernel's decode gives flat node `node` of a grid of extents N."""
-    idx = (C.c_int32 * MAX_DIM)()
-    g = extents_descriptor(N)
-    check(lib().hjm_decode(C.byref(g), int(node), C.byref(idx)))
-    return tuple(idx[:len(N)])
+    return _hffi.decode(lib().hjm_decode, check, extents_descriptor(N), len(N), node)

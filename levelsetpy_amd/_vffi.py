@@ -63,10 +63,7 @@ def plan(N, nfields=1, periodic=()):
 
 def decode(N, node):
     """hjv_decode: the multi-index the kernel's decode gives flat node `node` of a grid of extents N."""
-    idx = (C.c_int32 * MAX_DIM)()
-    g = extents_descriptor(N)
-    check(lib().hjv_decode(C.byref(g), int(node), C.byref(idx)))
-    return tuple(idx[:len(N)])
+    return _hffi.decode(lib().hjv_decode, check, extents_descriptor(N), len(N), node)
 
 
 def simplex_q(f):

@@ -7,9 +7,8 @@
 //                                    (cell, set) pair
 //   measure_fold_kernel              a thread owns one record: adds its slots, with the carry of Q_cut, and turns the bounds round
 // The per-simplex rule is hj_measure_dev.h's simplex_q / simplex_chain, which hjv_simplex_q_host runs on the host.  The minimum and
-// maximum are hj_shapes_dev.h's nmin / nmax.  The node decode is hj_hishapes.hip's scheme as hj_resample.hip carries it (tail / head
-// split, host-prepared reciprocals, blockIdx.x split in 32 bits: nothing divides) at a compile-time number of axes; `split_block` and
-// `node_index` are __host__ __device__: hjv_decode runs them on the host.
+// maximum are hj_shapes_dev.h's nmin / nmax.  The node decode is hj_index_dev.h's walk (tail / head split, host-prepared reciprocals,
+// blockIdx.x split in 32 bits: nothing divides) at a compile-time number of axes.
 // Nothing a lane indexes at run time is a register array: the corner values live in LDS, the recursion's row is indexed by vertex in
 // loops of compile-time bounds, the per-set accumulators are selected by predicates (make resource-usage-measure: no scratch).
 // Every sum is an integer sum -- ballots and shuffles in the wave, LDS across the waves, one atomic add per workgroup and counter
@@ -22,12 +21,14 @@
 #include "hj_tool_host.h"
 #include "../../include/hj_hidim.h"
 #include "hj_shapes_dev.h"
+#include "hj_index_dev.h"
 #include "hj_measure_dev.h"
 #include "../../include/hj_measure.h"
 
 namespace hjv {
 
 using namespace hj_tool;
+using namespace hj_index;
 using hjg_dev::nmin;
 using hjg_dev::nmax;
 using hjg_dev::MAX_Y;
@@ -40,23 +41,11 @@ constexpr int WAVE = 64;
 constexpr int WAVES = BLOCK / WAVE;
 constexpr int MD = HJV_MAX_DIM;
 constexpr int WORDS = HJV_RECORD_WORDS;
-constexpr long long MAX_X = 0x7fffffffll;   // gridDim.x of one launch
 constexpr int SUMS = 7;                      // per-wave partial sums: full, cut, invalid, inside, nan, Q_cut low, Q_cut high
 static_assert(HJV_LO == 8 && HJV_HI == HJV_LO + MD && WORDS == HJV_HI + MD, "the record ends with the two rows of bounds");
 
-// what the decode reads: the grid's extents (1 past ndim), their reciprocals and the split of blockIdx.x
-struct MvIndex {
-    unsigned long long recip[MD];           // floor(2^64 / n) + 1 for n > 1: quotient
-    unsigned long long chunk_recip;         // the same of `chunks`
-    unsigned n[MD];                         // nodes per axis
-    unsigned h0[MD];                        // multi-index of this launch's first head index (tail axes: 0)
-    unsigned chunks;                        // workgroups per head index
-    unsigned tail;                          // nodes of the tail, below 2^31
-    int first_tail;                         // axes first_tail .. ndim - 1 are the tail
-};
-
 struct MvArgs {
-    MvIndex X;
+    Index X;                                // the grid's extents and the split of blockIdx.x
     long long stride[MD];                   // nodes between neighbours along axis d
     long long node0;                        // flat node of this launch's first head index at tail node 0
     long long stride_a, stride_b;           // elements between fields (stride_b 0: one field of b for all)
@@ -66,53 +55,6 @@ struct MvArgs {
     unsigned f0;                            // first field of this launch
     unsigned nslots;                        // a power of two
 };
-
-// floor(v / n) for any 32-bit v by the reciprocal r = floor(2^64 / n) + 1 of n > 1: the high 64 bits of v * r
-__host__ __device__ __forceinline__ unsigned quotient(unsigned v, unsigned long long r) {
-    const unsigned long long lo = (unsigned long long)v * (unsigned)r;
-    const unsigned long long hi = (unsigned long long)v * (unsigned)(r >> 32);
-    return (unsigned)((hi + (lo >> 32)) >> 32);
-}
-
-// blockIdx.x = head' * chunks + chunk -> head' (counted from this launch's first head index) and the chunk; wave-uniform
-__host__ __device__ __forceinline__ void split_block(const MvIndex& X, unsigned block, unsigned& hl, unsigned& chunk) {
-    hl = block;
-    chunk = 0u;
-    if (X.chunks > 1u) {
-        hl = quotient(block, X.chunk_recip);
-        chunk = block - hl * X.chunks;
-    }
-}
-
-// The multi-index of tail node t of head index h0 + hl on a grid of ND axes.  The tail axes divide t, a lane's own value; the head
-// axes add hl to the launch's first head index with carry, wave-uniform.
-template <int ND>
-__host__ __device__ __forceinline__ void node_index(const MvIndex& X, unsigned hl, unsigned t, unsigned (&idx)[ND]) {
-    unsigned up = hl;
-#pragma unroll
-    for (int d = ND - 1; d >= 0; --d) {
-        if (d > X.first_tail) {
-            idx[d] = 0u;
-            if (X.n[d] > 1u) {
-                const unsigned q = quotient(t, X.recip[d]);
-                idx[d] = t - q * X.n[d];
-                t = q;
-            }
-        } else if (d == X.first_tail) {
-            idx[d] = t;
-        } else if (d > 0) {
-            const unsigned v = X.h0[d] + up;                     // both below 2^31
-            idx[d] = 0u;
-            up = v;                                              // an axis of one node passes the carry on
-            if (X.n[d] > 1u) {
-                up = quotient(v, X.recip[d]);
-                idx[d] = v - up * X.n[d];
-            }
-        } else {
-            idx[0] = X.h0[0] + up;
-        }
-    }
-}
 
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #pragma unroll
@@ -397,48 +339,11 @@ __global__ __launch_bounds__(BLOCK) void measure_fold_kernel(const FoldArgs F, c
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static unsigned long long recip64(unsigned n) { return n > 1u ? 0xffffffffffffffffull / n + 1ull : 0ull; }
-
-// the split of the grid's axes, the launches and what the decode reads of them (X.h0 is set per launch)
-static void make_plan(const hjh_grid* g, long long total, long long nfields, hjv_launch_plan& L, MvIndex& X) {
-    L = hjv_launch_plan{};
-    X = MvIndex{};
-    for (int d = 0; d < MD; ++d) {
-        X.n[d] = d < g->ndim ? (unsigned)g->N[d] : 1u;
-        X.recip[d] = recip64(X.n[d]);
-    }
-    L.nfields = nfields;
-    L.field_launches = (int32_t)((nfields + MAX_Y - 1) / MAX_Y);
-    L.total = total;
-    long long tail = 1;
-    int ft = g->ndim;
-    while (ft > 0 && tail * (long long)X.n[ft - 1] < 0x80000000ll) tail *= (long long)X.n[--ft];       // the last axis always fits
-    L.first_tail = ft;
-    L.tail = tail;
-    L.head = total / tail;
-    L.chunks = (tail + BLOCK - 1) / BLOCK;
-    L.heads_per_launch = std::min<long long>(L.head, MAX_X / L.chunks);
-    L.launches = (L.head + L.heads_per_launch - 1) / L.heads_per_launch;
-    L.blocks_full = L.heads_per_launch * L.chunks;
-    L.blocks_last = (L.head - (L.launches - 1) * L.heads_per_launch) * L.chunks;
-    if (L.launches == 1) L.blocks_full = L.blocks_last;
-    L.slots = 1;
-    while (L.slots < HJV_MAX_SLOTS && L.slots < L.head * L.chunks) L.slots *= 2;     // head * chunks <= total
-    X.chunks = (unsigned)L.chunks;
-    X.chunk_recip = recip64(X.chunks);
-    X.tail = (unsigned)tail;
-    X.first_tail = ft;
-}
-
-// the multi-index of head index `head` into X.h0: the one place that divides, on the host
-static void set_head(MvIndex& X, long long head) {
-    for (int d = MD - 1; d >= 0; --d) {
-        X.h0[d] = 0u;
-        if (d < X.first_tail) {
-            X.h0[d] = (unsigned)(head % (long long)X.n[d]);
-            head /= (long long)X.n[d];
-        }
-    }
+// partial records per field and set: a power of two, no more than the grid has workgroups
+static long long slots_of(const Plan& L) {
+    long long slots = 1;
+    while (slots < HJV_MAX_SLOTS && slots < L.head * L.chunks) slots *= 2;           // head * chunks <= total
+    return slots;
 }
 
 // the grid: 1 .. 6 axes of 2 .. 2^31 - 1 nodes, at most 2^63 - 1 in all, every boundary kind known
@@ -457,20 +362,18 @@ static int check_fields(int64_t nfields) {
 }
 
 template <typename TA, typename TB, int ND, bool CMP>
-static int run(MvArgs& A, const hjv_launch_plan& L, const FoldArgs& F, const void* a, const void* b, void* records, hipStream_t stream) {
-    HIP_TRY(hipMemsetAsync(A.slots, 0, (size_t)(F.records * L.slots * WORDS * 8), stream));
-    for (long long l = 0; l < L.launches; ++l) {
-        const long long head = l * L.heads_per_launch;
-        set_head(A.X, head);
-        A.node0 = head * L.tail;
-        const unsigned blocks = (unsigned)(l + 1 < L.launches ? L.blocks_full : L.blocks_last);
-        for (long long f0 = 0; f0 < L.nfields; f0 += MAX_Y) {
+static int run(MvArgs& A, const Plan& L, long long nfields, const FoldArgs& F, const void* a, const void* b, void* records, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(A.slots, 0, (size_t)(F.records * F.nslots * WORDS * 8), stream));
+    int rc = head_launches(L, A.X, A.node0, [&](unsigned blocks) {
+        for (long long f0 = 0; f0 < nfields; f0 += MAX_Y) {
             A.f0 = (unsigned)f0;
-            const unsigned ny = (unsigned)(L.nfields - f0 < MAX_Y ? L.nfields - f0 : MAX_Y);
+            const unsigned ny = (unsigned)(nfields - f0 < MAX_Y ? nfields - f0 : MAX_Y);
             hipLaunchKernelGGL((measure_kernel<TA, TB, ND, CMP>), dim3(blocks, ny), dim3(BLOCK), 0, stream, A, (const TA*)a, (const TB*)b);
             HIP_TRY(hipGetLastError());
         }
-    }
+        return (int)HJ_OK;
+    });
+    if (rc) return rc;
     launched((std::string("measure_kernel<") + type_tag<TA>::name() + ", " + type_tag<TB>::name() + ", " + std::to_string(ND) + ", " +
               (CMP ? "1>" : "0>")).c_str());
     unsigned blocks = 0;
@@ -482,23 +385,8 @@ static int run(MvArgs& A, const hjv_launch_plan& L, const FoldArgs& F, const voi
 }
 
 template <typename TA, typename TB, bool CMP>
-static int run_ndim(int ndim, MvArgs& A, const hjv_launch_plan& L, const FoldArgs& F, const void* a, const void* b, void* records, hipStream_t stream) {
-    switch (ndim) {
-        case 1: return run<TA, TB, 1, CMP>(A, L, F, a, b, records, stream);
-        case 2: return run<TA, TB, 2, CMP>(A, L, F, a, b, records, stream);
-        case 3: return run<TA, TB, 3, CMP>(A, L, F, a, b, records, stream);
-        case 4: return run<TA, TB, 4, CMP>(A, L, F, a, b, records, stream);
-        case 5: return run<TA, TB, 5, CMP>(A, L, F, a, b, records, stream);
-        default: return run<TA, TB, 6, CMP>(A, L, F, a, b, records, stream);
-    }
-}
-
-template <int ND>
-static void decode_nd(const MvIndex& X, unsigned block, unsigned lane, int32_t* idx) {
-    unsigned own[ND], hl = 0u, chunk = 0u;
-    split_block(X, block, hl, chunk);
-    node_index<ND>(X, hl, chunk * (unsigned)BLOCK + lane, own);
-    for (int d = 0; d < ND; ++d) idx[d] = (int32_t)own[d];
+static int run_ndim(int ndim, MvArgs& A, const Plan& L, long long nfields, const FoldArgs& F, const void* a, const void* b, void* records, hipStream_t stream) {
+    return dispatch_ndim(ndim, [&](auto nd) { return run<TA, TB, decltype(nd)::value, CMP>(A, L, nfields, F, a, b, records, stream); });
 }
 
 template <int D>
@@ -531,12 +419,11 @@ int hjv_measure(const hjh_grid* g, const void* a, int64_t nfields, int64_t strid
     if (!a || !records || !workspace) return fail(HJ_EINVAL, "null argument");
 
     MvArgs A{};
-    hjv_launch_plan L;
-    make_plan(g, total, nfields, L, A.X);
+    const Plan L = make_plan(g, total, BLOCK, A.X);
     FoldArgs F{};
     F.records = nfields * (b ? 4 : 1);
     F.cells = 1;
-    F.nslots = (unsigned)L.slots;
+    F.nslots = (unsigned)slots_of(L);
     long long stride = 1;
     for (int d = MD - 1; d >= 0; --d) {
         F.n[d] = A.X.n[d];
@@ -552,22 +439,20 @@ int hjv_measure(const hjh_grid* g, const void* a, int64_t nfields, int64_t strid
     A.stride_b = b && nfields_b > 1 ? stride_b : 0;
     A.slots = (unsigned long long*)workspace;
     A.level = level;
-    A.nslots = (unsigned)L.slots;
+    A.nslots = F.nslots;
     hipStream_t st = (hipStream_t)stream;
     const bool a64 = g->dtype == HJ_F64;
-    if (!b) return a64 ? run_ndim<double, double, false>(g->ndim, A, L, F, a, nullptr, records, st) : run_ndim<float, float, false>(g->ndim, A, L, F, a, nullptr, records, st);
+    if (!b) return a64 ? run_ndim<double, double, false>(g->ndim, A, L, nfields, F, a, nullptr, records, st) : run_ndim<float, float, false>(g->ndim, A, L, nfields, F, a, nullptr, records, st);
     const bool b64 = b_dtype == HJ_F64;
-    if (a64) return b64 ? run_ndim<double, double, true>(g->ndim, A, L, F, a, b, records, st) : run_ndim<double, float, true>(g->ndim, A, L, F, a, b, records, st);
-    return b64 ? run_ndim<float, double, true>(g->ndim, A, L, F, a, b, records, st) : run_ndim<float, float, true>(g->ndim, A, L, F, a, b, records, st);
+    if (a64) return b64 ? run_ndim<double, double, true>(g->ndim, A, L, nfields, F, a, b, records, st) : run_ndim<double, float, true>(g->ndim, A, L, nfields, F, a, b, records, st);
+    return b64 ? run_ndim<float, double, true>(g->ndim, A, L, nfields, F, a, b, records, st) : run_ndim<float, float, true>(g->ndim, A, L, nfields, F, a, b, records, st);
 }
 
 int64_t hjv_workspace_size(const hjh_grid* g, int64_t nfields, int compare) {
     long long total = 0;
     if (check_grid(g, total) || check_fields(nfields)) return 0;
-    hjv_launch_plan L;
-    MvIndex X;
-    make_plan(g, total, nfields, L, X);
-    return nfields * (compare ? 4 : 1) * L.slots * (int64_t)(WORDS * sizeof(unsigned long long));
+    Index X;
+    return nfields * (compare ? 4 : 1) * slots_of(make_plan(g, total, BLOCK, X)) * (int64_t)(WORDS * sizeof(unsigned long long));
 }
 
 int hjv_plan(const hjh_grid* g, int64_t nfields, hjv_launch_plan* plan) {
@@ -575,8 +460,12 @@ int hjv_plan(const hjh_grid* g, int64_t nfields, hjv_launch_plan* plan) {
     if (int rc = check_grid(g, total)) return rc;
     if (int rc = check_fields(nfields)) return rc;
     if (!plan) return fail(HJ_EINVAL, "null argument");
-    MvIndex X;
-    make_plan(g, total, nfields, *plan, X);
+    Index X;
+    const Plan L = make_plan(g, total, BLOCK, X);
+    publish(L, *plan);
+    plan->nfields = nfields;
+    plan->field_launches = (int32_t)((nfields + MAX_Y - 1) / MAX_Y);
+    plan->slots = slots_of(L);
     return HJ_OK;
 }
 
@@ -584,25 +473,10 @@ int hjv_decode(const hjh_grid* g, int64_t node, int32_t idx[6]) {
     long long total = 0;
     if (int rc = check_grid(g, total)) return rc;
     if (!idx) return fail(HJ_EINVAL, "null argument");
-    if (node < 0 || node >= total) return fail(HJ_EINVAL, "node %lld: the grid has nodes 0 .. %lld", (long long)node, total - 1);
-    hjv_launch_plan L;
-    MvIndex X;
-    make_plan(g, total, 1, L, X);
-    // the launch, workgroup and thread that own the node, as run() and the kernel lay them out
-    const long long head = node / L.tail, t = node % L.tail;
-    const long long launch = head / L.heads_per_launch;
-    set_head(X, launch * L.heads_per_launch);
-    const unsigned block = (unsigned)((head - launch * L.heads_per_launch) * L.chunks + t / BLOCK);
-    const unsigned lane = (unsigned)(t % BLOCK);
-    for (int d = 0; d < MD; ++d) idx[d] = 0;
-    switch (g->ndim) {
-        case 1: decode_nd<1>(X, block, lane, idx); break;
-        case 2: decode_nd<2>(X, block, lane, idx); break;
-        case 3: decode_nd<3>(X, block, lane, idx); break;
-        case 4: decode_nd<4>(X, block, lane, idx); break;
-        case 5: decode_nd<5>(X, block, lane, idx); break;
-        default: decode_nd<6>(X, block, lane, idx); break;
-    }
+    if (int rc = check_node(node, total)) return rc;
+    Index X;
+    const Plan L = make_plan(g, total, BLOCK, X);
+    decode(L, X, g->ndim, node, idx);
     return HJ_OK;
 }
 
@@ -611,14 +485,7 @@ int hjv_simplex_q_host(int D, const double* f, uint64_t* q) {
     if (!f || !q) return fail(HJ_EINVAL, "null argument");
     for (int k = 0; k <= D; ++k)
         if (!std::isfinite(f[k])) return fail(HJ_EINVAL, "f[%d] is not finite: such a cell is invalid and has no simplex", k);
-    switch (D) {
-        case 1: *q = simplex_host<1>(f); break;
-        case 2: *q = simplex_host<2>(f); break;
-        case 3: *q = simplex_host<3>(f); break;
-        case 4: *q = simplex_host<4>(f); break;
-        case 5: *q = simplex_host<5>(f); break;
-        default: *q = simplex_host<6>(f); break;
-    }
+    *q = dispatch_ndim(D, [&](auto d) { return simplex_host<decltype(d)::value>(f); });
     return HJ_OK;
 }
 

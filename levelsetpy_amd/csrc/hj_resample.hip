@@ -7,10 +7,10 @@
 //                                   of all K with FOLD) and stores the array's maximum there
 // The interpolant is not restated: it is hj_query_dev.h's locate / interp_value, compiled at six axes (HJ_QUERY_MAXD) the way
 // hj_hiquery.hip compiles them, on the grid with `ndim` overwritten by the template's constant (at<ND>), so lo / w and the 2^ND
-// corner loop stay in registers.  The fold is hj_shapes_dev.h's nmin / nmax.  The node decode is hj_hishapes.hip's scheme (tail /
+// corner loop stay in registers.  The fold is hj_shapes_dev.h's nmin / nmax.  The node decode is hj_index_dev.h's walk (tail /
 // head split, host-prepared reciprocals, blockIdx.x split in 32 bits: nothing divides) at a compile-time number of axes.
 // The map row and the field are read through blockIdx.y and the loop over members is the same in every lane: scalar loads and
-// wave-uniform branches.  `split_block` and `node_index` are __host__ __device__: hjm_decode runs them on the host.
+// wave-uniform branches.
 // Registers (make resource-usage-resample): no instantiation uses scratch or spills a register.  That takes three measures, each
 // explained where it stands: the fold reads the source grid again per member (member_grid) and the map one line at a time
 // (image<ND, true>), and the unfolded 6-D kernel carries the grid's bounds in vector registers under a bound of six waves per SIMD.
@@ -22,6 +22,7 @@
 #include "../../include/hj_hidim.h"
 #include "hj_query_dev.h"
 #include "hj_shapes_dev.h"
+#include "hj_index_dev.h"
 #include "../../include/hj_resample.h"
 
 static_assert(HJ_QUERY_MAXD == HJM_MAX_DIM, "the interpolant is compiled at the header's width");
@@ -29,6 +30,7 @@ static_assert(HJ_QUERY_MAXD == HJM_MAX_DIM, "the interpolant is compiled at the 
 namespace hjm {
 
 using namespace hj_tool;
+using namespace hj_index;
 using hjq::QGrid;
 using hjq::at;
 using hjg_dev::nmin;
@@ -38,23 +40,11 @@ using hjg_dev::MAX_Y;
 constexpr int BLOCK = 256;
 constexpr int WAVE = 64;
 constexpr int MD = HJM_MAX_DIM;
-constexpr long long MAX_X = 0x7fffffffll;   // gridDim.x of one launch
 constexpr int SLOTS = HJM_COUNT_SLOTS;       // partial counts per output array
-
-// what the decode reads: the destination's extents (1 past ndim), their reciprocals and the split of blockIdx.x
-struct RsIndex {
-    unsigned long long recip[MD];           // floor(2^64 / n) + 1 for n > 1: quotient
-    unsigned long long chunk_recip;         // the same of `chunks`
-    unsigned n[MD];                         // nodes per axis
-    unsigned h0[MD];                        // multi-index of this launch's first head index (tail axes: 0)
-    unsigned chunks;                        // workgroups per head index
-    unsigned tail;                          // nodes of the tail, below 2^31
-    int first_tail;                         // axes first_tail .. ndim - 1 are the tail
-};
 
 struct RsArgs {
     QGrid G;                                // the source
-    RsIndex X;                              // the destination
+    Index X;                                // the destination's extents and the split of blockIdx.x
     const double* coord[MD];                // the destination's coordinate vectors
     const double* maps;                     // K rows of ndim * ndim + ndim, or null: the identity
     long long total;                        // nodes of the destination
@@ -72,53 +62,6 @@ struct RsArgs {
     int fill_mode;
     int out_f64;
 };
-
-// floor(v / n) for any 32-bit v by the reciprocal r = floor(2^64 / n) + 1 of n > 1: the high 64 bits of v * r
-__host__ __device__ __forceinline__ unsigned quotient(unsigned v, unsigned long long r) {
-    const unsigned long long lo = (unsigned long long)v * (unsigned)r;
-    const unsigned long long hi = (unsigned long long)v * (unsigned)(r >> 32);
-    return (unsigned)((hi + (lo >> 32)) >> 32);
-}
-
-// blockIdx.x = head' * chunks + chunk -> head' (counted from this launch's first head index) and the chunk; wave-uniform
-__host__ __device__ __forceinline__ void split_block(const RsIndex& X, unsigned block, unsigned& hl, unsigned& chunk) {
-    hl = block;
-    chunk = 0u;
-    if (X.chunks > 1u) {
-        hl = quotient(block, X.chunk_recip);
-        chunk = block - hl * X.chunks;
-    }
-}
-
-// The multi-index of tail node t of head index h0 + hl on a grid of ND axes.  The tail axes divide t, a lane's own value; the head
-// axes add hl to the launch's first head index with carry, wave-uniform.
-template <int ND>
-__host__ __device__ __forceinline__ void node_index(const RsIndex& X, unsigned hl, unsigned t, unsigned (&idx)[ND]) {
-    unsigned up = hl;
-#pragma unroll
-    for (int d = ND - 1; d >= 0; --d) {
-        if (d > X.first_tail) {
-            idx[d] = 0u;
-            if (X.n[d] > 1u) {
-                const unsigned q = quotient(t, X.recip[d]);
-                idx[d] = t - q * X.n[d];
-                t = q;
-            }
-        } else if (d == X.first_tail) {
-            idx[d] = t;
-        } else if (d > 0) {
-            const unsigned v = X.h0[d] + up;                     // both below 2^31
-            idx[d] = 0u;
-            up = v;                                              // an axis of one node passes the carry on
-            if (X.n[d] > 1u) {
-                up = quotient(v, X.recip[d]);
-                idx[d] = v - up * X.n[d];
-            }
-        } else {
-            idx[0] = X.h0[0] + up;
-        }
-    }
-}
 
 // what a lane of either kernel starts from: whether it owns a node, the node's coordinates and its flat index
 template <int ND> struct Node {
@@ -310,49 +253,7 @@ __global__ __launch_bounds__(BLOCK) void resample_counts_kernel(const unsigned l
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static unsigned long long recip64(unsigned n) { return n > 1u ? 0xffffffffffffffffull / n + 1ull : 0ull; }
-
 static long long arrays_of(int64_t nfields, int64_t K, int reduce) { return reduce == HJM_REDUCE_NONE ? K * nfields : nfields; }
-
-// the split of the destination's axes, the launches and what the decode reads of them (X.h0 is set per launch)
-static void make_plan(const hjh_grid* g, long long total, long long arrays, hjm_launch_plan& L, RsIndex& X) {
-    L = hjm_launch_plan{};
-    X = RsIndex{};
-    for (int d = 0; d < MD; ++d) {
-        X.n[d] = d < g->ndim ? (unsigned)g->N[d] : 1u;
-        X.recip[d] = recip64(X.n[d]);
-    }
-    L.arrays = arrays;
-    L.array_launches = (int32_t)((arrays + MAX_Y - 1) / MAX_Y);
-    L.total = total;
-    long long tail = 1;
-    int ft = g->ndim;
-    while (ft > 0 && tail * (long long)X.n[ft - 1] < 0x80000000ll) tail *= (long long)X.n[--ft];       // the last axis always fits
-    L.first_tail = ft;
-    L.tail = tail;
-    L.head = total / tail;
-    L.chunks = (tail + BLOCK - 1) / BLOCK;
-    L.heads_per_launch = std::min<long long>(L.head, MAX_X / L.chunks);
-    L.launches = (L.head + L.heads_per_launch - 1) / L.heads_per_launch;
-    L.blocks_full = L.heads_per_launch * L.chunks;
-    L.blocks_last = (L.head - (L.launches - 1) * L.heads_per_launch) * L.chunks;
-    if (L.launches == 1) L.blocks_full = L.blocks_last;
-    X.chunks = (unsigned)L.chunks;
-    X.chunk_recip = recip64(X.chunks);
-    X.tail = (unsigned)tail;
-    X.first_tail = ft;
-}
-
-// the multi-index of head index `head` into X.h0: the one place that divides, on the host
-static void set_head(RsIndex& X, long long head) {
-    for (int d = MD - 1; d >= 0; --d) {
-        X.h0[d] = 0u;
-        if (d < X.first_tail) {
-            X.h0[d] = (unsigned)(head % (long long)X.n[d]);
-            head /= (long long)X.n[d];
-        }
-    }
-}
 
 // the destination: ndim as the source's, 1 .. 2^31 - 1 nodes per axis, at most 2^63 - 1 in all
 static int check_dst(const hjh_grid* dst, int ndim, long long& total) {
@@ -374,38 +275,33 @@ static int check_batch(int64_t nfields, int64_t K, int reduce, long long total) 
 
 // every launch of one kernel: along the head, and per head launch along the output arrays.  launch(blocks, ny)
 template <typename F>
-static int all_launches(RsArgs& A, const hjm_launch_plan& L, int reduce, F&& launch) {
-    for (long long l = 0; l < L.launches; ++l) {
-        const long long head = l * L.heads_per_launch;
-        set_head(A.X, head);
-        A.node0 = head * L.tail;
-        const unsigned blocks = (unsigned)(l + 1 < L.launches ? L.blocks_full : L.blocks_last);
-        for (long long a0 = 0; a0 < L.arrays; a0 += MAX_Y) {
+static int all_launches(RsArgs& A, const Plan& L, long long arrays, int reduce, F&& launch) {
+    return head_launches(L, A.X, A.node0, [&](unsigned blocks) {
+        for (long long a0 = 0; a0 < arrays; a0 += MAX_Y) {
             A.a0 = a0;
             A.k0 = reduce == HJM_REDUCE_NONE ? a0 / A.nfields : 0;
             A.f0 = (unsigned)(reduce == HJM_REDUCE_NONE ? a0 % A.nfields : a0);
-            launch(blocks, (unsigned)(L.arrays - a0 < MAX_Y ? L.arrays - a0 : MAX_Y));
+            launch(blocks, (unsigned)(arrays - a0 < MAX_Y ? arrays - a0 : MAX_Y));
             HIP_TRY(hipGetLastError());
         }
-    }
-    return HJ_OK;
+        return (int)HJ_OK;
+    });
 }
 
 template <typename T, int ND, int REDUCE>
-static int run(RsArgs& A, const hjm_launch_plan& L, long long* inside_counts, const void* data, void* out, hipStream_t stream) {
-    HIP_TRY(hipMemsetAsync(A.keys, 0, (size_t)hjm_workspace_size(L.arrays), stream));            // the keys and the partial counts
-    int rc = all_launches(A, L, REDUCE, [&](unsigned blocks, unsigned ny) {
+static int run(RsArgs& A, const Plan& L, long long arrays, long long* inside_counts, const void* data, void* out, hipStream_t stream) {
+    HIP_TRY(hipMemsetAsync(A.keys, 0, (size_t)hjm_workspace_size(arrays), stream));              // the keys and the partial counts
+    int rc = all_launches(A, L, arrays, REDUCE, [&](unsigned blocks, unsigned ny) {
         hipLaunchKernelGGL((resample_kernel<T, ND, REDUCE>), dim3(blocks, ny), dim3(BLOCK), 0, stream, A, (const T*)data, out);
     });
     if (rc) return rc;
     launched(kernel_name("resample_kernel", type_tag<T>::name(), {ND, REDUCE}).c_str());
-    hipLaunchKernelGGL(resample_counts_kernel, dim3((unsigned)((L.arrays + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, A.counts, inside_counts,
-                       (long long)L.arrays);
+    hipLaunchKernelGGL(resample_counts_kernel, dim3((unsigned)((arrays + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, stream, A.counts, inside_counts, arrays);
     HIP_TRY(hipGetLastError());
     launched_also("resample_counts_kernel");
     if (A.fill_mode != HJM_FILL_MAX) return HJ_OK;
     constexpr int FOLD = REDUCE == HJM_REDUCE_NONE ? HJM_REDUCE_NONE : HJM_REDUCE_MIN;       // the geometry of min and max is one
-    rc = all_launches(A, L, REDUCE, [&](unsigned blocks, unsigned ny) {
+    rc = all_launches(A, L, arrays, REDUCE, [&](unsigned blocks, unsigned ny) {
         hipLaunchKernelGGL((resample_fill_kernel<ND, FOLD>), dim3(blocks, ny), dim3(BLOCK), 0, stream, A, out);
     });
     if (rc) return rc;
@@ -414,30 +310,15 @@ static int run(RsArgs& A, const hjm_launch_plan& L, long long* inside_counts, co
 }
 
 template <typename T, int ND>
-static int run_reduce(int reduce, RsArgs& A, const hjm_launch_plan& L, long long* counts, const void* data, void* out, hipStream_t stream) {
-    if (reduce == HJM_REDUCE_NONE) return run<T, ND, HJM_REDUCE_NONE>(A, L, counts, data, out, stream);
-    if (reduce == HJM_REDUCE_MIN) return run<T, ND, HJM_REDUCE_MIN>(A, L, counts, data, out, stream);
-    return run<T, ND, HJM_REDUCE_MAX>(A, L, counts, data, out, stream);
+static int run_reduce(int reduce, RsArgs& A, const Plan& L, long long arrays, long long* counts, const void* data, void* out, hipStream_t stream) {
+    if (reduce == HJM_REDUCE_NONE) return run<T, ND, HJM_REDUCE_NONE>(A, L, arrays, counts, data, out, stream);
+    if (reduce == HJM_REDUCE_MIN) return run<T, ND, HJM_REDUCE_MIN>(A, L, arrays, counts, data, out, stream);
+    return run<T, ND, HJM_REDUCE_MAX>(A, L, arrays, counts, data, out, stream);
 }
 
 template <typename T>
-static int run_ndim(int ndim, int reduce, RsArgs& A, const hjm_launch_plan& L, long long* counts, const void* data, void* out, hipStream_t stream) {
-    switch (ndim) {
-        case 1: return run_reduce<T, 1>(reduce, A, L, counts, data, out, stream);
-        case 2: return run_reduce<T, 2>(reduce, A, L, counts, data, out, stream);
-        case 3: return run_reduce<T, 3>(reduce, A, L, counts, data, out, stream);
-        case 4: return run_reduce<T, 4>(reduce, A, L, counts, data, out, stream);
-        case 5: return run_reduce<T, 5>(reduce, A, L, counts, data, out, stream);
-        default: return run_reduce<T, 6>(reduce, A, L, counts, data, out, stream);
-    }
-}
-
-template <int ND>
-static void decode_nd(const RsIndex& X, unsigned block, unsigned lane, int32_t* idx) {
-    unsigned own[ND], hl = 0u, chunk = 0u;
-    split_block(X, block, hl, chunk);
-    node_index<ND>(X, hl, chunk * (unsigned)BLOCK + lane, own);
-    for (int d = 0; d < ND; ++d) idx[d] = (int32_t)own[d];
+static int run_ndim(int reduce, RsArgs& A, const Plan& L, long long arrays, long long* counts, const void* data, void* out, hipStream_t stream) {
+    return dispatch_ndim(A.G.ndim, [&](auto nd) { return run_reduce<T, decltype(nd)::value>(reduce, A, L, arrays, counts, data, out, stream); });
 }
 
 }  // namespace hjm
@@ -469,8 +350,8 @@ int hjm_resample(const hjh_grid* src, const hjh_grid* dst, const double* const* 
     for (int d = 0; d < A.G.ndim; ++d)
         if (!coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
 
-    hjm_launch_plan L;
-    make_plan(dst, total, arrays_of(nfields, K, reduce), L, A.X);
+    const Plan L = make_plan(dst, total, BLOCK, A.X);
+    const long long arrays = arrays_of(nfields, K, reduce);
     for (int d = 0; d < A.G.ndim; ++d) A.coord[d] = coord[d];
     A.maps = maps;
     A.total = total;
@@ -479,12 +360,12 @@ int hjm_resample(const hjh_grid* src, const hjh_grid* dst, const double* const* 
     A.nfields = (unsigned)nfields;
     A.field_recip = recip64(A.nfields);
     A.keys = (unsigned long long*)workspace;
-    A.counts = A.keys + L.arrays;
+    A.counts = A.keys + arrays;
     A.fill_value = fill_value;
     A.fill_mode = fill_mode;
     A.out_f64 = out_dtype == HJ_F64;
-    if (src->dtype == HJ_F64) return run_ndim<double>(A.G.ndim, reduce, A, L, (long long*)inside_counts, data, out, (hipStream_t)stream);
-    return run_ndim<float>(A.G.ndim, reduce, A, L, (long long*)inside_counts, data, out, (hipStream_t)stream);
+    if (src->dtype == HJ_F64) return run_ndim<double>(reduce, A, L, arrays, (long long*)inside_counts, data, out, (hipStream_t)stream);
+    return run_ndim<float>(reduce, A, L, arrays, (long long*)inside_counts, data, out, (hipStream_t)stream);
 }
 
 int64_t hjm_workspace_size(int64_t arrays) { return arrays > 0 ? arrays * (int64_t)((1 + SLOTS) * sizeof(unsigned long long)) : 0; }
@@ -494,8 +375,10 @@ int hjm_plan(const hjh_grid* dst, int64_t nfields, int64_t K, int reduce, hjm_la
     if (int rc = check_dst(dst, 0, total)) return rc;
     if (int rc = check_batch(nfields, K, reduce, total)) return rc;
     if (!plan) return fail(HJ_EINVAL, "null argument");
-    RsIndex X;
-    make_plan(dst, total, arrays_of(nfields, K, reduce), *plan, X);
+    Index X;
+    publish(make_plan(dst, total, BLOCK, X), *plan);
+    plan->arrays = arrays_of(nfields, K, reduce);
+    plan->array_launches = (int32_t)((plan->arrays + MAX_Y - 1) / MAX_Y);
     return HJ_OK;
 }
 
@@ -503,25 +386,10 @@ int hjm_decode(const hjh_grid* dst, int64_t node, int32_t idx[6]) {
     long long total = 0;
     if (int rc = check_dst(dst, 0, total)) return rc;
     if (!idx) return fail(HJ_EINVAL, "null argument");
-    if (node < 0 || node >= total) return fail(HJ_EINVAL, "node %lld: the grid has nodes 0 .. %lld", (long long)node, total - 1);
-    hjm_launch_plan L;
-    RsIndex X;
-    make_plan(dst, total, 1, L, X);
-    // the launch, workgroup and thread that own the node, as all_launches and the kernels lay them out
-    const long long head = node / L.tail, t = node % L.tail;
-    const long long launch = head / L.heads_per_launch;
-    set_head(X, launch * L.heads_per_launch);
-    const unsigned block = (unsigned)((head - launch * L.heads_per_launch) * L.chunks + t / BLOCK);
-    const unsigned lane = (unsigned)(t % BLOCK);
-    for (int d = 0; d < MD; ++d) idx[d] = 0;
-    switch (dst->ndim) {
-        case 1: decode_nd<1>(X, block, lane, idx); break;
-        case 2: decode_nd<2>(X, block, lane, idx); break;
-        case 3: decode_nd<3>(X, block, lane, idx); break;
-        case 4: decode_nd<4>(X, block, lane, idx); break;
-        case 5: decode_nd<5>(X, block, lane, idx); break;
-        default: decode_nd<6>(X, block, lane, idx); break;
-    }
+    if (int rc = check_node(node, total)) return rc;
+    Index X;
+    const Plan L = make_plan(dst, total, BLOCK, X);
+    decode(L, X, dst->ndim, node, idx);
     return HJ_OK;
 }
 

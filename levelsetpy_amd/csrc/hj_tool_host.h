@@ -1,6 +1,6 @@
-// Host layer of the stateless libraries (libhj_query.so, libhj_surface.so, libhj_ttr.so, libhj_rollout.so, libhj_batch.so, libhj_shapes.so, libhj_decomp.so, libhj_eikonal.so, libhj_hidim.so, libhj_hiquery.so, libhj_plant.so, libhj_hishapes.so): the
-// error text, the record of the kernels the last successful call launched, the argument checks more than one of them makes, and the
-// (dtype, scheme) dispatch of the point and rollout kernels.
+// Host layer of the stateless libraries (every library the Makefile builds beside libhj_mi355x.so): the error text, the record of
+// the kernels the last successful call launched, the argument checks more than one of them makes, the (dtype, scheme) dispatch of
+// the point and rollout kernels and the ndim dispatch of the 1-D to 6-D kernels.
 // Host code only.  Every one of these libraries is ONE translation unit that includes this header once, so the `static
 // thread_local` records below are that library's own: a refusal in libhj_query.so leaves hjt_last_error() as it was.
 // (libhj_mi355x.so has a record of its own, shared by its objects: hj_host.h.)
@@ -90,6 +90,18 @@ template <typename F> static int dispatch(int dtype, int scheme, F&& f) {
         return f(t, int_c<HJ_WENO5_ASSHIPPED>{});
     };
     return dtype == HJ_F64 ? schemes(type_tag<double>{}) : schemes(type_tag<float>{});
+}
+
+// ndim -> a compile-time constant: f(int_c<1>) .. f(int_c<6>) for a checked number of axes (or of a simplex's dimensions)
+template <typename F> static auto dispatch_ndim(int ndim, F&& f) {
+    switch (ndim) {
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 3: return f(int_c<3>{});
+        case 4: return f(int_c<4>{});
+        case 5: return f(int_c<5>{});
+        default: return f(int_c<6>{});
+    }
 }
 
 // what launch_done records: "kernel<double, 0, 2>" from the kernel's name, its element type and its integer arguments

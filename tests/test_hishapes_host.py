@@ -3,10 +3,9 @@
   * the argument checks of hjk_evaluate, hjk_plan and hjk_decode (the refusals of tests/tool_lib_cases.py, and valid programs up
     to the null output): every output pointer is null and every check comes before the first HIP call, so no
     device is touched -- a bad program is a refusal with a message, never a launch;
-  * hjk_plan: the launches cover every node exactly once, on grids below and past 2^32 nodes and where one launch's gridDim.x
-    does not hold the grid;
-  * hjk_decode: the DEVICE decode function run on the host against np.unravel_index, on the nodes either side of 2^31, 2^32
-    and 2^33 and on random nodes -- the precedent of tests/test_large_plans.py: no device sees these grids;
+  * hjk_plan of the named grids and of the members past gridDim.y = 65535; what hjk_plan and hjk_decode refuse (that the launches
+    cover every node once and that the decode is np.unravel_index: tests/test_node_index_host.py, for the three libraries that
+    share the walk);
   * the binding, the header and the export table name the same functions; the Makefile keeps its old lines.
 """
 import ctypes as C
@@ -15,7 +14,6 @@ import re
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -104,38 +102,7 @@ def test_a_refusal_leaves_the_shape_librarys_record_alone():
     assert rc == EINVAL and "leaves 2" in err and G.lib().hjg_last_error() == before
 
 
-# ------------------------------------------------------------------------------------------ the plan
-BIG = [(25,) * 6, (41,) * 6, (3, 2 ** 31 - 1), (65535, 65535, 2), (41, 41, 41, 41, 41, 80), (46341, 46341, 2 ** 31 - 1)]
-SMALL = [(7, 6, 8, 5, 9), (1, 1, 1, 1, 1, 1), (1, 2, 3, 25, 41, 70), (65535,), (37,), (5, 5, 6, 5, 70), (2, 2, 2, 2, 2), (3, 1, 4, 1, 5, 1)]
-
-
-def nodes_of(N):
-    total = 1
-    for n in N:
-        total *= int(n)
-    return total
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_the_plan_covers_every_node_exactly_once(N):
-    p = K.plan(N)
-    total = nodes_of(N)
-    assert p.total == total and p.head * p.tail == total and 1 <= p.tail < 2 ** 31
-    # the tail is the LONGEST suffix below 2^31: one more axis would pass it
-    assert p.tail == nodes_of(N[p.first_tail:]) and (p.first_tail == 0 or p.tail * N[p.first_tail - 1] >= 2 ** 31)
-    # a workgroup owns 256 consecutive tail nodes of one head index: the chunks of a head index cover its tail, the last one partly
-    assert (p.chunks - 1) * 256 < p.tail <= p.chunks * 256
-    # the launches split the head indices, none beyond gridDim.x
-    assert p.launches >= 1 and (p.launches - 1) * p.heads_per_launch < p.head <= p.launches * p.heads_per_launch
-    last_heads = p.head - (p.launches - 1) * p.heads_per_launch
-    assert p.blocks_last == last_heads * p.chunks and 1 <= p.blocks_last <= 2 ** 31 - 1
-    if p.launches > 1:
-        assert p.blocks_full == p.heads_per_launch * p.chunks <= 2 ** 31 - 1
-        assert (p.heads_per_launch + 1) * p.chunks > 2 ** 31 - 1           # a full launch is as large as gridDim.x lets it be
-    assert (p.launches - 1) * p.blocks_full + p.blocks_last == p.head * p.chunks
-    assert p.member_launches == 1
-
-
+# ------------------------------------------------------------------------------------------ the plan (its walk: tests/test_node_index_host.py)
 def test_plan_of_the_named_grids():
     p = K.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
@@ -157,41 +124,7 @@ def test_plan_refuses_what_the_grid_check_refuses():
         refused(case)
 
 
-# ------------------------------------------------------------------------------------------ the decode
-def crossings(total):
-    out = [0, total - 1]
-    for b in (2 ** 31, 2 ** 32, 2 ** 33):
-        out += [n for n in (b - 2, b - 1, b, b + 1) if 0 <= n < total]
-    return out
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_decode_is_unravel_index(N):
-    total = nodes_of(N)
-    rng = np.random.default_rng(total % (2 ** 32))
-    nodes = crossings(total) + [int(v) for v in rng.integers(0, total, 10000, dtype=np.int64)]
-    # the ends of rows, of workgroups and of waves
-    nodes += [n for n in (63, 64, 255, 256, N[-1] - 1, N[-1], nodes_of(N[-2:]) - 1, nodes_of(N[-2:])) if 0 <= n < total]
-    lib, g, idx = K.lib(), K.grid_descriptor(N), (C.c_int32 * 6)()
-    arr = np.array(nodes, dtype=object)
-    want = np.empty((len(nodes), len(N)), dtype=np.int64)
-    rest = arr
-    for d in range(len(N) - 1, -1, -1):                   # np.unravel_index in Python integers: 2^62 nodes pass int64 products
-        want[:, d] = [int(r) % int(N[d]) for r in rest]
-        rest = [int(r) // int(N[d]) for r in rest]
-    small = total < 2 ** 62
-    if small:
-        assert np.array_equal(want, np.stack(np.unravel_index(np.array(nodes, dtype=np.int64), N), axis=1))
-    for n, w in zip(nodes, want):
-        assert lib.hjk_decode(C.byref(g), n, C.byref(idx)) == OK
-        assert tuple(idx[:len(N)]) == tuple(w) and all(v == 0 for v in idx[len(N):]), (N, n)
-
-
-def test_decode_past_the_crossings_exists_in_the_cases():
-    assert nodes_of((41,) * 6) > 2 ** 32 and nodes_of((41, 41, 41, 41, 41, 80)) > 2 ** 33 and nodes_of((3, 2 ** 31 - 1)) > 2 ** 32
-    assert K.decode((41,) * 6, 2 ** 32) == tuple(int(v) for v in np.unravel_index(2 ** 32, (41,) * 6))
-
-
+# ------------------------------------------------------------------------------------------ the decode (against unravel_index: tests/test_node_index_host.py)
 def test_decode_refuses_a_node_outside_the_grid():
     rows = [c for c in T.CASES if c[1] in ("decode-node-1", "decode-node60", "decode-null")]
     assert len(rows) == 3

@@ -5,8 +5,8 @@ tests/test_resample_host.py.
     dimension, with ties, exact zeros, denormal-scale and 1e300-scale values;
   * every refusal of hjv_measure by code and text: each comes before the first HIP call, so no device is touched and the last-kernel
     record stays as it was;
-  * hjv_plan: the launches cover every node exactly once, below and past 2^32 nodes; hjv_decode against np.unravel_index on the nodes
-    either side of 2^31, 2^32 and 2^33: no device sees these grids;
+  * hjv_plan of the named grids and of the fields past gridDim.y = 65535; what hjv_plan and hjv_decode refuse (that the launches
+    cover every node once, the slots and that the decode is np.unravel_index: tests/test_node_index_host.py);
   * the binding, the header and the export table name the same functions; the Makefile builds the library beside the old lines;
   * truncateGrid against the restatement, on 1 to 6 axes, and against tests/golden/truncate.npz (the reference's own, 2-D to 4-D);
     setBounds' host arithmetic on records made by the restatement; what the front end refuses, it refuses before it asks for a device.
@@ -163,37 +163,7 @@ def test_a_refusal_leaves_another_librarys_record_alone():
     assert rc == EINVAL and "level" in err and _mffi.lib().hjm_last_error() == before
 
 
-# ------------------------------------------------------------------------------------------ the plan and the decode
-BIG = [(25,) * 6, (41,) * 6, (3, 2 ** 31 - 1), (65535, 65535, 2), (41, 41, 41, 41, 41, 80), (46341, 46341, 2 ** 31 - 1)]
-SMALL = [(7, 6, 8, 5, 9), (2, 2, 2, 2, 2, 2), (2, 2, 3, 25, 41, 70), (65535,), (37,), (5, 5, 6, 5, 70), (12, 7), (9, 12, 10), (3, 3)]
-
-
-def nodes_of(N):
-    total = 1
-    for n in N:
-        total *= int(n)
-    return total
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_the_plan_covers_every_node_exactly_once(N):
-    p = V.plan(N)
-    total = nodes_of(N)
-    assert p.total == total and p.head * p.tail == total and 1 <= p.tail < 2 ** 31
-    assert p.tail == nodes_of(N[p.first_tail:]) and (p.first_tail == 0 or p.tail * N[p.first_tail - 1] >= 2 ** 31)
-    assert (p.chunks - 1) * 256 < p.tail <= p.chunks * 256
-    assert p.launches >= 1 and (p.launches - 1) * p.heads_per_launch < p.head <= p.launches * p.heads_per_launch
-    last_heads = p.head - (p.launches - 1) * p.heads_per_launch
-    assert p.blocks_last == last_heads * p.chunks and 1 <= p.blocks_last <= 2 ** 31 - 1
-    if p.launches > 1:
-        assert p.blocks_full == p.heads_per_launch * p.chunks <= 2 ** 31 - 1
-        assert (p.heads_per_launch + 1) * p.chunks > 2 ** 31 - 1
-    assert (p.launches - 1) * p.blocks_full + p.blocks_last == p.head * p.chunks
-    assert p.nfields == 1 and p.field_launches == 1
-    blocks = p.head * p.chunks
-    assert p.slots == min(32, 1 << max(0, (blocks - 1).bit_length())) and p.slots & (p.slots - 1) == 0
-
-
+# ------------------------------------------------------------------------------------------ the plan and the decode (their walk: tests/test_node_index_host.py)
 def test_plan_of_the_named_grids_and_of_the_fields():
     p = V.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
@@ -219,37 +189,6 @@ def test_plan_and_decode_refuse_what_the_grid_check_refuses():
     for node in (-1, 60):
         assert lib.hjv_decode(C.byref(g), node, C.byref(idx)) == EINVAL and "node" in lib.hjv_last_error().decode()
     assert lib.hjv_decode(C.byref(g), 0, None) == EINVAL and "null argument" in lib.hjv_last_error().decode()
-
-
-def crossings(total):
-    out = [0, total - 1]
-    for b in (2 ** 31, 2 ** 32, 2 ** 33):
-        out += [n for n in (b - 2, b - 1, b, b + 1) if 0 <= n < total]
-    return out
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_decode_is_unravel_index(N):
-    total = nodes_of(N)
-    rng = np.random.default_rng(total % (2 ** 32))
-    nodes = crossings(total) + [int(v) for v in rng.integers(0, total, 4000, dtype=np.int64)]
-    nodes += [n for n in (63, 64, 255, 256, N[-1] - 1, N[-1], nodes_of(N[-2:]) - 1, nodes_of(N[-2:])) if 0 <= n < total]
-    lib, g, idx = V.lib(), grid(N), (C.c_int32 * 6)()
-    want = np.empty((len(nodes), len(N)), dtype=np.int64)
-    rest = list(nodes)
-    for d in range(len(N) - 1, -1, -1):                   # np.unravel_index in Python integers: 2^62 nodes pass int64 products
-        want[:, d] = [int(r) % int(N[d]) for r in rest]
-        rest = [int(r) // int(N[d]) for r in rest]
-    if total < 2 ** 62:
-        assert np.array_equal(want, np.stack(np.unravel_index(np.array(nodes, dtype=np.int64), N), axis=1))
-    for n, w in zip(nodes, want):
-        assert lib.hjv_decode(C.byref(g), n, C.byref(idx)) == OK
-        assert tuple(idx[:len(N)]) == tuple(w) and all(v == 0 for v in idx[len(N):]), (N, n)
-
-
-def test_decode_past_the_crossings_exists_in_the_cases():
-    assert nodes_of((41,) * 6) > 2 ** 32 and nodes_of((41, 41, 41, 41, 41, 80)) > 2 ** 33 and nodes_of((3, 2 ** 31 - 1)) > 2 ** 32
-    assert V.decode((41,) * 6, 2 ** 32) == tuple(int(v) for v in np.unravel_index(2 ** 32, (41,) * 6))
 
 
 # ------------------------------------------------------------------------------------------ header, binding, export table

@@ -3,10 +3,8 @@ tests/test_hishapes_host.py.
 
   * every refusal of hjm_resample by message: each comes before the first HIP call, so no device is touched and the last-kernel
     record stays as it was;
-  * hjm_plan: the launches cover every destination node exactly once, below and past 2^32 nodes and where one launch's gridDim.x
-    does not hold the grid; the output arrays past gridDim.y = 65535;
-  * hjm_decode: the DEVICE decode function run on the host against np.unravel_index, on the nodes either side of 2^31, 2^32 and
-    2^33 and on random nodes: no device sees these grids;
+  * hjm_plan of the named grids and of the output arrays past gridDim.y = 65535; what hjm_plan and hjm_decode refuse (that the
+    launches cover every node once and that the decode is np.unravel_index: tests/test_node_index_host.py);
   * the binding, the header and the export table name the same functions; the Makefile builds the library beside the old lines;
   * what levelsetpy_amd.resample refuses, it refuses before it asks for a device.
 """
@@ -136,39 +134,7 @@ def test_a_refusal_leaves_another_librarys_record_alone():
     assert rc == EINVAL and "reduce 9" in err and _kffi.lib().hjk_last_error() == before
 
 
-# ------------------------------------------------------------------------------------------ the plan
-BIG = [(25,) * 6, (41,) * 6, (3, 2 ** 31 - 1), (65535, 65535, 2), (41, 41, 41, 41, 41, 80), (46341, 46341, 2 ** 31 - 1)]
-SMALL = [(7, 6, 8, 5, 9), (1, 1, 1, 1, 1, 1), (1, 2, 3, 25, 41, 70), (65535,), (37,), (5, 5, 6, 5, 70), (2, 2, 2, 2, 2), (3, 1, 4, 1, 5, 1),
-         (12, 7), (9, 12, 10), (3, 3)]
-
-
-def nodes_of(N):
-    total = 1
-    for n in N:
-        total *= int(n)
-    return total
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_the_plan_covers_every_node_exactly_once(N):
-    p = M.plan(N)
-    total = nodes_of(N)
-    assert p.total == total and p.head * p.tail == total and 1 <= p.tail < 2 ** 31
-    # the tail is the LONGEST suffix below 2^31: one more axis would pass it
-    assert p.tail == nodes_of(N[p.first_tail:]) and (p.first_tail == 0 or p.tail * N[p.first_tail - 1] >= 2 ** 31)
-    # a workgroup owns 256 consecutive tail nodes of one head index: the chunks of a head index cover its tail, the last one partly
-    assert (p.chunks - 1) * 256 < p.tail <= p.chunks * 256
-    # the launches split the head indices, none beyond gridDim.x
-    assert p.launches >= 1 and (p.launches - 1) * p.heads_per_launch < p.head <= p.launches * p.heads_per_launch
-    last_heads = p.head - (p.launches - 1) * p.heads_per_launch
-    assert p.blocks_last == last_heads * p.chunks and 1 <= p.blocks_last <= 2 ** 31 - 1
-    if p.launches > 1:
-        assert p.blocks_full == p.heads_per_launch * p.chunks <= 2 ** 31 - 1
-        assert (p.heads_per_launch + 1) * p.chunks > 2 ** 31 - 1           # a full launch is as large as gridDim.x lets it be
-    assert (p.launches - 1) * p.blocks_full + p.blocks_last == p.head * p.chunks
-    assert p.arrays == 1 and p.array_launches == 1
-
-
+# ------------------------------------------------------------------------------------------ the plan (its walk: tests/test_node_index_host.py)
 def test_plan_of_the_named_grids_and_of_the_output_arrays():
     p = M.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
@@ -197,39 +163,6 @@ def test_plan_and_decode_refuse_what_the_grid_check_refuses():
     for node in (-1, 60):
         assert lib.hjm_decode(C.byref(g), node, C.byref(idx)) == EINVAL and "node" in lib.hjm_last_error().decode()
     assert lib.hjm_decode(C.byref(g), 0, None) == EINVAL and "null argument" in lib.hjm_last_error().decode()
-
-
-# ------------------------------------------------------------------------------------------ the decode
-def crossings(total):
-    out = [0, total - 1]
-    for b in (2 ** 31, 2 ** 32, 2 ** 33):
-        out += [n for n in (b - 2, b - 1, b, b + 1) if 0 <= n < total]
-    return out
-
-
-@pytest.mark.parametrize("N", BIG + SMALL, ids=lambda N: "x".join(map(str, N)))
-def test_decode_is_unravel_index(N):
-    total = nodes_of(N)
-    rng = np.random.default_rng(total % (2 ** 32))
-    nodes = crossings(total) + [int(v) for v in rng.integers(0, total, 4000, dtype=np.int64)]
-    # the ends of rows, of workgroups and of waves
-    nodes += [n for n in (63, 64, 255, 256, N[-1] - 1, N[-1], nodes_of(N[-2:]) - 1, nodes_of(N[-2:])) if 0 <= n < total]
-    lib, g, idx = M.lib(), dst_grid(N), (C.c_int32 * 6)()
-    want = np.empty((len(nodes), len(N)), dtype=np.int64)
-    rest = list(nodes)
-    for d in range(len(N) - 1, -1, -1):                   # np.unravel_index in Python integers: 2^62 nodes pass int64 products
-        want[:, d] = [int(r) % int(N[d]) for r in rest]
-        rest = [int(r) // int(N[d]) for r in rest]
-    if total < 2 ** 62:
-        assert np.array_equal(want, np.stack(np.unravel_index(np.array(nodes, dtype=np.int64), N), axis=1))
-    for n, w in zip(nodes, want):
-        assert lib.hjm_decode(C.byref(g), n, C.byref(idx)) == OK
-        assert tuple(idx[:len(N)]) == tuple(w) and all(v == 0 for v in idx[len(N):]), (N, n)
-
-
-def test_decode_past_the_crossings_exists_in_the_cases():
-    assert nodes_of((41,) * 6) > 2 ** 32 and nodes_of((41, 41, 41, 41, 41, 80)) > 2 ** 33 and nodes_of((3, 2 ** 31 - 1)) > 2 ** 32
-    assert M.decode((41,) * 6, 2 ** 32) == tuple(int(v) for v in np.unravel_index(2 ** 32, (41,) * 6))
 
 
 # ------------------------------------------------------------------------------------------ header, binding, export table
