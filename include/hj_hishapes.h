@@ -38,13 +38,27 @@
  * INDEXING, and its limits.  The axes are split into a TAIL -- the longest suffix of axes whose product of extents stays
  * below 2^31 -- and the HEAD, the axes before it.  A workgroup owns 256 consecutive tail nodes of one head index; it takes
  * `chunks` = ceil(tail / 256) workgroups per head index, and blockIdx.x = head' * chunks + chunk is split in 32 bits.
- * One launch covers at most heads_per_launch = floor((2^31 - 1) / chunks) head indices; a grid with more takes further
- * launches, each given the multi-index of its first head index by the host, to which the kernel adds head' by add and
- * carry.  A thread divides its own tail node through the tail axes.  No number the kernel divides exceeds 32 bits and it
+ * One launch has fewer than 2^32 threads -- the runtime takes gridDim.x * blockDim.x modulo 2^32 and reports nothing, so a
+ * larger launch would run a part of its threads only -- and so covers at most heads_per_launch = floor((2^24 - 1) / chunks)
+ * head indices (a head index is at most 2^23 workgroups); a grid with more, every grid past 2^32 nodes among them, takes
+ * further launches, each given the multi-index of its first head index by the host, to which the kernel adds head' by add
+ * and carry.  A thread divides its own tail node through the tail axes.  No number the kernel divides exceeds 32 bits and it
  * divides by nothing: the host prepares one 64-bit reciprocal per axis, and a quotient is one multiply-high.  So a grid may
  * have up to 2^63 - 1 nodes, an axis up to 2^31 - 1; what is NOT done is to pack several head indices into one workgroup:
  * a grid whose last axis alone is short and whose last two axes together pass 2^31 runs workgroups that are mostly idle.
  * hjk_plan refuses what the grid check refuses (an axis of 2^31 nodes or more, more than 2^63 - 1 nodes) and nothing else.
+ *
+ * A TEST FACILITY: the plan's two limits can be lowered, so that a grid of a few thousand nodes takes the head axes' carry, the
+ * 64-bit node of a head index and the walk over several launches, which otherwise need more than 2^31 nodes or 2^24 workgroups.
+ * Two environment variables, decimal whole numbers, read once by every call of hjk_evaluate, hjk_plan and hjk_decode (a call's
+ * plan, decode and launches see the same values):
+ *   HJ_INDEX_TAIL_BELOW     the tail stays below this many nodes           (1 .. 2^31, unset: 2^31)
+ *   HJ_INDEX_LAUNCH_BLOCKS  one launch has at most this many workgroups    (1 .. 2^24 - 1, unset: 2^24 - 1)
+ * The grid's last axis is the tail's whatever the first says (a value at or below N[ndim - 1] counts as just above it), and a
+ * launch holds one whole head index whatever the second says (a value below `chunks` counts as `chunks`).  Anything else -- 0, a
+ * negative number, a number above the constant, text that is no number -- is refused with HJ_EINVAL, the variable named, before
+ * anything is launched.  Unset, the plan is the one described above.  The kernels are the same either way: the limits change
+ * kernel arguments and launch counts alone.
  */
 #ifndef HJ_HISHAPES_H
 #define HJ_HISHAPES_H

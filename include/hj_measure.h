@@ -47,6 +47,13 @@
  * INDEXING is hj_hishapes.h's, as in hj_resample.h: tail / head split of the axes, a workgroup owns 256 consecutive tail nodes of
  * one head index, blockIdx.x is split in 32 bits, one host-prepared reciprocal per axis and nothing divides.  blockIdx.y is the
  * field; more than 65535 fields take further launches inside the call.  Node offsets are 64-bit.
+ *
+ * A TEST FACILITY, hj_hishapes.h's: the environment variables HJ_INDEX_TAIL_BELOW (the tail stays below this many nodes, 1 .. 2^31)
+ * and HJ_INDEX_LAUNCH_BLOCKS (workgroups of one launch at most, 1 .. 2^24 - 1) lower the plan's two limits so that small grids
+ * take the head axes and several launches.  hjv_measure, hjv_workspace_size, hjv_plan and hjv_decode read them once per call (the
+ * slots follow the plan: size the workspace under the values the measurement runs with); the grid's last axis stays in the tail
+ * and a launch holds a whole head index whatever they say; a value outside its range is refused with HJ_EINVAL before anything is
+ * launched (hjv_workspace_size: 0); unset, the plan is the one above.
  */
 #ifndef HJ_MEASURE_H
 #define HJ_MEASURE_H

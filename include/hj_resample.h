@@ -35,6 +35,12 @@
  * workgroup owns 256 consecutive tail nodes of one head index, blockIdx.x = head' * chunks + chunk is split in 32 bits, and the
  * kernel divides by nothing (one host-prepared 64-bit reciprocal per axis).  blockIdx.y is the output array; more than 65535
  * of them take further launches.  Source offsets are 64-bit.
+ *
+ * A TEST FACILITY, hj_hishapes.h's: the environment variables HJ_INDEX_TAIL_BELOW (the tail stays below this many nodes, 1 .. 2^31)
+ * and HJ_INDEX_LAUNCH_BLOCKS (workgroups of one launch at most, 1 .. 2^24 - 1) lower the plan's two limits so that small
+ * destinations take the head axes and several launches.  hjm_resample, hjm_plan and hjm_decode read them once per call; the
+ * destination's last axis stays in the tail and a launch holds a whole head index whatever they say; a value outside its range is
+ * refused with HJ_EINVAL before anything is launched; unset, the plan is the one above.
  */
 #ifndef HJ_RESAMPLE_H
 #define HJ_RESAMPLE_H

@@ -85,7 +85,9 @@ int hjk_evaluate(const hjh_grid* g, const hjk_program* program, const double* pa
                  int32_t* flags, void* stream) {
     HiArgs A;
     return evaluate<true, MD>(g, program, params, K, P, out, out_dtype, flags, A, [&](auto t) {
-        const Plan L = make_plan(g, A.total, BLOCK, A.X);
+        Limits lim;
+        if (int rc = read_limits(lim, BLOCK)) return rc;
+        const Plan L = make_plan(g, A.total, BLOCK, A.X, lim);
         A.node0 = 0;
         return scene_launch<typename decltype(t)::type>(A, L, K, out, (hipStream_t)stream);
     });
@@ -97,8 +99,10 @@ int hjk_plan(const hjh_grid* g, int64_t K, hjk_launch_plan* plan) {
     if (rc) return rc;
     if ((rc = check_members(K))) return rc;
     if (!plan) return null_argument();
+    Limits lim;
+    if ((rc = read_limits(lim, BLOCK))) return rc;
     Index X;
-    publish(make_plan(g, total, BLOCK, X), *plan);
+    publish(make_plan(g, total, BLOCK, X, lim), *plan);
     plan->member_launches = (int32_t)((K + MAX_Y - 1) / MAX_Y);
     return HJ_OK;
 }
@@ -109,8 +113,10 @@ int hjk_decode(const hjh_grid* g, int64_t node, int32_t idx[6]) {
     if (rc) return rc;
     if (!idx) return null_argument();
     if ((rc = check_node(node, total))) return rc;
+    Limits lim;
+    if ((rc = read_limits(lim, BLOCK))) return rc;
     Index X;
-    const Plan L = make_plan(g, total, BLOCK, X);
+    const Plan L = make_plan(g, total, BLOCK, X, lim);
     decode(L, X, MD, node, idx);                                 // at six axes, as the kernel decodes
     return HJ_OK;
 }

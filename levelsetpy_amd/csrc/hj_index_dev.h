@@ -2,6 +2,10 @@
 // NOTHING here divides or takes a remainder by a run-time extent on the device, in 32 or in 64 bits.
 //   * the host splits the axes into a tail (the longest suffix with fewer than 2^31 nodes) and a head; a workgroup owns `block`
 //     consecutive tail nodes of ONE head index, so blockIdx.x = head' * chunks + chunk and every linear index is below 2^32;
+//   * a launch has fewer than 2^32 THREADS: the runtime takes gridDim.x * blockDim.x modulo 2^32 and says nothing, so a launch
+//     of 2^24 workgroups of 256 or more runs only the first (gridDim.x * 256) mod 2^32 threads.  (Measured on a grid of
+//     4 305 300 000 nodes: one launch of 16 817 580 workgroups stored 10 333 184 nodes, profiles/node_walk_head.txt.)  A head
+//     index is at most 2^23 workgroups, so whole head indices always fit and a grid past 2^32 nodes takes several launches;
 //   * `quotient` divides a 32-bit value by an extent with the 64-bit reciprocal the host prepared: one multiply-high, exact for
 //     every 32-bit dividend;
 //   * blockIdx.x is split, and the head index decoded, ONCE per wave from wave-uniform values (scalar registers): the head index
@@ -13,6 +17,8 @@
 #ifndef HJ_INDEX_DEV_H
 #define HJ_INDEX_DEV_H
 #include <hip/hip_runtime.h>
+#include <cerrno>
+#include <cstdlib>
 #include "../../include/hj_hidim.h"
 
 namespace hj_index {
@@ -91,14 +97,43 @@ struct Plan {
     int block;                              // threads of a workgroup
     long long total, tail, head;            // nodes of the grid; of the tail; head indices: total = head * tail
     long long chunks;                       // workgroups per head index
-    long long heads_per_launch, launches;   // gridDim.x of one launch ends at 2^31 - 1
+    long long heads_per_launch, launches;   // a launch ends below 2^32 threads (LAUNCH_THREADS)
     long long blocks_full, blocks_last;     // gridDim.x of every launch but the last, and of the last
 };
 
 static unsigned long long recip64(unsigned n) { return n > 1u ? 0xffffffffffffffffull / n + 1ull : 0ull; }
 
+// The plan's two limits: the tail has fewer than `tail_below` nodes and a launch at most `launch_blocks` workgroups.  A test
+// facility lowers them through the environment, so that small grids take the head axes' carry, the 64-bit node and the walk
+// over several launches; unset they are the constants below.
+constexpr long long LAUNCH_THREADS = 0xffffffffll;           // threads of one launch at most: see the head of this file
+struct Limits {
+    long long tail_below = 0x80000000ll;
+    long long launch_blocks = LAUNCH_THREADS / 256;
+};
+
+static int read_limit(const char* name, long long& limit) {
+    const char* text = std::getenv(name);
+    if (!text) return HJ_OK;
+    char* end = nullptr;
+    errno = 0;
+    const long long v = std::strtoll(text, &end, 10);
+    if (end == text || *end || errno || v < 1 || v > limit)
+        return hj_tool::fail(HJ_EINVAL, "%s = '%s': a whole number from 1 to %lld", name, text, limit);
+    limit = v;
+    return HJ_OK;
+}
+
+// the limits of one entry call, read once: its plan, its decode and its launches see the same
+static int read_limits(Limits& lim, int block) {
+    lim = Limits{};
+    lim.launch_blocks = LAUNCH_THREADS / block;
+    if (int rc = read_limit("HJ_INDEX_TAIL_BELOW", lim.tail_below)) return rc;
+    return read_limit("HJ_INDEX_LAUNCH_BLOCKS", lim.launch_blocks);
+}
+
 // the plan of a grid of `total` nodes for workgroups of `block` threads, and what the decode reads of it (X.h0 is set per launch)
-static Plan make_plan(const hjh_grid* g, long long total, int block, Index& X) {
+static Plan make_plan(const hjh_grid* g, long long total, int block, Index& X, const Limits& lim) {
     Plan L{};
     X = Index{};
     for (int d = 0; d < AXES; ++d) {
@@ -110,12 +145,14 @@ static Plan make_plan(const hjh_grid* g, long long total, int block, Index& X) {
     if (total == 0) return L;
     long long tail = 1;
     int ft = AXES;
-    while (ft > 0 && tail * (long long)X.n[ft - 1] < 0x80000000ll) tail *= (long long)X.n[--ft];       // the last axis always fits
+    // the grid's last axis is the tail's whatever the limit: it always fits the constant, and a lowered limit at or below its
+    // extent counts as just above it
+    while (ft > 0 && (ft >= g->ndim || tail * (long long)X.n[ft - 1] < lim.tail_below)) tail *= (long long)X.n[--ft];
     L.first_tail = ft;
     L.tail = tail;
     L.head = total / tail;
     L.chunks = (tail + block - 1) / block;
-    L.heads_per_launch = std::min<long long>(L.head, 0x7fffffffll / L.chunks);
+    L.heads_per_launch = std::min<long long>(L.head, std::max<long long>(1, lim.launch_blocks / L.chunks));   // a launch holds a whole head index
     L.launches = (L.head + L.heads_per_launch - 1) / L.heads_per_launch;
     L.blocks_full = L.heads_per_launch * L.chunks;
     L.blocks_last = (L.head - (L.launches - 1) * L.heads_per_launch) * L.chunks;

@@ -377,7 +377,7 @@ static int run(MvArgs& A, const Plan& L, long long nfields, const FoldArgs& F, c
     launched((std::string("measure_kernel<") + type_tag<TA>::name() + ", " + type_tag<TB>::name() + ", " + std::to_string(ND) + ", " +
               (CMP ? "1>" : "0>")).c_str());
     unsigned blocks = 0;
-    if (int rc = blocks_for(F.records, "more than 2^31 - 1 workgroups of records", blocks)) return rc;
+    if (int rc = blocks_for(F.records, "more than 2^32 - 1 records", blocks)) return rc;
     hipLaunchKernelGGL(measure_fold_kernel, dim3(blocks), dim3(BLOCK), 0, stream, F, (const unsigned long long*)A.slots, (unsigned long long*)records);
     HIP_TRY(hipGetLastError());
     launched_also("measure_fold_kernel");
@@ -407,6 +407,8 @@ int hjv_measure(const hjh_grid* g, const void* a, int64_t nfields, int64_t strid
     long long total = 0;
     if (int rc = check_grid(g, total)) return rc;
     if (int rc = check_fields(nfields)) return rc;
+    Limits lim;                                                  // before the workspace is looked at: hjv_workspace_size gave 0 for a limit it refused
+    if (int rc = read_limits(lim, BLOCK)) return rc;
     if (!std::isfinite(level)) return fail(HJ_EINVAL, "level is not finite");
     if (nfields > 1 && stride_a < total) return fail(HJ_EINVAL, "stride_a %lld is smaller than the grid (%lld)", (long long)stride_a, total);
     if (b) {
@@ -419,7 +421,7 @@ int hjv_measure(const hjh_grid* g, const void* a, int64_t nfields, int64_t strid
     if (!a || !records || !workspace) return fail(HJ_EINVAL, "null argument");
 
     MvArgs A{};
-    const Plan L = make_plan(g, total, BLOCK, A.X);
+    const Plan L = make_plan(g, total, BLOCK, A.X, lim);
     FoldArgs F{};
     F.records = nfields * (b ? 4 : 1);
     F.cells = 1;
@@ -450,9 +452,10 @@ int hjv_measure(const hjh_grid* g, const void* a, int64_t nfields, int64_t strid
 
 int64_t hjv_workspace_size(const hjh_grid* g, int64_t nfields, int compare) {
     long long total = 0;
-    if (check_grid(g, total) || check_fields(nfields)) return 0;
+    Limits lim;
+    if (check_grid(g, total) || check_fields(nfields) || read_limits(lim, BLOCK)) return 0;
     Index X;
-    return nfields * (compare ? 4 : 1) * slots_of(make_plan(g, total, BLOCK, X)) * (int64_t)(WORDS * sizeof(unsigned long long));
+    return nfields * (compare ? 4 : 1) * slots_of(make_plan(g, total, BLOCK, X, lim)) * (int64_t)(WORDS * sizeof(unsigned long long));
 }
 
 int hjv_plan(const hjh_grid* g, int64_t nfields, hjv_launch_plan* plan) {
@@ -460,8 +463,10 @@ int hjv_plan(const hjh_grid* g, int64_t nfields, hjv_launch_plan* plan) {
     if (int rc = check_grid(g, total)) return rc;
     if (int rc = check_fields(nfields)) return rc;
     if (!plan) return fail(HJ_EINVAL, "null argument");
+    Limits lim;
+    if (int rc = read_limits(lim, BLOCK)) return rc;
     Index X;
-    const Plan L = make_plan(g, total, BLOCK, X);
+    const Plan L = make_plan(g, total, BLOCK, X, lim);
     publish(L, *plan);
     plan->nfields = nfields;
     plan->field_launches = (int32_t)((nfields + MAX_Y - 1) / MAX_Y);
@@ -474,8 +479,10 @@ int hjv_decode(const hjh_grid* g, int64_t node, int32_t idx[6]) {
     if (int rc = check_grid(g, total)) return rc;
     if (!idx) return fail(HJ_EINVAL, "null argument");
     if (int rc = check_node(node, total)) return rc;
+    Limits lim;
+    if (int rc = read_limits(lim, BLOCK)) return rc;
     Index X;
-    const Plan L = make_plan(g, total, BLOCK, X);
+    const Plan L = make_plan(g, total, BLOCK, X, lim);
     decode(L, X, g->ndim, node, idx);
     return HJ_OK;
 }

@@ -350,7 +350,9 @@ int hjm_resample(const hjh_grid* src, const hjh_grid* dst, const double* const* 
     for (int d = 0; d < A.G.ndim; ++d)
         if (!coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
 
-    const Plan L = make_plan(dst, total, BLOCK, A.X);
+    Limits lim;
+    if (int rc = read_limits(lim, BLOCK)) return rc;
+    const Plan L = make_plan(dst, total, BLOCK, A.X, lim);
     const long long arrays = arrays_of(nfields, K, reduce);
     for (int d = 0; d < A.G.ndim; ++d) A.coord[d] = coord[d];
     A.maps = maps;
@@ -375,8 +377,10 @@ int hjm_plan(const hjh_grid* dst, int64_t nfields, int64_t K, int reduce, hjm_la
     if (int rc = check_dst(dst, 0, total)) return rc;
     if (int rc = check_batch(nfields, K, reduce, total)) return rc;
     if (!plan) return fail(HJ_EINVAL, "null argument");
+    Limits lim;
+    if (int rc = read_limits(lim, BLOCK)) return rc;
     Index X;
-    publish(make_plan(dst, total, BLOCK, X), *plan);
+    publish(make_plan(dst, total, BLOCK, X, lim), *plan);
     plan->arrays = arrays_of(nfields, K, reduce);
     plan->array_launches = (int32_t)((plan->arrays + MAX_Y - 1) / MAX_Y);
     return HJ_OK;
@@ -387,8 +391,10 @@ int hjm_decode(const hjh_grid* dst, int64_t node, int32_t idx[6]) {
     if (int rc = check_dst(dst, 0, total)) return rc;
     if (!idx) return fail(HJ_EINVAL, "null argument");
     if (int rc = check_node(node, total)) return rc;
+    Limits lim;
+    if (int rc = read_limits(lim, BLOCK)) return rc;
     Index X;
-    const Plan L = make_plan(dst, total, BLOCK, X);
+    const Plan L = make_plan(dst, total, BLOCK, X, lim);
     decode(L, X, dst->ndim, node, idx);
     return HJ_OK;
 }

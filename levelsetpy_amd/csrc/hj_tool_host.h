@@ -60,10 +60,11 @@ static int launch_done(const char* name) {
     const char* prefix##_last_kernel(void) { return ::hj_tool::g_kernels.c_str(); }
 
 // ---- checks
-// workgroups of 256 threads for `threads` threads; `refusal` is the caller's message for more than 2^31 - 1 of them
+// workgroups of 256 threads for `threads` threads; `refusal` is the caller's message for a launch of 2^32 threads or more: the
+// runtime takes gridDim.x * blockDim.x modulo 2^32 without an error, and such a launch would run only a part of its threads
 static int blocks_for(long long threads, const char* refusal, unsigned& blocks) {
     const long long b = (threads + 255) / 256;
-    if (b > 0x7fffffffll) return fail(HJ_EINVAL, "%s", refusal);
+    if (b > 0xffffffffll / 256) return fail(HJ_EINVAL, "%s", refusal);
     blocks = (unsigned)b;
     return HJ_OK;
 }

@@ -11,7 +11,10 @@ need + 8 GiB free skips and says so.  HJ_LARGE_ARRAYS_PROFILE=<file> makes the r
 
 Boxes: at most 24 a case.  In 4-D the 16 corners leave room for ONE box per chunk seam (alternately across a tile seam and elsewhere) and two
 random ones; everywhere else every seam gets both and there are four random boxes.  A launch cut into more chunks than that leaves room for
-(the 2-D grid at the default environment: 85) gets the first and the last seam and an even spread of the others."""
+(the 2-D grid at the default environment: 85) gets the first and the last seam and an even spread of the others.
+
+The last section ("walk") is the 1-D to 6-D node walk of libhj_hishapes.so, libhj_resample.so and libhj_measure.so on a 6-D grid past 2^32
+nodes, whose first two axes are head axes, and hjh_substep of libhj_hidim.so past 2^31 cells; its boxes are placed by walk_places."""
 import ctypes as C
 import os
 import sys
@@ -55,7 +58,7 @@ SYSTEMS = {
 }
 
 REPORT = []          # lines of profiles/large_arrays.txt
-HEADER = """Large arrays: the solver library and four of the stateless libraries past 2 GiB, 4 GiB and 2^31 cells
+HEADER = """Large arrays: the solver library and the stateless libraries past 2 GiB, 4 GiB, 2^31 cells and (the 6-D node walk) 2^32 nodes
 Written by tests/test_gpu_large_arrays.py (HJ_LARGE_ARRAYS_PROFILE=<this file>) on one %s; everything below this header is measured.
 
 Per case: label (A..H as in the test file; TB1 = HJ_TARGET_BLOCKS=1, the longest chunks the 4 GiB cap allows; "tuner" = the untouched default
@@ -1017,3 +1020,286 @@ def test_tools_eval_u_field_stride_past_2e31_elements():
         assert ok.sum() > 500 and np.array_equal(got[k][ok], ref[ok]), k
     _report("tools eval_u %d fields of %d^2 fp64 (field %d starts at element 2^31), 1000 states: fields 0, 1023, %d, %d bitwise" % (
         T, n, T - 1, T - 2, T - 1))
+
+
+# ------------------------------------------------------------------ the 1-D to 6-D node walk past 2^32 nodes, hidim past 2^31 cells
+# libhj_hishapes.so, libhj_resample.so and libhj_measure.so share one node walk (csrc/hj_index_dev.h).  tests/test_gpu_node_walk.py runs
+# its head axes and its launches on small grids with the plan's limits lowered; here the limits are the constants and the grid is real:
+# 4 305 300 000 nodes, 16.04 GiB per fp32 array, the tail (axes 2 .. 5, 717 550 000 nodes) times 3 past 2^31, so axes 0 and 1 are the head:
+# six head indices, one of the two head extents no power of two.  Boxes: the grid's corners, both sides of each of the five head-index
+# seams (the last tail node of head index h, the first of h + 1), the elements at flat offsets 2^31 and 2^32, four seeded random places.
+WALK_N = (2, 3, 5, 127, 1000, 1130)
+WALK_EXT = (2, 3, 2, 3, 4, 8)                                    # a box's extents: both head axes whole
+
+
+def _walk_plan(binding, *args):
+    """The published plan of WALK_N at the default limits: the form these cases mean to run."""
+    assert "HJ_INDEX_TAIL_BELOW" not in os.environ and "HJ_INDEX_LAUNCH_BLOCKS" not in os.environ
+    p = binding.plan(WALK_N, *args)
+    assert p.total == 4305300000 >= (1 << 32) and p.first_tail == 2 and p.tail == 717550000 and p.head == 6
+    assert p.tail * WALK_N[1] >= (1 << 31) > p.tail and p.chunks == (p.tail + 255) // 256
+    # a launch has fewer than 2^32 threads (one launch of all 16 817 580 workgroups ran 10 333 184 threads of them and reported nothing:
+    # profiles/node_walk_head.txt), so a grid past 2^32 nodes takes two launches at least: five head indices, then (1, 2) alone
+    assert (p.launches, p.heads_per_launch, p.blocks_full, p.blocks_last) == (2, 5, 5 * p.chunks, p.chunks) and p.blocks_full * 256 < (1 << 32)
+    return p
+
+
+def walk_places(N, tail, head, seed=99):
+    """[(kind, multi-index)]: corners, head-index seams, flat offsets 2^31 and 2^32 (where the grid has them), four random nodes."""
+    nd, total = len(N), int(np.prod(N, dtype=np.int64))
+    at = lambda flat: tuple(int(v) for v in np.unravel_index(flat, N))           # noqa: E731
+    places = [("corner", tuple((N[d] - 1) if c >> d & 1 else 0 for d in range(nd))) for c in range(1 << nd)]
+    for h in range(head - 1):
+        places += [("seam-", at((h + 1) * tail - 1)), ("seam+", at((h + 1) * tail))]
+    places += [("offset", at(e)) for e in (1 << 31, 1 << 32) if e < total]
+    rng = np.random.default_rng(seed)
+    places += [("random", tuple(int(rng.integers(0, n)) for n in N)) for _ in range(4)]
+    return places
+
+
+def walk_boxes(N, ext, places):
+    """[(kinds, lo, hi)]: a box of extents `ext` (clipped to the grid) around every place; places that give the same box share it."""
+    ext = [min(e, n) for e, n in zip(ext, N)]
+    boxes = {}
+    for kind, idx in places:
+        lo, hi = _around(N, ext, idx)
+        assert all(l <= i < h for l, i, h in zip(lo, idx, hi)) and all(0 <= l < h <= n for l, h, n in zip(lo, hi, N))
+        boxes.setdefault((tuple(lo), tuple(hi)), []).append(kind)
+    out = [("+".join(sorted(set(k))), list(lo), list(hi)) for (lo, hi), k in boxes.items()]
+    kinds = set(k for ks, _, _ in out for k in ks.split("+"))
+    assert {"corner", "random"} <= kinds and ("offset" in kinds) == (int(np.prod(N, dtype=np.int64)) > (1 << 31))
+    return out
+
+
+def _walk_setup(what, arrays):
+    _tool_start(arrays * 4 * int(np.prod(WALK_N, dtype=np.int64)), "%s %s f32" % (what, WALK_N))
+
+
+def test_walk_the_places_on_a_small_grid():
+    """The placement, without a large array: a (2, 3, 4, 5, 6, 7) grid split like WALK_N."""
+    N, tail = (2, 3, 4, 5, 6, 7), 4 * 5 * 6 * 7
+    places = walk_places(N, tail, 6)
+    assert [k for k, _ in places].count("corner") == 64 and [k for k, _ in places].count("random") == 4
+    seams = [i for k, i in places if k.startswith("seam")]
+    assert seams[:4] == [(0, 0, 3, 4, 5, 6), (0, 1, 0, 0, 0, 0), (0, 1, 3, 4, 5, 6), (0, 2, 0, 0, 0, 0)] and len(seams) == 10
+    assert seams[4:6] == [(0, 2, 3, 4, 5, 6), (1, 0, 0, 0, 0, 0)]                 # the seam where the first head axis moves on
+    boxes = walk_boxes(N, WALK_EXT, places)
+    # (the head axes and the last axis are whole in every box: 8 corner boxes)
+    assert 8 <= len(boxes) <= len(places) and any("seam" in k and "corner" in k for k, _, _ in boxes)
+    big = walk_places(WALK_N, 717550000, 6)
+    assert ("offset", tuple(int(v) for v in np.unravel_index(1 << 32, WALK_N))) in big and len(big) == 64 + 10 + 2 + 4
+
+
+def test_walk_evaluate_shape_past_2e32_nodes():
+    import hishapes_ref as H
+    from levelsetpy_amd import _kffi, shapes as S
+    _walk_plan(_kffi, 1)
+    _walk_setup("evaluate_shape", 1)
+    N = WALK_N
+    col = lambda v, t=np.float64: np.asarray(v, dtype=t).reshape(-1, 1)          # noqa: E731
+    g = L.createGrid(col([-1., -1.2, -.9, -1.1, -1., -.8]), col([1.1, 1., 1., .9, 1.2, 1.]), col(N, np.int64), None, low_mem=True)
+    rows = np.array([[1., .5, -.3, .2, .1, -.4], [-.2, 1., .4, -.1, .3, .2], [.3, -.1, .2, 1., -.5, .6]])
+    node = S.union(S.sphere_of(rows, [.1, -.05, .2], .9), S.hyperplane([1., 2., -1., .5, -.7, .3], [.1, 0., 0., .2, -.1, 0.]),
+                   S.rectangle_by_corners([-.5, -.6, -.4, -.7, -.3, -.2], [.6, .4, .5, .3, .8, .7]))
+    comp = S.compile_program_hi(node, 6)
+    t0 = time.perf_counter()
+    out = S.evaluate_shape(g, node, 'float32')
+    torch.cuda.synchronize()
+    call = time.perf_counter() - t0
+    assert tuple(out.shape) == N and out.dtype == torch.float32 and S.last_info()["kernel"] == _kffi.kernel_name("float32")
+    vs = [np.asarray(v, dtype=np.float64).ravel() for v in g.vs]
+    boxes = walk_boxes(N, WALK_EXT, walk_places(N, 717550000, 6))
+    nodes = 0
+    for kind, lo, hi in boxes:
+        ref = H.run_program(H.PlainGrid([vs[d][lo[d]:hi[d]] for d in range(6)]), comp)[0].astype(np.float32)
+        got = B.gather(out, _ranges(lo, hi)).astype(np.float32)
+        assert np.array_equal(got, ref), (kind, lo)
+        nodes += ref.size
+    from levelsetpy_amd import _gffi
+    assert int(S.last_info()["flags"][0]) & (_gffi.NEG | _gffi.POS) == _gffi.NEG | _gffi.POS      # both signs on the grid
+    _report("walk evaluate_shape %s f32 %.2f GiB kernel %s, first_tail 2, 6 head indices, 2 launches: %d boxes (%d nodes) bitwise; the call %.3f s" % (
+        N, 4 * out.numel() / GiB, S.last_info()["kernel"], len(boxes), nodes, call))
+
+
+def test_walk_migrate_grid_past_2e32_nodes():
+    import hishapes_ref as H
+    import query_ref as Q
+    import resample_ref as R
+    from levelsetpy_amd import _mffi, resample
+    _walk_plan(_mffi)
+    _walk_setup("migrateGrid", 1)
+    N = WALK_N
+    src, pd = (3, 4, 5, 9, 11, 12), (2,)
+    smin, smax = Q.grid_bounds(src, pd)
+    rO = R.RefGrid(smin, smax, src, pd)
+    gO = L.createGrid(rO.min.reshape(-1, 1), rO.max.reshape(-1, 1), rO.N.reshape(-1, 1), list(pd))
+    data = R.field(rO, 77).astype(np.float32)
+    c, h = 0.5 * (smin + smax), 0.5 * (smax - smin)
+    # the destination: from 0.9 half-widths below the source box's centre to 1.2 above it, so a part of every axis falls outside
+    dst = H.PlainGrid([np.linspace(c[d] - 0.9 * h[d], c[d] + 1.2 * h[d], n) for d, n in enumerate(N)])
+    # inside is separable per axis (the identity map): the nodes of axis d that locate finds inside, the other coordinates at the centre
+    inside = []
+    for d in range(6):
+        y = np.tile(c, (N[d], 1))
+        y[:, d] = dst.vs[d]
+        inside.append(int((~Q.locate(rO, y)[2]).sum()))
+    assert all(0 < k < n for k, n, d in zip(inside, N, range(6)) if d not in pd) and inside[2] == N[2], inside
+    filled = int(np.prod(inside, dtype=np.int64))
+    boxes = walk_boxes(N, WALK_EXT, walk_places(N, 717550000, 6))
+    dt = torch.as_tensor(data, device="cuda")
+    for fill in ('nan', -2.5):
+        t0 = time.perf_counter()
+        out = L.migrateGrid(gO, dt, dst, fill=fill)
+        torch.cuda.synchronize()
+        call = time.perf_counter() - t0
+        assert tuple(out.shape) == N and out.dtype == torch.float32
+        assert resample.last_path() == _mffi.kernel_names("float32", 6, 0, False)
+        assert int(resample.last_info()["counts"]) == filled, (resample.last_info()["counts"], inside)
+        some_in = some_out = 0
+        for kind, lo, hi in boxes:
+            ref, cnt = R.resample_ref(rO, data, H.PlainGrid([dst.vs[d][lo[d]:hi[d]] for d in range(6)]), None, None, None, fill, dtype=np.float32)
+            got = B.gather(out, _ranges(lo, hi)).astype(np.float32)
+            assert np.array_equal(got, ref, equal_nan=True), (kind, lo, fill)
+            some_in += int(cnt)
+            some_out += ref.size - int(cnt)
+        assert some_in > 0 and some_out > 0
+        del out
+        _report("walk migrateGrid %s -> %s f32 %.2f GiB fill %s, %s: %d of %d nodes filled == the product of the per-axis counts %s; "
+                "%d boxes (%d nodes inside, %d outside) bitwise; the call %.3f s" % (
+                    src, N, 4 * int(np.prod(N, dtype=np.int64)) / GiB, fill, resample.last_path(), filled,
+                    int(np.prod(N, dtype=np.int64)), inside, len(boxes), some_in, some_out, call))
+
+
+def test_walk_set_volume_past_2e32_nodes():
+    import measure_ref as MR
+    from levelsetpy_amd import _kffi, _vffi, measure, shapes as S
+    _walk_plan(_vffi, 1)
+    _walk_plan(_kffi, 1)
+    _walk_setup("setVolume (and the array leaf that builds its data)", 2)
+    N = WALK_N
+    total = int(np.prod(N, dtype=np.int64))
+    col = lambda v, t=np.float64: np.asarray(v, dtype=t).reshape(-1, 1)          # noqa: E731
+    g = L.createGrid(col([0.] * 6), col([n - 1 for n in N]), col(N, np.int64), None, low_mem=True)     # unit spacing: node = coordinate
+    assert all(np.array_equal(np.asarray(v).ravel(), np.arange(n)) for v, n in zip(g.vs, N))
+    centres = sorted(set(i for _, i in walk_places(N, 717550000, 6)))
+    # a ball of radius 0.6 around every place holds its centre alone; everything else is positive.  A program holds 64 instructions: 31 balls
+    # a pass, a later pass takes the earlier result as an array leaf
+    data = None
+    t0 = time.perf_counter()
+    for k in range(0, len(centres), 31):
+        parts = ([S.array(data)] if data is not None else []) + [S.sphere(np.array(c, dtype=np.float64), 0.6) for c in centres[k:k + 31]]
+        data = S.evaluate_shape(g, S.union(*parts), 'float32')
+        assert S.last_info()["kernel"] == _kffi.kernel_name("float32")
+    torch.cuda.synchronize()
+    build = time.perf_counter() - t0
+    # windows: a ball's bounding box plus one node, clipped; windows that meet are merged until none do
+    wins = [([max(0, i - 2) for i in c], [min(n, i + 3) for i, n in zip(c, N)]) for c in centres]
+    merged = True
+    while merged:
+        merged = False
+        for a in range(len(wins)):
+            for b in range(a + 1, len(wins)):
+                if all(wins[a][0][d] < wins[b][1][d] and wins[b][0][d] < wins[a][1][d] for d in range(6)):
+                    wins[a] = ([min(x, y) for x, y in zip(wins[a][0], wins[b][0])], [max(x, y) for x, y in zip(wins[a][1], wins[b][1])])
+                    del wins[b]
+                    merged = True
+                    break
+            if merged:
+                break
+    want = dict(cells=int(np.prod([n - 1 for n in N], dtype=np.int64)), full=0, cut=0, invalid=0, Q_cut=0, inside=0, nan=0, lo=list(N), hi=[-1] * 6)
+    for lo, hi in wins:
+        w = B.gather(data, _ranges(lo, hi)).astype(np.float32)
+        r = MR.measure_ref(w, 0.0, ())
+        for key in ("full", "cut", "invalid", "Q_cut", "inside", "nan"):
+            want[key] += r[key]
+        if r["inside"]:
+            want["lo"] = [min(a, l + b) for a, l, b in zip(want["lo"], lo, r["lo"])]
+            want["hi"] = [max(a, l + b) for a, l, b in zip(want["hi"], lo, r["hi"])]
+    want["Q"] = want["full"] * 720 * MR.Q_ONE + want["Q_cut"]
+    assert want["inside"] == len(centres) and want["cut"] > len(centres) and want["full"] == 0
+    # the condition of the test: no inside node lies outside a window
+    flat, below = data.view(-1), 0
+    for a in range(0, total, 1 << 28):
+        below += int((flat[a:a + (1 << 28)] <= 0).sum())
+    assert below == want["inside"], (below, want["inside"])
+    t0 = time.perf_counter()
+    vol = L.setVolume(g, data)
+    torch.cuda.synchronize()
+    call = time.perf_counter() - t0
+    got = measure.last_info()[0]
+    assert measure.last_path() == _vffi.kernel_names("float32", None, 6)
+    for key in ("cells", "full", "cut", "invalid", "Q_cut", "Q", "inside", "nan", "lo", "hi"):
+        assert got[key] == want[key], (key, got[key], want[key])
+    assert vol == MR.volume_of(want["Q"], 6, 1.0)
+    _report("walk setVolume %s f32 %.2f GiB %s: %d balls in %d disjoint windows, cut %d inside %d Q_cut %d lo %s hi %s, every integer ==; "
+            "the data in %d passes of evaluate_shape %.3f s, the call %.3f s" % (
+                N, 4 * total / GiB, measure.last_path(), len(centres), len(wins), want["cut"], want["inside"], want["Q_cut"], want["lo"],
+                want["hi"], (len(centres) + 30) // 31, build, call))
+
+
+def _box_grid32(G, idx):
+    """box_ref.box_grid in the oracle's float32 mode: the fp64 nodes kept for the trig tables, the working coordinates rounded once."""
+    g = O.Grid(G.min, G.max, [len(i) for i in idx], None, dtype=np.float32)
+    g.bc = ['extrapolate'] * G.dim
+    g.dx = G.dx.copy()
+    vs64 = [np.asarray(G.vs[d]).reshape(-1, 1)[idx[d]].copy() for d in range(G.dim)]
+    g.xs64 = np.meshgrid(*vs64, indexing='ij')
+    g.vs = [v.astype(np.float32) for v in vs64]
+    g.xs = [x.astype(np.float32) for x in g.xs64]
+    return g
+
+
+def test_walk_hidim_substep_past_2e31_cells():
+    """hjh_substep of libhj_hidim.so, DubinsPair6D, ENO2, fp32, stage EULER on 36^6 = 2 176 782 336 cells: the 64-bit branch of decode at six
+    axes and gather_stencils' 64-bit offsets, against the float32 oracle on boxes (margin 3), bit for bit as tests/test_gpu_fp32_exact.py
+    holds ENO2."""
+    import hidim_cases as HC
+    from levelsetpy_amd import _hffi, hidim
+    N = (36,) * 6
+    sh = _Shape(N, 4)
+    assert sh.cells == 2176782336 >= (1 << 31)
+    _tool_start(2 * sh.bytes + (1 << 30), "hjh_substep %s f32" % (N,))
+    pd = [2, 5]
+    gmin, gmax = [-2.0, -2.2, 0.0, -2.1, -1.9, 0.0], [2.1, 2.0, 2 * np.pi * (1 - 1 / 36), 1.9, 2.2, 2 * np.pi * (1 - 1 / 36)]
+    col = lambda v, t=np.float64: np.asarray(v, dtype=t).reshape(-1, 1)          # noqa: E731
+    g = L.createGrid(col(gmin), col(gmax), col(N, np.int64), pd, low_mem=True)
+    G = B.light_grid(gmin, gmax, N, pd)
+    for a, b in zip(g.vs, G.vs):
+        assert np.array_equal(np.asarray(a).ravel(), b.ravel())
+    system = L.DubinsPair6D(g, **HC.PARAMS["pair6d"])
+    ham, par = system.native()
+    # the data of tests/hidim_cases.py with noise per cell, written on the device one axis-0 slab at a time
+    y = torch.empty(N, dtype=torch.float32, device="cuda")
+    gen = torch.Generator(device="cuda").manual_seed(36)
+    x = [torch.as_tensor(v.ravel(), device="cuda") for v in G.vs]
+    shape5 = lambda d: [-1 if j == d else 1 for j in range(1, 6)]                # noqa: E731
+    for i in range(N[0]):
+        base = ((x[0][i] - x[3].reshape(shape5(3))) ** 2 + (x[1].reshape(shape5(1)) - x[4].reshape(shape5(4))) ** 2 + 0.01).sqrt() - 1
+        y[i] = (base.expand(N[1:]) + 0.05 * (2 * torch.rand(N[1:], generator=gen, device="cuda", dtype=torch.float64) - 1)).float()
+    del base
+    out = torch.empty(N, dtype=torch.float32, device="cuda")
+    hg = hidim.hi_grid(g, "float32")
+    dt = 0.004
+    t0 = time.perf_counter()
+    hidim._substep(hg, _ffi.ENO2, ham, par, _ffi.STAGE_EULER, 0, y, None, out, dt)
+    torch.cuda.synchronize()
+    call = time.perf_counter() - t0
+    assert _hffi.last_kernel() == _hffi.kernel_name("float32", ham, _ffi.ENO2)
+    ext = (2, 2, 2, 2, 2, 4)
+    places = [(k, i) for k, i in walk_places(N, sh.cells, 1)]
+    assert [k for k, _ in places].count("offset") == 1
+    boxes = walk_boxes(N, ext, places)
+    cells = 0
+    for kind, lo, hi in boxes:
+        idx, cmp = B.box(G, lo, hi, B.M_SUBSTEP)
+        gb = _box_grid32(G, idx)
+        yb = B.gather(y, idx).astype(np.float32)
+        yd, _ = O.term_lax_friedrichs(gb, HC.DubinsPair6D(gb, **HC.PARAMS["pair6d"]), "ENO2", 0.0, yb.reshape(-1))
+        assert yd.dtype == np.float32
+        ref = (yb + np.float32(dt) * yd.reshape(yb.shape))[tuple(cmp)]
+        got = B.gather(out, _ranges(lo, hi)).astype(np.float32)
+        assert ref.dtype == np.float32 and np.array_equal(got, ref), (kind, lo, int((got != ref).sum()))
+        assert not np.array_equal(got, yb[tuple(cmp)])                           # the step moved the data
+        cells += ref.size
+    _report("walk hjh_substep %s f32 %.2f GiB per array %s EULER: %d boxes (%d cells, margin %d) bitwise against the float32 oracle; the call %.3f s" % (
+        N, sh.bytes / GiB, _hffi.last_kernel(), len(boxes), cells, B.M_SUBSTEP, call))

@@ -107,11 +107,12 @@ def test_plan_of_the_named_grids():
     p = K.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
     p = K.plan((41,) * 6)
-    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.launches) == (1, 41, 41 ** 5, 1)
+    # a launch has fewer than 2^32 threads, 2^24 - 1 workgroups: a grid past 2^32 nodes takes more than one
+    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.heads_per_launch, p.launches) == (1, 41, 41 ** 5, 37, 2)
     p = K.plan((3, 2 ** 31 - 1))
-    assert (p.first_tail, p.head, p.tail, p.chunks, p.launches) == (1, 3, 2 ** 31 - 1, 2 ** 23, 1)
+    assert (p.first_tail, p.head, p.tail, p.chunks, p.heads_per_launch, p.launches) == (1, 3, 2 ** 31 - 1, 2 ** 23, 1, 3)
     p = K.plan((46341, 46341, 2 ** 31 - 1))
-    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 255 and p.launches == -(-46341 ** 2 // 255)
+    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 1 and p.launches == 46341 ** 2
     # members: gridDim.y ends at 65535
     assert [K.plan((2, 1, 2, 1, 2), k).member_launches for k in (1, 65535, 65536, 65537, 131071)] == [1, 1, 2, 2, 3]
 

@@ -168,9 +168,10 @@ def test_plan_of_the_named_grids_and_of_the_fields():
     p = V.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
     p = V.plan((41,) * 6)
-    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.launches) == (1, 41, 41 ** 5, 1)
+    # a launch has fewer than 2^32 threads, 2^24 - 1 workgroups: a grid past 2^32 nodes takes more than one
+    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.heads_per_launch, p.launches) == (1, 41, 41 ** 5, 37, 2)
     p = V.plan((46341, 46341, 2 ** 31 - 1))
-    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 255 and p.launches == -(-46341 ** 2 // 255)
+    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 1 and p.launches == 46341 ** 2
     for F, launches in ((1, 1), (65535, 1), (65536, 2), (131071, 3)):
         p = V.plan((3, 2), F)
         assert (p.nfields, p.field_launches) == (F, launches)

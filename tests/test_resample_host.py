@@ -139,9 +139,10 @@ def test_plan_of_the_named_grids_and_of_the_output_arrays():
     p = M.plan((25,) * 6)
     assert (p.first_tail, p.head, p.tail, p.launches) == (0, 1, 25 ** 6, 1)
     p = M.plan((41,) * 6)
-    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.launches) == (1, 41, 41 ** 5, 1)
+    # a launch has fewer than 2^32 threads, 2^24 - 1 workgroups: a grid past 2^32 nodes takes more than one
+    assert 41 ** 6 > 2 ** 32 and (p.first_tail, p.head, p.tail, p.heads_per_launch, p.launches) == (1, 41, 41 ** 5, 37, 2)
     p = M.plan((46341, 46341, 2 ** 31 - 1))
-    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 255 and p.launches == -(-46341 ** 2 // 255)
+    assert p.head == 46341 ** 2 > 2 ** 31 and p.heads_per_launch == 1 and p.launches == 46341 ** 2
     # output arrays: K x nfields without a fold, nfields with one; gridDim.y ends at 65535
     for K, F, reduce, arrays, launches in ((1, 1, 0, 1, 1), (65535, 1, 0, 65535, 1), (65537, 1, 0, 65537, 2), (300, 3, 0, 900, 1),
                                            (65537, 3, 0, 196611, 4), (65537, 3, 1, 3, 1), (2, 70000, 2, 70000, 2)):
