@@ -45,6 +45,7 @@ from .eikonal import signedDistance, addCRadius                                 
 from .resample import transformData, migrateGrid, shiftData, rotateData         # noqa: F401
 from .measure import setVolume, setCompare, setBounds, truncateGrid             # noqa: F401
 from . import hidim                                                              # noqa: F401
+from . import stochastic                                                         # noqa: F401
 from .hidim_ham import register_hidim_hamiltonian, HidimRegistration, HidimSystem, hidim_kernel_cache_stats   # noqa: F401
 from .plant import register_plant, PlantRegistration, PlantSystem, plant_kernel_cache_stats   # noqa: F401
 

@@ -113,6 +113,7 @@ _REASONS = {'stopInit': 'a stopping condition', 'stopSetInclude': 'a stopping co
             'stopConverge': 'a stopping condition', 'stopLevel': 'a stopping condition', 'convergeThreshold': 'a stopping condition',
             'ignoreBoundary': 'a stopping condition', 'discountFactor': 'discounting', 'discountMode': 'discounting',
             'discountAnneal': 'discounting', 'SDModFunc': 'an SDModFunc', 'SDModParams': 'an SDModFunc',
+            'addGaussianNoiseStandardDeviation': 'noise: the batched kernel has no diffusion term',
             'computeTTR': 'computeTTR', 'ttrLevel': 'computeTTR', 'ttrCrossing': 'computeTTR', 'ttrInterpolate': 'computeTTR'}
 
 

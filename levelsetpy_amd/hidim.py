@@ -286,6 +286,8 @@ def solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
         v = _get(extraArgs, name)
         if v is not None and v is not False:
             error('extraArgs.%s has no implementation on grids of 5 or 6 dimensions' % name)
+    if isfield(extraArgs, 'addGaussianNoiseStandardDeviation'):
+        error('extraArgs.addGaussianNoiseStandardDeviation has no implementation on grids of 5 or 6 dimensions')
     if isfield(schemeData, 'dissFunc') and schemeData.dissFunc in (artificialDissipationLLF, artificialDissipationLLLF):
         error('%s (a local Lax-Friedrichs dissipation) has no implementation on grids of 5 or 6 dimensions: '
               'artificialDissipationGLF only' % schemeData.dissFunc.__name__)

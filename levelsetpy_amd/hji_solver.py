@@ -9,8 +9,9 @@ Stopping conditions (stopInit via multilinear point evaluation, stopSetInclude /
 stopLevel, stopConverge with ignoreBoundary) and the discounting steps (default and 'Kene' mode,
 discountAnneal) are applied to the device-resident state as well; flipOutput reverses the stored time
 axis.  extraArgs.computeTTR records the time-to-reach function of the solve on the device (ttr.py; extraOuts.TTR).
-Visualisation, noise injection (addGaussianNoiseStandardDeviation) and trajectory extraction are
-outside the path.
+extraArgs.addGaussianNoiseStandardDeviation = sigma adds the diffusion term trace(sigma^T D^2phi sigma) (stochastic.py: the
+reference's termSum wiring, :449-471, or one fused launch per stage of libhj_stoch.so where the solve is eligible;
+extraOuts.path says which).  Visualisation and trajectory extraction are outside the path.
 
 Deviations from the shipped reference, all listed in SURVEY Appendix D: the integrator honours
 the schemeFunc that was built (minWithZero -> termRestrictUpdate; the reference ignores it,
@@ -200,6 +201,20 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
     if compMethod in ('minWithZero', 'zero'):
         schemeFunc = termRestrictUpdate
         sd_run = Bundle(dict(innerFunc=termLaxFriedrichs, innerData=schemeData, positive=0))
+    # ---- noise (hji_solver.py:449-471): guarded on the key's presence, so a solve without it runs exactly what it ran before
+    noise = None
+    if isfield(extraArgs, 'addGaussianNoiseStandardDeviation'):
+        from . import stochastic
+        noise = stochastic.check_sigma(extraArgs.addGaussianNoiseStandardDeviation, gDim)
+        setup, why = stochastic.classify(data0, schemeData, compMethod, extraArgs)
+        if setup is not None:
+            return stochastic.solve(setup, data0, tau, compMethod, extraArgs)
+        extraOuts.path = stochastic._set_path('generic: termSum(%s, termTraceHessian) through the integrator loop: %s'
+                                              % (schemeFunc.__name__, why))
+        info('HJIPDE_solve: ' + extraOuts.path)
+    run_func, run_data = schemeFunc, sd_run
+    if noise is not None:
+        run_func, run_data = stochastic.noise_scheme(noise[0], noise[1], g, schemeFunc, sd_run)
     integratorOptions = odeCFLset(Bundle({'factorCFL': 0.8, 'singleStep': 'on'}))
     startTime = cputime()
 
@@ -279,6 +294,9 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
                 sd_run = Bundle(dict(innerFunc=termLaxFriedrichs, innerData=schemeData, positive=0))
             else:
                 sd_run = schemeData
+            run_func, run_data = schemeFunc, sd_run
+            if noise is not None:
+                run_func, run_data = stochastic.noise_scheme(noise[0], noise[1], g, schemeFunc, sd_run)
             if schemeData.grid is not g:
                 error('SDModFunc must keep schemeData.grid (the stored arrays live on it)')
             new_plan = native_plan(schemeData, y)
@@ -320,7 +338,7 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
             known = False
         post_b = (3, obstacle_i) if obstacle_i is not None else None
         stepwise = os.environ.get("HJ_HJIPDE_STEPWISE") == "1"     # test knob: force the loop below
-        if dg is not None and known and discountFactor is None and not stepwise and tNow < tau[i] - small:
+        if dg is not None and known and discountFactor is None and not stepwise and noise is None and tNow < tau[i] - small:
             res = integrate_span_device(schemeFunc, sd_run, y, tNow, tau[i], integratorOptions, small, post,
                                         post_a=post_a, post_b=post_b)
             if res is not None:
@@ -332,7 +350,7 @@ def HJIPDE_solve(data0, tau, schemeData, compMethod=None, extraArgs=None):
                 yLast = y          # the integrators never write their input: no copy needed
             if not quiet:
                 info('Cur Time %s bound: %s' % (tNow, tau[i] - small))
-            tNow, y, _ = odeCFL3(schemeFunc, [tNow, tau[i]], y, integratorOptions, sd_run)
+            tNow, y, _ = odeCFL3(run_func, [tNow, tau[i]], y, integratorOptions, run_data)
             if ops.has_nan(y):
                 error('Nans encountered in the integrated result of HJI PDE data')   # :544-545
             # ---- compMethod (hji_solver.py:566-599); in 'Kene' discount mode the min/max with the target
