@@ -1,5 +1,5 @@
-// Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip), libhj_hiquery.so (hj_hiquery.hip) and the ones
-// libhj_plant.so has hipRTC compile (hj_plant.hip): what does not depend on the plant -- sgn, the RK4 step, and a trajectory from
+// Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip), libhj_hiquery.so (hj_hiquery.hip), libhj_mc.so (hj_mc.hip,
+// through the hook type below) and the ones libhj_plant.so has hipRTC compile (hj_plant.hip): what does not depend on the plant -- sgn, the RK4 step, and a trajectory from
 // its first state to its last (the bisection over the stored sets, the costate, the sub-steps).  One source, so a 5-D / 6-D
 // trajectory is stepped by the statements a 2-D .. 4-D one is.  At the end, the host side the three share: check_rollout.
 // A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).  A plant with
@@ -77,12 +77,19 @@ struct RolloutOut {
     int* status;
 };
 
+// What a caller may add to a trajectory, the way Control was introduced: a hook type with `plain` false is asked after every sub-step
+// (after_substep: libhj_mc.so's noise), which slice to read (slice: true where it chose tE itself and no bisection runs), and told of every
+// recorded column (recorded: the target function's value there); it maps a group to its row of x0 (state_of), may leave traj out
+// (a null O.traj) and writes its own outputs at the end (finish).  Every use below is an `if constexpr (!HK::plain)`: with the
+// default the statements are discarded, and the kernels of libhj_rollout.so, libhj_hiquery.so and libhj_plant.so are what they were.
+struct NoHooks { static constexpr bool plain = true; };
+
 // The body of a rollout kernel: the thread's trajectory (2^ND lanes per trajectory, this thread one corner of its cell).
 // Control flow is uniform inside a group and predicated across groups: see hj_rollout.hip.
-template <typename T, int SCHEME, typename PL, typename UP, typename PD = hjr_plant>
+template <typename T, int SCHEME, typename PL, typename UP, typename PD = hjr_plant, typename HK = NoHooks>
 __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long long field_stride, int ntimes,
                                              const double* __restrict__ x0, long long M, const QGrid& G, const QStencil<T>& S,
-                                             int sub_samples, double dt_small, const PD& P, const RolloutOut& O) {
+                                             int sub_samples, double dt_small, const PD& P, const RolloutOut& O, HK&& H = HK()) {
     constexpr int ND = PL::ND;                     // == G.ndim (checked by the host)
     constexpr int lanes = 1 << ND;                 // 4 .. 64: divides the wavefront, groups never straddle one
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
@@ -92,8 +99,10 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
     const double nan = __builtin_nan("");
     const double small = 1e-4;
     double x[MAXD];
+    long long xr = m;                              // the row of x0: a hook may run several groups from one
+    if constexpr (!HK::plain) xr = H.state_of(m);
 #pragma unroll
-    for (int d = 0; d < MAXD; ++d) x[d] = d < ND ? x0[m * ND + d] : 0.0;
+    for (int d = 0; d < MAXD; ++d) x[d] = d < ND ? x0[xr * ND + d] : 0.0;
 
     // where the state is: the cell, this lane's corner of it and the corner's weight
     int lo[MAXD];
@@ -159,26 +168,33 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
     };
 
     double* __restrict__ row = O.traj + m * ND * (long long)ntimes;         // traj[m][d][col] = row[d * ntimes + col]
+    bool paths = true;                             // a hook may run without traj
+    if constexpr (!HK::plain) paths = O.traj != nullptr;
     int* __restrict__ te_row = O.t_earliest ? O.t_earliest + m * (long long)ntimes : nullptr;
     find();
-    if (c == 0) {
+    if (c == 0 && paths) {
 #pragma unroll
         for (int d = 0; d < ND; ++d) row[d * (long long)ntimes] = x[d];
     }
+    if constexpr (!HK::plain) H.recorded(value_at(ntimes - 1), true);
     int tE = 0, len = 1;
     bool done = false, reached = false, left = !inside;
     for (int it = 0; it < ntimes - 1; ++it) {
         // the largest index of [tE, ntimes-1] whose set holds x: only the visited slices are interpolated
         const bool active = !done;
-        int lower = tE, upper = active ? ntimes - 1 : tE;
-        while (upper > lower) {
-            const int mid = (upper + lower + 1) / 2;
-            if (value_at(mid) < small) lower = mid;
-            else upper = mid - 1;
-        }
-        if (active) {
-            tE = upper;
-            if (tE == ntimes - 1) done = reached = true;
+        bool chosen = false;
+        if constexpr (!HK::plain) chosen = H.slice(it, tE);
+        if (!chosen) {
+            int lower = tE, upper = active ? ntimes - 1 : tE;
+            while (upper > lower) {
+                const int mid = (upper + lower + 1) / 2;
+                if (value_at(mid) < small) lower = mid;
+                else upper = mid - 1;
+            }
+            if (active) {
+                tE = upper;
+                if (tE == ntimes - 1) done = reached = true;
+            }
         }
         if (te_row && c == 0) te_row[it] = active ? tE : -1;
         if (!done) {
@@ -188,12 +204,14 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
                 costate_at(tE, p);
                 plant_controls<PL>(P, p, x, ctl);
                 rk4<PL>(P, x, dt_small, ctl);
+                if constexpr (!HK::plain) H.after_substep(x, it, s);
                 find();
             }
             len = it + 2;
             left = left || !inside;
+            if constexpr (!HK::plain) H.recorded(value_at(ntimes - 1), false);
         }
-        if (c == 0) {
+        if (c == 0 && paths) {
 #pragma unroll
             for (int d = 0; d < ND; ++d) row[d * (long long)ntimes + it + 1] = done ? nan : x[d];
         }
@@ -202,6 +220,7 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
         if (te_row) te_row[ntimes - 1] = -1;
         O.length[m] = len;
         O.status[m] = left ? HJR_LEFT_GRID : (reached ? HJR_REACHED : HJR_EXHAUSTED);
+        if constexpr (!HK::plain) H.finish(m, x);       // a finished trajectory's state no longer moves: x is the last recorded one
     }
 }
 
