@@ -395,13 +395,6 @@ unsigned long long* next_ring(hj_ctx* c, int user_slot, int* rc) {
     return c->ring + (size_t)pos * HJ_MAX_DIM;
 }
 
-double key_to_double(unsigned long long k) {
-    unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
 // max(D1^2) per dim of `y` -> `out` (ndim values of the ctx dtype, device), stream-ordered
 int weno_eps_to(hj_ctx* c, const void* y, void* out) {
     if (c->ndim < 2) return fail(HJ_EUNSUPPORTED, "grid.dim must be 2..4 here, got %d", c->ndim);

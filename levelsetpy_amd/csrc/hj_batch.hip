@@ -9,6 +9,10 @@
 // The per-cell functions (gather_stencils, upwind_cd, HAM::cell / plane / eval, lf_ydot, rk_stage_out, post_step) are the solver's own
 // source, compiled with the solver's flags: a problem's result has the bits direct_substep_kernel gives for it alone.  The library links
 // nothing of libhj_mi355x.so.
+// What this library shares with libhj_stoch.so and libhj_hidim.so is in two headers.  hj_stage_dev.h: tables_of, the clamp, what a stage
+// stores (stage_result, array_op), the fold that ends the bound kernel.  hj_stage_host.h: the descriptor as GridArgs (fill_grid) and its
+// checks, the step bound from the keys, a stage's and an interval's checks, and the RK schedule (rk_schedule) whose stages hjb_integrate
+// writes into its table.  Here: the problem axis, the device table and the per-problem prefix of the refusals.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -17,6 +21,8 @@
 #include <vector>
 #include "hj_tool_host.h"
 #include "hj_split.h"
+#include "hj_stage_host.h"
+#include "hj_stage_dev.h"
 #include "../../include/hj_batch.h"
 
 namespace hjb {
@@ -27,6 +33,7 @@ using namespace hj_tool;
 constexpr long long MAX_Y = 65535;      // gridDim.y of one launch
 
 static_assert(sizeof(hjb_entry) == 64, "hjb_entry is 64 bytes (include/hj_batch.h)");
+static_assert(HJB_ARR_NONE == 0 && HJB_ARR_MIN == 1 && HJB_ARR_MAX == 2 && HJB_ARR_MAX_NEG == 3, "array_op and check_array_ops take the numbers");
 
 // what every problem of a launch shares
 template <typename T, int ND> struct BatchArgs {
@@ -39,32 +46,6 @@ template <typename T, int ND> struct BatchArgs {
     int stage, restrict_sign;
 };
 
-template <typename T, int ND>
-__device__ __forceinline__ HamTables<T> problem_tables(const T* const* coord, const T* const* aux, const double* par) {
-    HamTables<T> P;
-#pragma unroll
-    for (int d = 0; d < HJ_MAX_DIM; ++d) P.coord[d] = coord[d];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) P.aux[s] = aux[s];
-#pragma unroll
-    for (int s = 0; s < HJ_PAR_SLOTS; ++s) P.par[s] = (T)par[s];     // rounded as the solver's host side rounds them (fill_ham)
-    P.range = nullptr;
-    P.local_mode = 0;
-    return P;
-}
-
-// min / max against an array: minmax_kernel's expression (hj_split.h), NaN propagating as NumPy's minimum / maximum
-template <typename T>
-__device__ __forceinline__ T array_op(int op, T a, T b) {
-    T r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else if (op == HJB_ARR_MIN) r = a < b ? a : b;
-    else if (op == HJB_ARR_MAX) r = a > b ? a : b;
-    else r = a > -b ? a : -b;
-    return r;
-}
-
 template <typename T, typename HAM, int SCHEME>
 __global__ __launch_bounds__(256) void batch_substep_kernel(const BatchArgs<T, HAM::ND> A) {
     constexpr int ND = HAM::ND;
@@ -75,7 +56,7 @@ __global__ __launch_bounds__(256) void batch_substep_kernel(const BatchArgs<T, H
     if (e->active == 0) return;
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (t >= A.G.total) return;
-    const HamTables<T> P = problem_tables<T, ND>(A.coord, A.aux, A.par + (long long)blockIdx.y * HJB_PAR_SLOTS);
+    const HamTables<T> P = tables_of<T>(A.coord, A.aux, A.par + (long long)blockIdx.y * HJB_PAR_SLOTS);
     const T* __restrict__ y = (const T*)e->src;
     const T* __restrict__ y0 = (const T*)e->y0;
     T* __restrict__ out = (T*)e->dst;
@@ -107,18 +88,8 @@ __global__ __launch_bounds__(256) void batch_substep_kernel(const BatchArgs<T, H
     for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], eps[d], wk[d], pc[d], hd[d]);
     T alpha[ND];
     T ydot = lf_ydot<NP, HAM>(P, hc, hp, A.sc, pc, hd, alpha);
-    // termRestrictUpdate clamp, written like direct_substep_kernel's (a NaN stays a NaN)
-    if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
-    else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
-    T o;
-    if (stage == HJ_STAGE_YDOT) o = ydot;
-    else {
-        o = rk_stage_out<NP>(stage, ca, cb, dt, y0v, centre, ydot);
-        if (e->post_prev) o = post_step(e->post_prev, o, use_y0 ? y0v : centre);
-        if (e->op_a) o = array_op(e->op_a, o, ((const T*)e->post_a)[t]);
-        if (e->op_b) o = array_op(e->op_b, o, ((const T*)e->post_b)[t]);
-    }
-    out[t] = o;
+    ydot = restrict_clamp(A.restrict_sign, ydot);
+    out[t] = stage_result<NP>(*e, stage, ca, cb, use_y0, dt, y0v, centre, ydot, t);
 }
 
 // max over the grid of alpha_d at zero costate, per problem: the evaluation of alpha_bound_kernel (hj_split.h) -- HAM::eval with unit scales --
@@ -127,7 +98,7 @@ template <typename T, typename HAM>
 __global__ __launch_bounds__(256) void batch_bound_kernel(const GridArgs<T, HAM::ND> G, const hjb_tables tab, const double* par,
                                                          unsigned long long* keys) {
     constexpr int ND = HAM::ND;
-    const HamTables<T> P = problem_tables<T, ND>((const T* const*)tab.coord, (const T* const*)tab.aux, par + (long long)blockIdx.y * HJB_PAR_SLOTS);
+    const HamTables<T> P = tables_of<T>((const T* const*)tab.coord, (const T* const*)tab.aux, par + (long long)blockIdx.y * HJB_PAR_SLOTS);
     double m[ND];
     T one[ND], p[ND];
 #pragma unroll
@@ -140,19 +111,7 @@ __global__ __launch_bounds__(256) void batch_bound_kernel(const GridArgs<T, HAM:
 #pragma unroll
         for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
     }
-    __shared__ double red[4][ND];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const double w = wave_max(m[d]);
-        if (lane == 0) red[wv][d] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < ND) {
-        const int d = threadIdx.x;
-        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
-        if (w > -1e299) key_max(keys + (long long)blockIdx.y * HJ_MAX_DIM + d, w);
-    }
+    fold_bound<ND>(m, keys + (long long)blockIdx.y * HJ_MAX_DIM);
 }
 
 template <typename T>
@@ -176,36 +135,8 @@ static int check_setup(const hjq_grid* g, const hjb_tables* tab, int ham, long l
     const int nd = ham_ndim(ham);
     if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no batched kernel (the three built-in systems only)", ham);
     if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
-    total = 1;
-    for (int d = 0; d < nd; ++d) {
-        if (g->N[d] < HJ_STENCIL || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range (need %d .. 2^30)", d, (long long)g->N[d], HJ_STENCIL);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d])) return fail(HJ_EINVAL, "axis %d: dx must be positive and finite", d);
-        if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
-        total *= g->N[d];
-        if (total > (1ll << 38)) return fail(HJ_EINVAL, "grid too large");
-    }
-    const int naux = ham == HJ_HAM_DUBINS_REL ? 2 : (ham == HJ_HAM_DOUBLE_PENDULUM ? 4 : 0);
-    for (int s = 0; s < naux; ++s)
-        if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
-    return HJ_OK;
-}
-
-// fill_grid of the solver (hj_host.h) from the descriptor: a single domain, no slab halos
-template <typename T, int ND> static void fill_grid(const hjq_grid* g, GridArgs<T, ND>& G) {
-    long long s = 1;
-    for (int d = ND - 1; d >= 0; --d) {
-        G.n[d] = (int)g->N[d];
-        G.bc[d] = g->bc[d];
-        G.km[d] = g->toward_zero[d] ? T(-1) : T(1);
-        G.inv_dx[d] = (T)(1.0 / g->dx[d]);
-        fill_stencil_constants<T>(g->dx[d], G.K[d]);
-        G.stride[d] = s;
-        s *= g->N[d];
-    }
-    G.halo_lo = 0;
-    G.halo_hi = 0;
-    G.total = s;
+    const int rc = check_axes(g, nd, tab->coord, total);
+    return rc ? rc : check_aux(tab->aux, builtin_naux(ham), ham);
 }
 
 template <typename T, typename HAM, int SCHEME>
@@ -275,13 +206,6 @@ static int launch_bound(const hjq_grid* g, const hjb_tables* tab, const double* 
     return HJ_OK;
 }
 
-static double key_to_double(unsigned long long k) {
-    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
 }  // namespace hjb
 
 using namespace hjb;
@@ -310,17 +234,8 @@ int hjb_step_bounds(const hjq_grid* g, const hjb_tables* tab, int ham, const dou
     std::vector<unsigned long long> h((size_t)B * HJ_MAX_DIM);
     HIP_TRY(hipMemcpyAsync(h.data(), k, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    for (int64_t b = 0; b < B; ++b) {
-        // stepBound = 1 / sum_d max alpha_d / dx_d, summed in dimension order (hj_static_step_bound)
-        double inv = 0.0;
-        for (int d = 0; d < g->ndim; ++d) {
-            const double a = key_to_double(h[(size_t)b * HJ_MAX_DIM + d]);
-            if (amax_host) amax_host[b * HJ_MAX_DIM + d] = a;
-            inv += a / g->dx[d];
-        }
-        for (int d = g->ndim; d < HJ_MAX_DIM && amax_host; ++d) amax_host[b * HJ_MAX_DIM + d] = 0.0;
-        sb_host[b] = 1.0 / inv;
-    }
+    for (int64_t b = 0; b < B; ++b)
+        sb_host[b] = step_bound_of_keys(&h[(size_t)b * HJ_MAX_DIM], g->dx, g->ndim, amax_host ? amax_host + b * HJ_MAX_DIM : nullptr, HJ_MAX_DIM);
     return HJ_OK;
 }
 
@@ -330,7 +245,7 @@ int hjb_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, i
     int rc = check_setup(g, tab, ham, total);
     if (rc) return rc;
     if ((rc = check_point_scheme(scheme, "batched"))) return rc;
-    if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
+    if ((rc = check_stage_id(stage))) return rc;
     if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
     if (B == 0) return HJ_OK;
     if (!params || !entries) return fail(HJ_EINVAL, "null argument");
@@ -339,12 +254,13 @@ int hjb_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, i
 
 int hjb_plan(int order, const double* sb_host, int64_t B, double t0, double tf, double factor_cfl, double max_step,
              double stop_tol, double* t_host, int64_t* steps_host) {
-    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    int rc = check_order(order);
+    if (rc) return rc;
     if (B < 0 || (B > 0 && !sb_host)) return fail(HJ_EINVAL, "null argument");
     for (int64_t b = 0; b < B; ++b) {
         std::vector<double> dts;
         double t;
-        int rc = plan_problem(order, sb_host[b], t0, tf, factor_cfl, max_step, stop_tol, &dts, t, b);
+        rc = plan_problem(order, sb_host[b], t0, tf, factor_cfl, max_step, stop_tol, &dts, t, b);
         if (rc) return rc;
         if (t_host) t_host[b] = t;
         if (steps_host) steps_host[b] = (int64_t)dts.size();
@@ -360,8 +276,8 @@ int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
     int rc = check_setup(g, tab, ham, total);
     if (rc) return rc;
     if ((rc = check_point_scheme(scheme, "batched"))) return rc;
-    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
-    if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
+    if ((rc = check_order(order))) return rc;
+    if ((rc = check_post_prev(post_prev))) return rc;
     if (B < 0) return fail(HJ_EINVAL, "B must not be negative");
     if (B == 0) return HJ_OK;
     if (!params || !sb_host || !problems_host) return fail(HJ_EINVAL, "null argument");
@@ -370,13 +286,8 @@ int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
     int64_t nmax = 0;
     for (int64_t b = 0; b < B; ++b) {
         const hjb_problem& p = problems_host[b];
-        if (!p.y_in || !p.buf_a || !p.buf_b) return fail(HJ_EINVAL, "problem %lld: null buffer", (long long)b);
-        if (order >= 2 && !p.work) return fail(HJ_EINVAL, "problem %lld: work buffer required for order >= 2", (long long)b);
-        if (p.buf_a == p.buf_b || p.buf_a == p.y_in || p.buf_b == p.y_in || p.work == p.y_in || p.work == p.buf_a || p.work == p.buf_b)
-            return fail(HJ_EINVAL, "problem %lld: buffers must be distinct", (long long)b);
-        if (p.op_a < HJB_ARR_NONE || p.op_a > HJB_ARR_MAX_NEG || p.op_b < HJB_ARR_NONE || p.op_b > HJB_ARR_MAX_NEG)
-            return fail(HJ_EINVAL, "problem %lld: unknown array operator", (long long)b);
-        if ((p.op_a && !p.post_a) || (p.op_b && !p.post_b)) return fail(HJ_EINVAL, "problem %lld: an array operator without its array", (long long)b);
+        if ((rc = check_buffers(order, p.y_in, p.buf_a, p.buf_b, p.work, b))) return rc;
+        if ((rc = check_array_ops(p.op_a, p.post_a, p.op_b, p.post_b, b))) return rc;
         if ((rc = plan_problem(order, sb_host[b], t0, tf, factor_cfl, max_step, stop_tol, &dts[(size_t)b], tend[(size_t)b], b))) return rc;
         nmax = std::max<int64_t>(nmax, (int64_t)dts[(size_t)b].size());
     }
@@ -387,42 +298,23 @@ int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
                     (long long)launches, (long long)B, (long long)table_bytes);
     hipStream_t s = (hipStream_t)stream;
     if (launches > 0) {
-        // entry (step k, stage j, problem b) at [(k*order + j)*B + b]; zero = inactive
+        // entry (step k, stage j, problem b) -- stage k*order + j of the problem's schedule -- at [(k*order + j)*B + b]; zero = inactive
         std::vector<hjb_entry> sched((size_t)(launches * B));
         memset(sched.data(), 0, sched.size() * sizeof(hjb_entry));
+        std::vector<Stage> st;
         for (int64_t b = 0; b < B; ++b) {
             const hjb_problem& p = problems_host[b];
-            void* outs[2] = {p.buf_a, p.buf_b};
-            const void* cur = p.y_in;
-            const int64_t n = (int64_t)dts[(size_t)b].size();
-            for (int64_t k = 0; k < n; ++k) {
-                void* nxt = outs[k & 1];
-                hjb_entry* e = &sched[(size_t)((k * order) * B + b)];
-                // RK3: the first stage buffer doubles as the output; RK2: `work` is the first stage buffer (hj_rk_integrate)
-                if (order == 1) { e[0].src = cur; e[0].dst = nxt; }
-                else if (order == 2) {
-                    e[0].src = cur; e[0].dst = p.work;
-                    e[B].src = p.work; e[B].y0 = cur; e[B].dst = nxt;
-                } else {
-                    e[0].src = cur; e[0].dst = nxt;
-                    e[B].src = nxt; e[B].y0 = cur; e[B].dst = p.work;
-                    e[2 * B].src = p.work; e[2 * B].y0 = cur; e[2 * B].dst = nxt;
-                }
-                for (int j = 0; j < order; ++j) { e[j * B].dt = dts[(size_t)b][(size_t)k]; e[j * B].active = 1; }
-                hjb_entry& last = e[(order - 1) * B];
-                last.post_prev = post_prev;
-                last.post_a = p.op_a ? p.post_a : nullptr; last.op_a = p.op_a;
-                last.post_b = p.op_b ? p.post_b : nullptr; last.op_b = p.op_b;
-                cur = nxt;
+            rk_schedule(order, p.y_in, p.buf_a, p.buf_b, p.work, dts[(size_t)b], post_prev, p.op_a, p.post_a, p.op_b, p.post_b, st);
+            for (size_t i = 0; i < st.size(); ++i) {
+                const Stage& q = st[i];
+                sched[i * (size_t)B + (size_t)b] = hjb_entry{q.src, q.y0, q.dst, q.post_a, q.post_b, q.dt, 1, q.post_prev, q.op_a, q.op_b};
             }
         }
         // ONE copy for the whole interval; the wait keeps `sched` alive until the copy has read it
         HIP_TRY(hipMemcpyAsync(table, sched.data(), sched.size() * sizeof(hjb_entry), hipMemcpyHostToDevice, s));
         HIP_TRY(hipStreamSynchronize(s));
-        static const int stages[3][3] = {{HJ_STAGE_EULER, 0, 0}, {HJ_STAGE_EULER, HJ_STAGE_RK2_FULL, 0},
-                                         {HJ_STAGE_EULER, HJ_STAGE_RK3_HALF, HJ_STAGE_RK3_FULL}};
         for (int64_t l = 0; l < launches; ++l) {
-            rc = dispatch_substep(g, tab, scheme, ham, stages[order - 1][l % order], restrict_sign, params,
+            rc = dispatch_substep(g, tab, scheme, ham, rk_stage_id(order, (int)(l % order)), restrict_sign, params,
                                   (const hjb_entry*)table + l * B, B, s);
             if (rc) return rc;
         }
@@ -431,7 +323,7 @@ int hjb_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
         const int64_t n = (int64_t)dts[(size_t)b].size();
         if (t_host) t_host[b] = tend[(size_t)b];
         if (steps_host) steps_host[b] = n;
-        if (result_in_host) result_in_host[b] = n == 0 ? 0 : 1 + (int32_t)((n - 1) & 1);
+        if (result_in_host) result_in_host[b] = result_in(n);
     }
     return HJ_OK;
 }

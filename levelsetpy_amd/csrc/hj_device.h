@@ -956,6 +956,11 @@ __device__ __forceinline__ void key_max(unsigned long long* p, double v) {
     const unsigned long long k = max_key(v);
     if (k > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, k);
 }
+// the value a key stands for: max_key's inverse, for the host that copies the keys back
+inline double key_to_double(unsigned long long k) {
+    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
+    return __builtin_bit_cast(double, b);
+}
 
 // Wavefront max / min of a double, every lane receives the result.  DPP data moves (row_shr 1,2,4,8 inside the four
 // 16-lane rows, then row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3: lane 63 ends up with the

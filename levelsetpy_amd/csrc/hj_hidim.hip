@@ -7,11 +7,14 @@
 // hj_split.h), instantiated at ND = 5 and 6 and compiled with the solver's flags.  HJ_MAX_DIM stays 4: HamTables cannot hold the coordinates
 // of axes 4 and 5, so the two systems here read a table struct of their own (HiTables), and the one solver function that takes a HamTables,
 // lf_ydot, has its dissipation sum restated (hidim_ydot).  The library links nothing of libhj_mi355x.so.
-// The substep and bound kernels, HiTables, hidim_ydot, array_op and SubstepArgs live in hj_hidim_dev.h: this file instantiates them for the two
+// The substep and bound kernels, HiTables, hidim_ydot and SubstepArgs live in hj_hidim_dev.h (array_op, the clamp, what a stage stores and
+// the bound kernel's fold: hj_stage_dev.h, which it includes and libhj_batch.so / libhj_stoch.so share): this file instantiates them for the two
 // built-in systems, and hipRTC compiles them around an expression registered with hjh_ham_register (HamUser<T>, generated below; ids from
 // HJH_HAM_USER_BASE).  Such a kernel is built lazily at its first launch, per device, under the lock of hj_rtc_host.h, kept in the on-disk
 // code-object cache that libhj_mi355x.so's registrations use, and launched through the module API with the very SubstepArgs block the
 // built-in instantiations get: 256 threads, one thread per cell, 64-bit indexing.
+// Host side, hj_stage_host.h holds what the three libraries share: the descriptor as GridArgs (fill_grid) and its checks, the step bound from
+// the keys, struct Stage, a stage's and an interval's checks, and the RK schedule (rk_schedule) that hjh_integrate hands to ONE dispatch.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -22,6 +25,7 @@
 #include <vector>
 #include "hj_tool_host.h"
 #include "hj_hidim_dev.h"
+#include "hj_stage_host.h"
 #define HJ_RTC_FAIL ::hj_tool::fail
 #include "hj_rtc_host.h"
 
@@ -245,7 +249,7 @@ static std::string user_source(const HiUserHam& u, int id) {
 
 // what the disk cache's key covers besides the generated source (hj_rtc_host.h)
 static const hj_rtc::Unit& hidim_unit() {
-    static const hj_rtc::Unit u = {{"/hj_hidim_dev.h", "/hj_split.h", "/hj_device.h", "/../../include/hj_hidim.h", "/../../include/hj_mi355x.h"},
+    static const hj_rtc::Unit u = {{"/hj_hidim_dev.h", "/hj_stage_dev.h", "/hj_split.h", "/hj_device.h", "/../../include/hj_hidim.h", "/../../include/hj_mi355x.h"},
                                    {sizeof(SubstepArgs<double, 5>), sizeof(SubstepArgs<double, 6>), sizeof(SubstepArgs<float, 5>),
                                     sizeof(SubstepArgs<float, 6>), sizeof(HiTables<double>), sizeof(HiTables<float>)}};
     return u;
@@ -278,15 +282,7 @@ static int check_grid(const hjh_grid* g, long long& total) {
     if (g->ndim < HJH_MIN_DIM || g->ndim > HJH_MAX_DIM)
         return fail(HJ_EINVAL, "grid.ndim must be %d..%d here (got %d; 1..%d: the solver of hj_mi355x.h)", (int)HJH_MIN_DIM, (int)HJH_MAX_DIM,
                     (int)g->ndim, HJ_MAX_DIM);
-    total = 1;
-    for (int d = 0; d < g->ndim; ++d) {
-        if (g->N[d] < HJ_STENCIL || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range (need %d .. 2^30)", d, (long long)g->N[d], HJ_STENCIL);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d])) return fail(HJ_EINVAL, "axis %d: dx must be positive and finite", d);
-        total *= g->N[d];
-        if (total > (1ll << 38)) return fail(HJ_EINVAL, "grid too large");
-    }
-    return HJ_OK;
+    return check_axes(g, g->ndim, nullptr, total);
 }
 
 // the checks every entry point that evaluates a system makes on (grid, tables, system, parameters)
@@ -304,37 +300,16 @@ static int check_setup(const hjh_grid* g, const hjh_tables* tab, int ham, const 
     }
     if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no kernel here (HJH_HAM_PLANE5D, HJH_HAM_DUBINS_PAIR6D)", ham);
     if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
-    for (int d = 0; d < nd; ++d)
-        if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
-    for (int s = 0; s < naux; ++s)
-        if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
+    if ((rc = check_coord(tab->coord, nd))) return rc;
+    if ((rc = check_aux(tab->aux, naux, ham))) return rc;
     if (!params_host) return fail(HJ_EINVAL, "null parameters");
     return HJ_OK;
 }
 
 // what a stage needs besides the setup; shared by hjh_substep and hjh_integrate
 static int check_ops(int restrict_sign, int post_prev, int op_a, const void* post_a, int op_b, const void* post_b) {
-    if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
-    if (op_a < HJH_ARR_NONE || op_a > HJH_ARR_MAX_NEG || op_b < HJH_ARR_NONE || op_b > HJH_ARR_MAX_NEG) return fail(HJ_EINVAL, "unknown array operator");
-    if ((op_a && !post_a) || (op_b && !post_b)) return fail(HJ_EINVAL, "an array operator without its array");
-    return HJ_OK;
-}
-
-// fill_grid of the solver (hj_host.h) from the descriptor: a single domain, no slab halos
-template <typename T, int ND> static void fill_grid(const hjh_grid* g, GridArgs<T, ND>& G) {
-    long long s = 1;
-    for (int d = ND - 1; d >= 0; --d) {
-        G.n[d] = (int)g->N[d];
-        G.bc[d] = g->bc[d];
-        G.km[d] = g->toward_zero[d] ? T(-1) : T(1);
-        G.inv_dx[d] = (T)(1.0 / g->dx[d]);
-        fill_stencil_constants<T>(g->dx[d], G.K[d]);
-        G.stride[d] = s;
-        s *= g->N[d];
-    }
-    G.halo_lo = 0;
-    G.halo_hi = 0;
-    G.total = s;
+    const int rc = check_post_prev(post_prev);
+    return rc ? rc : check_array_ops(op_a, post_a, op_b, post_b);
 }
 
 template <typename T> static void fill_tables(const hjh_tables* tab, const double* params_host, HiTables<T>& P) {
@@ -342,17 +317,6 @@ template <typename T> static void fill_tables(const hjh_tables* tab, const doubl
     for (int s = 0; s < 4; ++s) P.aux[s] = (const T*)tab->aux[s];
     for (int s = 0; s < HJH_PAR_SLOTS; ++s) P.par[s] = (T)params_host[s];
 }
-
-// one stage's pointers and scalars
-struct Stage {
-    const void* src;
-    const void* y0;
-    void* dst;
-    double dt;
-    int stage, post_prev, op_a, op_b;
-    const void* post_a;
-    const void* post_b;
-};
 
 // the argument block of one call's stages (every stage of a call shares it but for set_stage's fields), and its workgroup count
 template <typename T, int ND>
@@ -508,13 +472,6 @@ static int launch_builtin_bound(const hjh_grid* g, const hjh_tables* tab, int ha
     return HJ_OK;
 }
 
-static double key_to_double(unsigned long long k) {
-    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
 }  // namespace hjh
 
 using namespace hjh;
@@ -528,12 +485,12 @@ int hjh_substep(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham, i
     int rc = check_setup(g, tab, ham, params_host, total);
     if (rc) return rc;
     if ((rc = check_point_scheme(scheme, "5-D / 6-D substep"))) return rc;
-    if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
+    if ((rc = check_stage_id(stage))) return rc;
     if ((rc = check_ops(restrict_sign, post_prev, op_a, post_a, op_b, post_b))) return rc;
     if (!src || !dst) return fail(HJ_EINVAL, "null argument");
     if (src == dst) return fail(HJ_EINVAL, "dst must not alias src");
-    if (stage >= HJ_STAGE_RK3_HALF && !y0) return fail(HJ_EINVAL, "stage %d reads y0, which is null", stage);
-    const Stage st = {src, y0, dst, dt, stage, post_prev, op_a, op_b, post_a, post_b};
+    if ((rc = check_y0(stage, y0))) return rc;
+    const Stage st = {stage, src, y0, dst, dt, post_prev, op_a, op_b, post_a, post_b};
     return dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, &st, 1, (hipStream_t)stream);
 }
 
@@ -554,15 +511,7 @@ int hjh_step_bound(const hjh_grid* g, const hjh_tables* tab, int ham, const doub
     unsigned long long h[HJH_MAX_DIM];
     HIP_TRY(hipMemcpyAsync(h, k, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    // stepBound = 1 / sum_d max alpha_d / dx_d, summed in axis order (hjb_step_bounds)
-    double inv = 0.0;
-    for (int d = 0; d < g->ndim; ++d) {
-        const double a = key_to_double(h[d]);
-        if (amax_host) amax_host[d] = a;
-        inv += a / g->dx[d];
-    }
-    for (int d = g->ndim; d < HJH_MAX_DIM && amax_host; ++d) amax_host[d] = 0.0;
-    *sb_host = 1.0 / inv;
+    *sb_host = step_bound_of_keys(h, g->dx, g->ndim, amax_host, HJH_MAX_DIM);
     return HJ_OK;
 }
 
@@ -574,44 +523,20 @@ int hjh_integrate(const hjh_grid* g, const hjh_tables* tab, int scheme, int ham,
     int rc = check_setup(g, tab, ham, params_host, total);
     if (rc) return rc;
     if ((rc = check_point_scheme(scheme, "5-D / 6-D substep"))) return rc;
-    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    if ((rc = check_order(order))) return rc;
     if ((rc = check_ops(restrict_sign, post_prev, op_a, post_a, op_b, post_b))) return rc;
-    if (!y_in || !buf_a || !buf_b) return fail(HJ_EINVAL, "null buffer");
-    if (order >= 2 && !work) return fail(HJ_EINVAL, "work buffer required for order >= 2");
-    if (buf_a == buf_b || buf_a == y_in || buf_b == y_in || work == y_in || work == buf_a || work == buf_b)
-        return fail(HJ_EINVAL, "buffers must be distinct");
+    if ((rc = check_buffers(order, y_in, buf_a, buf_b, work))) return rc;
     // the schedule: the time arithmetic of hjb_plan (hj_tool_host.h), known before the first launch because alpha ignores the data
     std::vector<double> dts;
     double tend;
     if ((rc = plan_problem(order, sb, t0, tf, factor_cfl, max_step, stop_tol, &dts, tend, 0))) return rc;
     const int64_t n = (int64_t)dts.size();
     std::vector<Stage> st;
-    st.reserve((size_t)(n * order));
-    void* outs[2] = {buf_a, buf_b};
-    const void* cur = y_in;
-    for (int64_t k = 0; k < n; ++k) {
-        void* nxt = outs[k & 1];
-        const double dt = dts[(size_t)k];
-        // RK3: the first stage buffer doubles as the output; RK2: `work` is the first stage buffer (hj_rk_integrate)
-        if (order == 1) st.push_back(Stage{cur, nullptr, nxt, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
-        else if (order == 2) {
-            st.push_back(Stage{cur, nullptr, work, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
-            st.push_back(Stage{work, cur, nxt, dt, HJ_STAGE_RK2_FULL, 0, 0, 0, nullptr, nullptr});
-        } else {
-            st.push_back(Stage{cur, nullptr, nxt, dt, HJ_STAGE_EULER, 0, 0, 0, nullptr, nullptr});
-            st.push_back(Stage{nxt, cur, work, dt, HJ_STAGE_RK3_HALF, 0, 0, 0, nullptr, nullptr});
-            st.push_back(Stage{work, cur, nxt, dt, HJ_STAGE_RK3_FULL, 0, 0, 0, nullptr, nullptr});
-        }
-        Stage& last = st.back();
-        last.post_prev = post_prev;
-        last.op_a = op_a; last.post_a = op_a ? post_a : nullptr;
-        last.op_b = op_b; last.post_b = op_b ? post_b : nullptr;
-        cur = nxt;
-    }
+    rk_schedule(order, y_in, buf_a, buf_b, work, dts, post_prev, op_a, post_a, op_b, post_b, st);
     if (n > 0 && (rc = dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, st.data(), (int)st.size(), (hipStream_t)stream))) return rc;
     if (t_host) *t_host = tend;
     if (steps_host) *steps_host = n;
-    if (result_in_host) *result_in_host = n == 0 ? 0 : 1 + (int32_t)((n - 1) & 1);
+    if (result_in_host) *result_in_host = result_in(n);
     return HJ_OK;
 }
 

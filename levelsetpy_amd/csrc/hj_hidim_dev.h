@@ -7,9 +7,12 @@
 // A system HAM has  ND, ID, struct Cell,  cell(P, idx, sc) -> Cell  and  eval<NP>(cell, q, H, alpha): interface and scaling as hj_device.h's --
 // cell() folds the costate scales sc[d] into the cell's coefficients, eval() takes the UNSCALED costates q (p_d = sc[d] q_d), returns H(x, p)
 // and alpha_s[d] = sc[d] alpha_d.
+// What the two kernels share with batch_substep_kernel / stoch_substep_kernel and their bound kernels -- the clamp, what a stage stores
+// (stage_result, array_op), the fold of the per-axis maxima -- is hj_stage_dev.h's, device code only like this header.
 #ifndef HJ_HIDIM_DEV_H
 #define HJ_HIDIM_DEV_H
 #include "hj_split.h"
+#include "hj_stage_dev.h"
 #include "../../include/hj_hidim.h"
 
 namespace hjh {
@@ -41,17 +44,7 @@ __device__ __forceinline__ T hidim_ydot(const typename HAM::Cell& c, const T* pc
     }
 }
 
-// min / max against an array: batch_substep_kernel's expression, NaN propagating as NumPy's minimum / maximum
-template <typename T>
-__device__ __forceinline__ T array_op(int op, T a, T b) {
-    T r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else if (op == HJH_ARR_MIN) r = a < b ? a : b;
-    else if (op == HJH_ARR_MAX) r = a > b ? a : b;
-    else r = a > -b ? a : -b;
-    return r;
-}
+static_assert(HJH_ARR_NONE == 0 && HJH_ARR_MIN == 1 && HJH_ARR_MAX == 2 && HJH_ARR_MAX_NEG == 3, "array_op (hj_stage_dev.h) takes the numbers");
 
 template <typename T, int ND> struct SubstepArgs {
     GridArgs<T, ND> G;
@@ -94,18 +87,8 @@ __global__ __launch_bounds__(256) void hidim_substep_kernel(const SubstepArgs<T,
     for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], T(0), wk, pc[d], hd[d]);
     T alpha[ND];
     T ydot = hidim_ydot<NP, HAM>(hc, pc, hd, alpha);
-    // termRestrictUpdate clamp, written like direct_substep_kernel's (a NaN stays a NaN)
-    if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
-    else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
-    T o;
-    if (stage == HJ_STAGE_YDOT) o = ydot;
-    else {
-        o = rk_stage_out<NP>(stage, ca, cb, A.dt, y0v, centre, ydot);
-        if (A.post_prev) o = post_step(A.post_prev, o, use_y0 ? y0v : centre);
-        if (A.op_a) o = array_op(A.op_a, o, A.post_a[t]);
-        if (A.op_b) o = array_op(A.op_b, o, A.post_b[t]);
-    }
-    A.dst[t] = o;
+    ydot = restrict_clamp(A.restrict_sign, ydot);
+    A.dst[t] = stage_result<NP>(A, stage, ca, cb, use_y0, A.dt, y0v, centre, ydot, t);
 }
 
 // max over the grid of alpha_d at zero costate: batch_bound_kernel's evaluation (unit scales), one workgroup maximum per axis folded into
@@ -125,19 +108,7 @@ __global__ __launch_bounds__(256) void hidim_bound_kernel(const GridArgs<T, HAM:
 #pragma unroll
         for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
     }
-    __shared__ double red[4][ND];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const double w = wave_max(m[d]);
-        if (lane == 0) red[wv][d] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < ND) {
-        const int d = threadIdx.x;
-        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
-        if (w > -1e299) key_max(keys + d, w);
-    }
+    fold_bound<ND>(m, keys);
 }
 
 }  // namespace hjh

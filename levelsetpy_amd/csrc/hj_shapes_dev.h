@@ -10,7 +10,7 @@
 
 namespace hjg_dev {
 
-// NaN on either side gives NaN, as np.minimum / np.maximum (and array_op of hj_batch.hip)
+// NaN on either side gives NaN, as np.minimum / np.maximum (and array_op of hj_stage_dev.h)
 __device__ __forceinline__ double nmin(double a, double b) {
     double r;
     if (a != a) r = a;

@@ -10,6 +10,10 @@
 //                                               parameters, dt, the arrays and the post-step operators ride in the kernel arguments.
 //   stoch_bound_kernel<T, HAM>                  the per-dimension maxima of alpha at zero costate (batch_bound_kernel's evaluation)
 // The per-cell functions are the solver's own source, compiled with the solver's flags.  The library links nothing of libhj_mi355x.so.
+// What this library shares with libhj_batch.so and libhj_hidim.so is in two headers.  hj_stage_dev.h: tables_of, what a stage stores
+// (stage_result, array_op), the fold that ends the bound kernel.  hj_stage_host.h: the descriptor as GridArgs (fill_grid) and its checks,
+// the Lax-Friedrichs step bound from the keys, struct Stage and its checks, and the RK schedule (rk_schedule) whose stages hjw_integrate
+// dispatches one by one.  Here: sigma and its checks, the stage's alias checks, the interval's check against the post-step arrays.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cmath>
@@ -18,6 +22,8 @@
 #include <vector>
 #include "hj_tool_host.h"
 #include "hj_curv.h"
+#include "hj_stage_host.h"
+#include "hj_stage_dev.h"
 #include "../../include/hj_stoch.h"
 
 namespace hjw {
@@ -43,31 +49,7 @@ template <typename T, int ND> struct StochArgs {
     int stage, restrict_sign, post_prev, op_a, op_b;
 };
 
-template <typename T, int ND>
-__device__ __forceinline__ HamTables<T> tables_of(const T* const* coord, const T* const* aux, const double* par) {
-    HamTables<T> P;
-#pragma unroll
-    for (int d = 0; d < HJ_MAX_DIM; ++d) P.coord[d] = coord[d];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) P.aux[s] = aux[s];
-#pragma unroll
-    for (int s = 0; s < HJ_PAR_SLOTS; ++s) P.par[s] = (T)par[s];
-    P.range = nullptr;
-    P.local_mode = 0;
-    return P;
-}
-
-// min / max against an array: minmax_kernel's expression (hj_split.h), NaN propagating as NumPy's minimum / maximum
-template <typename T>
-__device__ __forceinline__ T array_op(int op, T a, T b) {
-    T r;
-    if (a != a) r = a;
-    else if (b != b) r = b;
-    else if (op == HJB_ARR_MIN) r = a < b ? a : b;
-    else if (op == HJB_ARR_MAX) r = a > b ? a : b;
-    else r = a > -b ? a : -b;
-    return r;
-}
+static_assert(HJB_ARR_NONE == 0 && HJB_ARR_MIN == 1 && HJB_ARR_MAX == 2 && HJB_ARR_MAX_NEG == 3, "array_op and check_array_ops take the numbers");
 
 template <typename T, typename HAM, int SCHEME, bool DIAG>
 __global__ __launch_bounds__(256) void stoch_substep_kernel(const StochArgs<T, HAM::ND> A) {
@@ -77,7 +59,7 @@ __global__ __launch_bounds__(256) void stoch_substep_kernel(const StochArgs<T, H
     static_assert(SCHEME != HJ_WENO5, "the intended WENO5 needs an epsilon reduction over the grid");
     const long long t = blockIdx.x * (long long)blockDim.x + threadIdx.x;
     if (t >= A.G.total) return;
-    const HamTables<T> P = tables_of<T, ND>(A.coord, A.aux, A.par);
+    const HamTables<T> P = tables_of<T>(A.coord, A.aux, A.par);
     const T* __restrict__ y = A.src;
     const int stage = A.stage;
     T eps[ND];
@@ -141,7 +123,8 @@ __global__ __launch_bounds__(256) void stoch_substep_kernel(const StochArgs<T, H
     for (int d = 0; d < ND; ++d) upwind_cd<SCHEME, T>(v[d], A.G.K[d], eps[d], wk[d], pc[d], hd[d]);
     T alpha[ND];
     T ydot = lf_ydot<NP, HAM>(P, hc, hp, A.sc, pc, hd, alpha);
-    // termRestrictUpdate clamp on the Lax-Friedrichs term, written like direct_substep_kernel's (a NaN stays a NaN)
+    // termRestrictUpdate clamp on the Lax-Friedrichs term, written like direct_substep_kernel's (a NaN stays a NaN).  Written out, not
+    // restrict_clamp (hj_stage_dev.h): with the trace added behind it the inlined helper turns a branch of the ENO3 kernels around
     if (A.restrict_sign > 0) ydot = (ydot < T(0)) ? T(0) : ydot;
     else if (A.restrict_sign < 0) ydot = (ydot > T(0)) ? T(0) : ydot;
     {
@@ -189,15 +172,7 @@ __global__ __launch_bounds__(256) void stoch_substep_kernel(const StochArgs<T, H
         }
         ydot = ydot + tr;                                                  // termSum (term_sum.py:97)
     }
-    T o;
-    if (stage == HJ_STAGE_YDOT) o = ydot;
-    else {
-        o = rk_stage_out<NP>(stage, ca, cb, A.dt, y0v, centre, ydot);
-        if (A.post_prev) o = post_step(A.post_prev, o, use_y0 ? y0v : centre);
-        if (A.op_a) o = array_op(A.op_a, o, A.post_a[t]);
-        if (A.op_b) o = array_op(A.op_b, o, A.post_b[t]);
-    }
-    A.dst[t] = o;
+    A.dst[t] = stage_result<NP>(A, stage, ca, cb, use_y0, A.dt, y0v, centre, ydot, t);
 }
 
 // max over the grid of alpha_d at zero costate: the evaluation of alpha_bound_kernel (hj_split.h) / batch_bound_kernel, one workgroup
@@ -211,7 +186,7 @@ template <typename T, int ND> struct BoundArgs {
 template <typename T, typename HAM>
 __global__ __launch_bounds__(256) void stoch_bound_kernel(const BoundArgs<T, HAM::ND> A, unsigned long long* keys) {
     constexpr int ND = HAM::ND;
-    const HamTables<T> P = tables_of<T, ND>(A.coord, A.aux, A.par);
+    const HamTables<T> P = tables_of<T>(A.coord, A.aux, A.par);
     double m[ND];
     T one[ND], p[ND];
 #pragma unroll
@@ -224,19 +199,7 @@ __global__ __launch_bounds__(256) void stoch_bound_kernel(const BoundArgs<T, HAM
 #pragma unroll
         for (int d = 0; d < ND; ++d) m[d] = fmax(m[d], (double)a[d]);
     }
-    __shared__ double red[4][ND];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-        const double w = wave_max(m[d]);
-        if (lane == 0) red[wv][d] = w;
-    }
-    __syncthreads();
-    if (threadIdx.x < ND) {
-        const int d = threadIdx.x;
-        const double w = fmax(fmax(red[0][d], red[1][d]), fmax(red[2][d], red[3][d]));
-        if (w > -1e299) key_max(keys + d, w);
-    }
+    fold_bound<ND>(m, keys);
 }
 
 // ---------------------------------------------------------------------------------------------- host side
@@ -248,19 +211,9 @@ static int check_setup(const hjq_grid* g, const hjb_tables* tab, int ham) {
     const int nd = ham_ndim(ham);
     if (nd == 0) return fail(HJ_EUNSUPPORTED, "Hamiltonian %d has no stochastic kernel (the three built-in systems only)", ham);
     if (g->ndim != nd) return fail(HJ_EINVAL, "Hamiltonian %d lives on %d-D grids, the grid has %d dimensions", ham, nd, (int)g->ndim);
-    long long total = 1;
-    for (int d = 0; d < nd; ++d) {
-        if (g->N[d] < HJ_STENCIL || g->N[d] > (1ll << 30)) return fail(HJ_EINVAL, "N[%d] = %lld out of range (need %d .. 2^30)", d, (long long)g->N[d], HJ_STENCIL);
-        if (g->bc[d] != HJ_BC_EXTRAPOLATE && g->bc[d] != HJ_BC_PERIODIC) return fail(HJ_EINVAL, "unknown boundary kind %d on axis %d", (int)g->bc[d], d);
-        if (!(g->dx[d] > 0.0) || !std::isfinite(g->dx[d])) return fail(HJ_EINVAL, "axis %d: dx must be positive and finite", d);
-        if (!tab->coord[d]) return fail(HJ_EINVAL, "null coordinate table of axis %d", d);
-        total *= g->N[d];
-        if (total > (1ll << 38)) return fail(HJ_EINVAL, "grid too large");
-    }
-    const int naux = ham == HJ_HAM_DUBINS_REL ? 2 : (ham == HJ_HAM_DOUBLE_PENDULUM ? 4 : 0);
-    for (int s = 0; s < naux; ++s)
-        if (!tab->aux[s]) return fail(HJ_EINVAL, "Hamiltonian %d reads aux table %d, which is null", ham, s);
-    return HJ_OK;
+    long long total;
+    const int rc = check_axes(g, nd, tab->coord, total);
+    return rc ? rc : check_aux(tab->aux, builtin_naux(ham), ham);
 }
 
 static int check_scheme(int scheme) {
@@ -283,44 +236,14 @@ static int check_sigma(const double* sigma, int nd, int form, bool& diag) {
     return HJ_OK;
 }
 
-// fill_grid of the solver (hj_host.h) from the descriptor: a single domain, no slab halos
-template <typename T, int ND> static void fill_grid(const hjq_grid* g, GridArgs<T, ND>& G) {
-    long long s = 1;
-    for (int d = ND - 1; d >= 0; --d) {
-        G.n[d] = (int)g->N[d];
-        G.bc[d] = g->bc[d];
-        G.km[d] = g->toward_zero[d] ? T(-1) : T(1);
-        G.inv_dx[d] = (T)(1.0 / g->dx[d]);
-        fill_stencil_constants<T>(g->dx[d], G.K[d]);
-        G.stride[d] = s;
-        s *= g->N[d];
-    }
-    G.halo_lo = 0;
-    G.halo_hi = 0;
-    G.total = s;
-}
-
-// one stage's share of the launch arguments
-struct Stage {
-    int stage;
-    const void* src;
-    const void* y0;
-    void* dst;
-    const void* post_a;
-    const void* post_b;
-    double dt;
-    int post_prev, op_a, op_b;
-};
-
 // the checks on a stage's arrays: nothing read may be null, the output aliases none of them
 static int check_stage(const Stage& s) {
     if (!s.src || !s.dst) return fail(HJ_EINVAL, "null src or dst");
+    int rc = check_y0(s.stage, s.y0);
+    if (rc) return rc;
+    if ((rc = check_post_prev(s.post_prev))) return rc;
+    if ((rc = check_array_ops(s.op_a, s.post_a, s.op_b, s.post_b))) return rc;
     const bool use_y0 = s.stage >= HJ_STAGE_RK3_HALF;
-    if (use_y0 && !s.y0) return fail(HJ_EINVAL, "stage %d reads y0, which is null", s.stage);
-    if (s.post_prev < HJ_POST_NONE || s.post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", s.post_prev);
-    if (s.op_a < HJB_ARR_NONE || s.op_a > HJB_ARR_MAX_NEG || s.op_b < HJB_ARR_NONE || s.op_b > HJB_ARR_MAX_NEG)
-        return fail(HJ_EINVAL, "unknown array operator");
-    if ((s.op_a && !s.post_a) || (s.op_b && !s.post_b)) return fail(HJ_EINVAL, "an array operator without its array");
     if (s.dst == s.src || (use_y0 && s.dst == s.y0) || (s.op_a && s.dst == s.post_a) || (s.op_b && s.dst == s.post_b))
         return fail(HJ_EINVAL, "dst must not alias an array the stage reads");
     return HJ_OK;
@@ -399,13 +322,6 @@ static int launch_bound(const hjq_grid* g, const hjb_tables* tab, const double* 
     return launch_done("stoch_bound_kernel");
 }
 
-static double key_to_double(unsigned long long k) {
-    const unsigned long long b = (k & 0x8000000000000000ull) ? (k & 0x7fffffffffffffffull) : ~k;
-    double v;
-    memcpy(&v, &b, 8);
-    return v;
-}
-
 // trace((L D) R) for L = sigma^T, R = sigma, D[m][k] = 1 / (dx_m dx_k): the expression order of trace_ldr (hj_api.hip), which is
 // trace_triple's (term_trace_hess.py:119-122)
 static double trace_ldr(const hjq_grid* g, const double* sigma) {
@@ -447,10 +363,7 @@ int hjw_step_bound(const hjq_grid* g, const hjb_tables* tab, int ham, const doub
     unsigned long long h[HJ_MAX_DIM];
     HIP_TRY(hipMemcpyAsync(h, k, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    // sb_LF = 1 / sum_d max alpha_d / dx_d, summed in dimension order (hj_static_step_bound)
-    double inv_lf = 0.0;
-    for (int d = 0; d < g->ndim; ++d) inv_lf += key_to_double(h[d]) / g->dx[d];
-    const double sb_lf = 1.0 / inv_lf;
+    const double sb_lf = step_bound_of_keys(h, g->dx, g->ndim, nullptr, 0);
     // sb_TH = 1 / (2 max |trace((L D) R)|), inf when nothing diffuses (hj_term_trace_hessian)
     const double mt = std::fabs(trace_ldr(g, sigma_host));
     const double sb_th = mt == 0.0 ? std::numeric_limits<double>::infinity() : 1.0 / (2.0 * mt);
@@ -469,24 +382,25 @@ int hjw_substep(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham, i
     int rc = check_setup(g, tab, ham);
     if (rc) return rc;
     if ((rc = check_scheme(scheme))) return rc;
-    if (stage < HJ_STAGE_YDOT || stage > HJ_STAGE_RK2_FULL) return fail(HJ_EINVAL, "unknown stage %d", stage);
+    if ((rc = check_stage_id(stage))) return rc;
     bool diag;
     if ((rc = check_sigma(sigma_host, g->ndim, form, diag))) return rc;
     if (!params_host || !entry_host) return fail(HJ_EINVAL, "null argument");
     const hjb_entry& e = *entry_host;
     const bool ops = stage != HJ_STAGE_YDOT;
-    Stage s{stage, e.src, e.y0, e.dst, ops ? e.post_a : nullptr, ops ? e.post_b : nullptr, e.dt,
-            ops ? e.post_prev : 0, ops ? e.op_a : 0, ops ? e.op_b : 0};
+    Stage s{stage, e.src, e.y0, e.dst, e.dt, ops ? e.post_prev : 0, ops ? e.op_a : 0, ops ? e.op_b : 0, ops ? e.post_a : nullptr,
+            ops ? e.post_b : nullptr};
     if ((rc = check_stage(s))) return rc;
     return dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, sigma_host, diag, s, (hipStream_t)stream);
 }
 
 int hjw_plan(int order, double sb, double t0, double tf, double factor_cfl, double max_step, double stop_tol, double* t_host,
              int64_t* steps_host) {
-    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
+    int rc = check_order(order);
+    if (rc) return rc;
     std::vector<double> dts;
     double t;
-    int rc = plan_problem(order, sb, t0, tf, factor_cfl, max_step, stop_tol, &dts, t, 0);
+    rc = plan_problem(order, sb, t0, tf, factor_cfl, max_step, stop_tol, &dts, t, 0);
     if (rc) return rc;
     if (t_host) *t_host = t;
     if (steps_host) *steps_host = (int64_t)dts.size();
@@ -500,19 +414,14 @@ int hjw_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
     int rc = check_setup(g, tab, ham);
     if (rc) return rc;
     if ((rc = check_scheme(scheme))) return rc;
-    if (order < 1 || order > 3) return fail(HJ_EINVAL, "order must be 1, 2 or 3");
-    if (post_prev < HJ_POST_NONE || post_prev > HJ_POST_MAX_PREV) return fail(HJ_EINVAL, "unknown post-step operator %d", post_prev);
+    if ((rc = check_order(order))) return rc;
+    if ((rc = check_post_prev(post_prev))) return rc;
     bool diag;
     if ((rc = check_sigma(sigma_host, g->ndim, form, diag))) return rc;
     if (!params_host || !problem_host) return fail(HJ_EINVAL, "null argument");
     const hjb_problem& p = *problem_host;
-    if (!p.y_in || !p.buf_a || !p.buf_b) return fail(HJ_EINVAL, "null buffer");
-    if (order >= 2 && !p.work) return fail(HJ_EINVAL, "work buffer required for order >= 2");
-    if (p.buf_a == p.buf_b || p.buf_a == p.y_in || p.buf_b == p.y_in || p.work == p.y_in || p.work == p.buf_a || p.work == p.buf_b)
-        return fail(HJ_EINVAL, "buffers must be distinct");
-    if (p.op_a < HJB_ARR_NONE || p.op_a > HJB_ARR_MAX_NEG || p.op_b < HJB_ARR_NONE || p.op_b > HJB_ARR_MAX_NEG)
-        return fail(HJ_EINVAL, "unknown array operator");
-    if ((p.op_a && !p.post_a) || (p.op_b && !p.post_b)) return fail(HJ_EINVAL, "an array operator without its array");
+    if ((rc = check_buffers(order, p.y_in, p.buf_a, p.buf_b, p.work))) return rc;
+    if ((rc = check_array_ops(p.op_a, p.post_a, p.op_b, p.post_b))) return rc;
     for (const void* w : {(const void*)p.buf_a, (const void*)p.buf_b, (const void*)p.work})
         if (w && ((p.op_a && w == p.post_a) || (p.op_b && w == p.post_b)))
             return fail(HJ_EINVAL, "a buffer the interval writes aliases a post-step array");
@@ -522,35 +431,13 @@ int hjw_integrate(const hjq_grid* g, const hjb_tables* tab, int scheme, int ham,
     const int64_t n = (int64_t)dts.size();
     hipStream_t s = (hipStream_t)stream;
     launched_none();
-    void* outs[2] = {p.buf_a, p.buf_b};
-    const void* cur = p.y_in;
-    for (int64_t k = 0; k < n; ++k) {
-        void* nxt = outs[k & 1];
-        // RK3: the first stage buffer doubles as the output; RK2: `work` is the first stage buffer (hj_rk_integrate)
-        Stage st[3];
-        memset(st, 0, sizeof(st));
-        if (order == 1) st[0] = Stage{HJ_STAGE_EULER, cur, nullptr, nxt};
-        else if (order == 2) {
-            st[0] = Stage{HJ_STAGE_EULER, cur, nullptr, p.work};
-            st[1] = Stage{HJ_STAGE_RK2_FULL, p.work, cur, nxt};
-        } else {
-            st[0] = Stage{HJ_STAGE_EULER, cur, nullptr, nxt};
-            st[1] = Stage{HJ_STAGE_RK3_HALF, nxt, cur, p.work};
-            st[2] = Stage{HJ_STAGE_RK3_FULL, p.work, cur, nxt};
-        }
-        Stage& last = st[order - 1];
-        last.post_prev = post_prev;
-        last.post_a = p.op_a ? p.post_a : nullptr; last.op_a = p.op_a;
-        last.post_b = p.op_b ? p.post_b : nullptr; last.op_b = p.op_b;
-        for (int j = 0; j < order; ++j) {
-            st[j].dt = dts[(size_t)k];
-            if ((rc = dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, sigma_host, diag, st[j], s))) return rc;
-        }
-        cur = nxt;
-    }
+    std::vector<Stage> st;
+    rk_schedule(order, p.y_in, p.buf_a, p.buf_b, p.work, dts, post_prev, p.op_a, p.post_a, p.op_b, p.post_b, st);
+    for (const Stage& q : st)
+        if ((rc = dispatch_substep(g, tab, scheme, ham, restrict_sign, params_host, sigma_host, diag, q, s))) return rc;
     if (t_host) *t_host = tend;
     if (steps_host) *steps_host = n;
-    if (result_in_host) *result_in_host = n == 0 ? 0 : 1 + (int32_t)((n - 1) & 1);
+    if (result_in_host) *result_in_host = result_in(n);
     return HJ_OK;
 }
 

@@ -223,6 +223,37 @@ def test_the_schedule_is_hjb_plans():
         assert (tout.value, n.value, where.value) == (tb.value, nb.value, 0) == (0.5, 0, 0)
 
 
+def test_what_the_three_stage_libraries_share_is_defined_once():
+    """libhj_batch.so, libhj_stoch.so and libhj_hidim.so: the descriptor's fill_grid, key_to_double, array_op, struct Stage and the RK
+    buffer rotation have one definition each -- in hj_stage_host.h, hj_stage_dev.h or (key_to_double, beside key_max) hj_device.h --
+    and none in the libraries' own files.  (tests/test_stage_libs_host.py holds the three libraries' refusals to one table.)"""
+    src = lambda n: open(os.path.join(ROOT, "levelsetpy_amd", "csrc", n)).read()      # noqa: E731
+    host, dev, device = src("hj_stage_host.h"), src("hj_stage_dev.h"), src("hj_device.h")
+    own = {n: src(n) for n in ("hj_batch.hip", "hj_stoch.hip", "hj_hidim.hip", "hj_hidim_dev.h", "hj_api.hip")}
+    definitions = {
+        "fill_grid": r"^template <[^>]*>\s*(?:static |inline )*void fill_grid\(const \w+\* g,",
+        "key_to_double": r"^(?:static |inline )*double key_to_double\(",
+        "array_op": r"^(?:__device__ |__forceinline__ )+T array_op\(",
+        "struct Stage": r"^struct Stage \{",
+        "rotation": r"outs\[k & 1\]",
+    }
+    home = {"fill_grid": host, "key_to_double": device, "array_op": dev, "struct Stage": host, "rotation": host}
+    # (hj_rk_integrate of hj_api.hip, the context's solver, steps with a bound it measures as it goes: its loop and its words stay its own)
+    words = "the first stage buffer doubles as the output"
+    assert host.count(words) == 1 and not any(words in text for n, text in own.items() if n != "hj_api.hip")
+    for what, rx in definitions.items():
+        assert len(re.findall(rx, home[what], re.M)) == 1, what
+        for n, text in own.items():
+            assert not re.search(rx, text, re.M), (what, n)
+        for other in (host, dev, device):
+            assert other is home[what] or not re.search(rx, other, re.M), what
+    for n in ("hj_batch.hip", "hj_stoch.hip", "hj_hidim.hip"):
+        assert '#include "hj_stage_host.h"' in own[n] and "rk_schedule(" in own[n] and "result_in(" in own[n], n
+    # the device header is hipRTC's too (through hj_hidim_dev.h, and in the cache key's file list): nothing of the host layer in it
+    assert '#include "hj_stage_dev.h"' in own["hj_hidim_dev.h"] and '"/hj_stage_dev.h"' in own["hj_hidim.hip"]
+    assert "hj_tool::" not in dev and "#include \"hj_tool_host.h\"" not in dev and "#include \"hj_stage_host.h\"" not in dev
+
+
 # ------------------------------------------------------------------------------------------ the systems
 def lgrid(name, low_mem=False):
     gmin, gmax, N, pd = HC.limits(name)
