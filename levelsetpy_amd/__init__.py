@@ -47,6 +47,7 @@ from .measure import setVolume, setCompare, setBounds, truncateGrid             
 from . import hidim                                                              # noqa: F401
 from . import stochastic                                                         # noqa: F401
 from .montecarlo import computeStochTrajs, reachProbability                     # noqa: F401
+from .safety import computeSafeTrajs, safeControls                              # noqa: F401
 from .hidim_ham import register_hidim_hamiltonian, HidimRegistration, HidimSystem, hidim_kernel_cache_stats   # noqa: F401
 from .plant import register_plant, PlantRegistration, PlantSystem, plant_kernel_cache_stats   # noqa: F401
 

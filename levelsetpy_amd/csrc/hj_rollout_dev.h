@@ -1,5 +1,5 @@
 // Device code shared by the rollout kernels of libhj_rollout.so (hj_rollout.hip), libhj_hiquery.so (hj_hiquery.hip), libhj_mc.so (hj_mc.hip,
-// through the hook type below) and the ones libhj_plant.so has hipRTC compile (hj_plant.hip): what does not depend on the plant -- sgn, the RK4 step, and a trajectory from
+// through the hook type below), libhj_filter.so (hj_filter.hip, through a hook type with the filter's points) and the ones libhj_plant.so has hipRTC compile (hj_plant.hip): what does not depend on the plant -- sgn, the RK4 step, and a trajectory from
 // its first state to its last (the bisection over the stored sets, the costate, the sub-steps).  One source, so a 5-D / 6-D
 // trajectory is stepped by the statements a 2-D .. 4-D one is.  At the end, the host side the three share: check_rollout.
 // A plant is a specialisation of Plant<ID> in the including file: ND, controls(P, p, x, c0, c1), f(P, x, c0, c1, k).  A plant with
@@ -84,6 +84,17 @@ struct RolloutOut {
 // default the statements are discarded, and the kernels of libhj_rollout.so, libhj_hiquery.so and libhj_plant.so are what they were.
 struct NoHooks { static constexpr bool plain = true; };
 
+// A hook type that names a member type Filter has three more points (libhj_filter.so's FilterHooks, hj_filter_dev.h), detected the way
+// control_of detects Control, so NoHooks and hj_mc_dev.h's NoisyHooks stay as they are and their kernels keep their code: decide(),
+// between the plant's controls and the RK4 step, sees the column, the sub-step, the slice, the state, the held values and the body's own
+// value and costate queries (the costate of any stack on the grid) and may replace the held values; at_end(), before the outputs,
+// sees the same queries and whether the trajectory left the grid; a type whose `point` is true is answered at the first state alone:
+// decided(), and no step is taken.
+template <typename HK, typename = void> struct filter_of { static constexpr bool value = false, point = false; };
+template <typename HK> struct filter_of<HK, typename void_of<typename HK::Filter>::type> {
+    static constexpr bool value = true, point = HK::point;
+};
+
 // The body of a rollout kernel: the thread's trajectory (2^ND lanes per trajectory, this thread one corner of its cell).
 // Control flow is uniform inside a group and predicated across groups: see hj_rollout.hip.
 template <typename T, int SCHEME, typename PL, typename UP, typename PD = hjr_plant, typename HK = NoHooks>
@@ -130,12 +141,12 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
     };
     // grad V[f](x) in fp64: costate_points_kernel's `costate`.  The middle block is hjq::corner_derivs' statements, written out: calling it
     // here costs the 4-D kernels two VGPRs and 36 bytes of scratch (profiles/refactor_query_rollout.txt).
-    auto costate_at = [&](int f, double* p) {
+    auto costate_in = [&](const T* __restrict__ base, long long stride, int f, double* p) {
         T cC[ND];
 #pragma unroll
         for (int d = 0; d < ND; ++d) cC[d] = T(0);
         if (inside && used) {
-            const T* pc0 = data + (long long)f * field_stride + off;
+            const T* pc0 = base + (long long)f * stride + off;
             const T raw = *pc0;
             if (!hjq::finite(raw)) {
                 // the node's own NaN / inf is put back after the differences (computeGradients: NaN stays NaN, +-inf becomes +inf)
@@ -166,12 +177,22 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
             p[d] = inside ? sC : nan;
         }
     };
+    auto costate_at = [&](int f, double* p) { costate_in(data, field_stride, f, p); };
 
     double* __restrict__ row = O.traj + m * ND * (long long)ntimes;         // traj[m][d][col] = row[d * ntimes + col]
     bool paths = true;                             // a hook may run without traj
     if constexpr (!HK::plain) paths = O.traj != nullptr;
     int* __restrict__ te_row = O.t_earliest ? O.t_earliest + m * (long long)ntimes : nullptr;
     find();
+    if constexpr (filter_of<HK>::point) {
+        double p[ND];
+        typename control_of<PL>::type ctl;
+        const int f = H.field();
+        costate_at(f, p);
+        plant_controls<PL>(P, p, x, ctl);
+        H.decided(m, c, x, p, ctl, P, value_at(f));
+        return;
+    }
     if (c == 0 && paths) {
 #pragma unroll
         for (int d = 0; d < ND; ++d) row[d * (long long)ntimes] = x[d];
@@ -203,6 +224,7 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
                 typename control_of<PL>::type ctl;
                 costate_at(tE, p);
                 plant_controls<PL>(P, p, x, ctl);
+                if constexpr (filter_of<HK>::value) H.decide(m, c, it, s, tE, x, ctl, P, value_at, costate_in);
                 rk4<PL>(P, x, dt_small, ctl);
                 if constexpr (!HK::plain) H.after_substep(x, it, s);
                 find();
@@ -216,6 +238,7 @@ __device__ __forceinline__ void rollout_body(const T* __restrict__ data, long lo
             for (int d = 0; d < ND; ++d) row[d * (long long)ntimes + it + 1] = done ? nan : x[d];
         }
     }
+    if constexpr (filter_of<HK>::value) H.at_end(P, value_at, left);
     if (c == 0) {
         if (te_row) te_row[ntimes - 1] = -1;
         O.length[m] = len;
