@@ -40,7 +40,11 @@
  */
 #ifndef HJ_FILTER_H
 #define HJ_FILTER_H
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else                                  /* hipRTC has no system headers and declares the signed widths alone */
+typedef __UINT8_TYPE__ uint8_t;
+#endif
 #include "hj_rollout.h"
 
 #ifdef __cplusplus

@@ -32,7 +32,12 @@
  */
 #ifndef HJ_MC_H
 #define HJ_MC_H
+#ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else                                  /* hipRTC has no system headers and declares the signed widths alone */
+typedef __UINT32_TYPE__ uint32_t;
+typedef __UINT64_TYPE__ uint64_t;
+#endif
 #include "hj_rollout.h"
 
 #ifdef __cplusplus

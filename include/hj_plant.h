@@ -27,6 +27,9 @@
 #define HJ_PLANT_H
 #ifndef __HIPCC_RTC__
 #include <stdint.h>
+#else                                  /* hipRTC has no system headers and declares the signed widths alone */
+typedef __UINT8_TYPE__ uint8_t;
+typedef __UINT64_TYPE__ uint64_t;
 #endif
 #include "hj_hidim.h"
 #include "hj_rollout.h"
@@ -82,9 +85,57 @@ int hjp_rollout_hi(const hjh_grid* g, int scheme, const void* data, int64_t ntim
                    int64_t nstates, int sub_samples, double dt_small, const hjp_plant* plant, double* traj, int32_t* length,
                    int32_t* t_earliest, int32_t* status, void* stream);
 
+/* ---- a registered plant under the Monte Carlo check of hj_mc.h and the safety filter of hj_filter.h.  The kernels are that
+ * library's trajectory bodies compiled at run time around the plant, as user_rollout_kernel is: user_noisy_rollout_kernel,
+ * user_filtered_rollout_kernel, user_decide_points_kernel<T, SCHEME>.  _hi: a plant of 5 or 6 states on an hjh_grid. */
+enum { HJP_KERNEL_ROLLOUT = 0, HJP_KERNEL_NOISY = 1, HJP_KERNEL_FILTERED = 2, HJP_KERNEL_DECIDE = 3 };
+
+/* hjp_plant_compile_check for the kernel of `kind` (HJP_KERNEL_*).  A plant without controls has no FILTERED / DECIDE kernel */
+int hjp_plant_compile_kind(int plant_id, int kind, int scheme, int dtype);
+
+/* hjn_rollout (hj_mc.h): its arguments, its contract word for word, its outputs.  The checks are hjp_rollout's, then hjn_rollout's.
+ * G is ndim x ndim, row-major, HOST memory. */
+int hjp_noisy_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                      int64_t nstates, int64_t nreal, uint64_t first_realisation, uint64_t seed, const double* normals,
+                      const double* G, double sq, int policy, int sub_samples, double dt_small, const hjp_plant* plant,
+                      double* final_state, int32_t* length, int32_t* status, double* value_end, double* value_min, double* traj,
+                      int32_t* t_earliest, void* stream);
+int hjp_noisy_rollout_hi(const hjh_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                         int64_t nstates, int64_t nreal, uint64_t first_realisation, uint64_t seed, const double* normals,
+                         const double* G, double sq, int policy, int sub_samples, double dt_small, const hjp_plant* plant,
+                         double* final_state, int32_t* length, int32_t* status, double* value_end, double* value_min, double* traj,
+                         int32_t* t_earliest, void* stream);
+
+/* hjf_rollout (hj_filter.h) with the plant's held values u[0 .. ncontrols) and dst[0 .. ndisturbances): the nominal replaces the
+ * controls u[] (a row of u_nom has ncontrols values; the value nominal runs controls_src on grad Vn with u_max from nom_u_mode and
+ * takes its u[] only), HJF_DSTB_ZERO sets every dst[j] to 0.0.  applied (may be null): nstates x nsteps x W fp64, W = max(2,
+ * ncontrols + ndisturbances): u then dst, padded with 0.0.  Everything else as there; the checks are hjp_rollout's, then
+ * hjf_rollout's.  HJ_EINVAL for a plant without controls: there is nothing to filter. */
+int hjp_filtered_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                         int64_t nstates, int sub_samples, double dt_small, const hjp_plant* plant, int slice_policy, int64_t slice,
+                         int nominal, const double* u_nom, const void* nom_data, int64_t nom_ntimes, int64_t nom_field_stride,
+                         int nom_u_mode, double level, double margin, int dstb, double* final_state, double* gap_min,
+                         double* value_end, int32_t* interventions, int32_t* first_intervention, int32_t* length, int32_t* status,
+                         double* traj, uint8_t* active, double* applied, void* stream);
+int hjp_filtered_rollout_hi(const hjh_grid* g, int scheme, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
+                            int64_t nstates, int sub_samples, double dt_small, const hjp_plant* plant, int slice_policy,
+                            int64_t slice, int nominal, const double* u_nom, const void* nom_data, int64_t nom_ntimes,
+                            int64_t nom_field_stride, int nom_u_mode, double level, double margin, int dstb, double* final_state,
+                            double* gap_min, double* value_end, int32_t* interventions, int32_t* first_intervention, int32_t* length,
+                            int32_t* status, double* traj, uint8_t* active, double* applied, void* stream);
+
+/* hjf_decide (hj_filter.h): u_nom nstates x ncontrols, applied nstates x W */
+int hjp_decide(const hjq_grid* g, int scheme, const void* data, int64_t nfields, int64_t field_stride, int64_t slice, const double* xs,
+               int64_t nstates, const hjp_plant* plant, const double* u_nom, double level, double margin, int dstb, double* applied,
+               uint8_t* active, double* value, double* gap, double* costate, void* stream);
+int hjp_decide_hi(const hjh_grid* g, int scheme, const void* data, int64_t nfields, int64_t field_stride, int64_t slice,
+                  const double* xs, int64_t nstates, const hjp_plant* plant, const double* u_nom, double level, double margin, int dstb,
+                  double* applied, uint8_t* active, double* value, double* gap, double* costate, void* stream);
+
 const char* hjp_last_error(void);
 /* name of the kernel the calling thread's last successful launch ran, e.g.
- * "user_rollout_kernel<double, 3, PlantUser:planar_quad>" (element type, scheme, plant) */
+ * "user_rollout_kernel<double, 3, PlantUser:planar_quad>" or "user_filtered_rollout_kernel<double, 3, PlantUser:planar_quad>"
+ * (element type, scheme, plant) */
 const char* hjp_last_kernel(void);
 
 #ifdef __cplusplus

@@ -12,6 +12,9 @@ MAX_CONTROLS = 8                                   # HJP_MAX_CONTROLS
 MIN_DIM, MAX_DIM = 2, 6                            # HJP_MIN_DIM, HJP_MAX_DIM
 PLANT_BASE = 1000000                               # HJP_PLANT_BASE
 SCHEMES = _qffi.POINT_SCHEMES                      # the schemes user_rollout_kernel is instantiated for
+KERNEL_ROLLOUT, KERNEL_NOISY, KERNEL_FILTERED, KERNEL_DECIDE = 0, 1, 2, 3      # HJP_KERNEL_*
+KINDS = {"rollout": KERNEL_ROLLOUT, "noisy": KERNEL_NOISY, "filtered": KERNEL_FILTERED, "decide": KERNEL_DECIDE}
+KERNELS = ("user_rollout_kernel", "user_noisy_rollout_kernel", "user_filtered_rollout_kernel", "user_decide_points_kernel")
 
 
 class Plant(C.Structure):
@@ -22,7 +25,12 @@ class Plant(C.Structure):
 
 _vp, _i, _i64, _d = C.c_void_p, C.c_int, C.c_int64, C.c_double
 _pi = C.POINTER(C.c_int)
+_u64 = C.c_uint64
 _roll = [_i, _vp, _i64, _i64, _vp, _i64, _i, _d, C.POINTER(Plant), _vp, _vp, _vp, _vp, _vp]
+# hjn_rollout's, hjf_rollout's and hjf_decide's lists after the grid, with the plant descriptor this library's
+_noisy = [_i, _vp, _i64, _i64, _vp, _i64, _i64, _u64, _u64, _vp, _vp, _d, _i, _i, _d, C.POINTER(Plant)] + [_vp] * 8
+_filtered = [_i, _vp, _i64, _i64, _vp, _i64, _i, _d, C.POINTER(Plant), _i, _i64, _i, _vp, _vp, _i64, _i64, _i, _d, _d, _i] + [_vp] * 11
+_decide = [_i, _vp, _i64, _i64, _i64, _vp, _i64, C.POINTER(Plant), _vp, _d, _d, _i] + [_vp] * 6
 
 # name -> (restype, argtypes): every symbol the header declares
 SIGNATURES = {
@@ -33,6 +41,13 @@ SIGNATURES = {
     "hjp_plant_compile_check": (_i, [_i, _i, _i]),
     "hjp_rollout": (_i, [C.POINTER(_qffi.Grid)] + _roll),
     "hjp_rollout_hi": (_i, [C.POINTER(_hffi.Grid)] + _roll),
+    "hjp_plant_compile_kind": (_i, [_i, _i, _i, _i]),
+    "hjp_noisy_rollout": (_i, [C.POINTER(_qffi.Grid)] + _noisy),
+    "hjp_noisy_rollout_hi": (_i, [C.POINTER(_hffi.Grid)] + _noisy),
+    "hjp_filtered_rollout": (_i, [C.POINTER(_qffi.Grid)] + _filtered),
+    "hjp_filtered_rollout_hi": (_i, [C.POINTER(_hffi.Grid)] + _filtered),
+    "hjp_decide": (_i, [C.POINTER(_qffi.Grid)] + _decide),
+    "hjp_decide_hi": (_i, [C.POINTER(_hffi.Grid)] + _decide),
     "hjp_last_error": (C.c_char_p, []),
     "hjp_last_kernel": (C.c_char_p, []),
 }
@@ -48,6 +63,6 @@ def plant_descriptor(plant_id, u_mode, d_mode, params):
     return p
 
 
-def kernel_name(dtype_name, scheme, plant_name):
-    """What hjp_last_kernel() reads after a rollout of this instantiation."""
-    return "user_rollout_kernel<%s, %d, PlantUser:%s>" % ("double" if dtype_name == "float64" else "float", scheme, plant_name)
+def kernel_name(dtype_name, scheme, plant_name, kind="rollout"):
+    """What hjp_last_kernel() reads after a launch of this instantiation."""
+    return "%s<%s, %d, PlantUser:%s>" % (KERNELS[KINDS[kind]], "double" if dtype_name == "float64" else "float", scheme, plant_name)

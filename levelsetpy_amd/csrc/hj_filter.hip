@@ -6,6 +6,8 @@
 //                                              decision, no step
 // The nominal kind, the slice policy and the disturbance rule are kernel arguments: wave-uniform branches.  Control flow is uniform inside a
 // group of lanes (every lane holds the same gap bits) and predicated across groups.  No shared memory, no reduction across trajectories.
+// The filter's checks stand in this file alone.  hj_plant.hip, whose filter kernels for registered plants are compiled at run time, reads
+// them from here: it includes this file with HJ_FILTER_CHECKS_ONLY defined, which leaves out the kernels and the entry points.
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include "hj_tool_host.h"
@@ -21,6 +23,7 @@ using hjq::QStencil;
 using hjq::UpwindSolver;
 using namespace hj_tool;
 
+#ifndef HJ_FILTER_CHECKS_ONLY
 template <typename T, int SCHEME, int PLANT>
 __global__ __launch_bounds__(256) void filtered_rollout_kernel(const T* __restrict__ data, long long field_stride, int ntimes,
                                                                const double* __restrict__ x0, long long M, QGrid G, QStencil<T> S,
@@ -42,6 +45,8 @@ __global__ __launch_bounds__(256) void decide_points_kernel(const T* __restrict_
                                                                   hjr::RolloutOut{nullptr, nullptr, nullptr, nullptr},
                                                                   HK{F, E, 0.0, 0.0, 0, -1, false, false});
 }
+
+#endif  // HJ_FILTER_CHECKS_ONLY
 
 // ---------------------------------------------------------------------------------------------- host side
 static const char TOO_MANY_STATES[] = "too many states for one launch (nstates * 2^ndim must be below 2^32): split over states";
@@ -68,6 +73,37 @@ static int check_states(int64_t nstates, int ndim) {
     return HJ_OK;
 }
 
+// hjf_rollout's refusals after check_rollout's and before the look at `go`; single: one field serves every time stamp.  CLOCK: slice <- 0
+static int check_rollout_filter(long long total, int64_t ntimes, int sub_samples, bool single, int slice_policy, int64_t& slice, int nominal,
+                                int64_t nom_ntimes, int64_t nom_field_stride, int nom_u_mode, double level, double margin, int dstb) {
+    if (slice_policy != HJF_SLICE_CLOCK && slice_policy != HJF_SLICE_STATIC)
+        return fail(HJ_EINVAL, "slice_policy %d is neither HJF_SLICE_CLOCK nor HJF_SLICE_STATIC", slice_policy);
+    if (slice_policy == HJF_SLICE_CLOCK) slice = 0;               // not read
+    int rc = check_filter(single ? 1 : ntimes, slice, level, margin, dstb);
+    if (rc) return rc;
+    if (nominal != HJF_NOMINAL_TABLE && nominal != HJF_NOMINAL_VALUE)
+        return fail(HJ_EINVAL, "nominal %d is neither HJF_NOMINAL_TABLE nor HJF_NOMINAL_VALUE", nominal);
+    if (nominal == HJF_NOMINAL_VALUE) {
+        if (nom_ntimes != 1 && nom_ntimes != ntimes)
+            return fail(HJ_EINVAL, "nom_ntimes %lld: the nominal value function has one field or ntimes (%lld)", (long long)nom_ntimes, (long long)ntimes);
+        if (nom_ntimes > 1 && nom_field_stride < total)
+            return fail(HJ_EINVAL, "nom_field_stride %lld is smaller than the grid (%lld)", (long long)nom_field_stride, total);
+        if (nom_u_mode != HJR_MODE_MIN && nom_u_mode != HJR_MODE_MAX) return fail(HJ_EINVAL, "nom_u_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
+    }
+    if ((ntimes - 1) * (long long)sub_samples > 0x7fffffffll)
+        return fail(HJ_EINVAL, "(ntimes - 1) * sub_samples = %lld: a step index is an int32", (long long)((ntimes - 1) * (long long)sub_samples));
+    return HJ_OK;
+}
+
+// hjf_decide's
+static int check_decide_filter(long long total, int64_t nfields, int64_t field_stride, int64_t slice, double level, double margin, int dstb) {
+    if (nfields < 1 || nfields > 0x7fffffffll) return fail(HJ_EINVAL, "nfields %lld: a decision needs a stored set", (long long)nfields);
+    if (nfields > 1 && field_stride < total)
+        return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
+    return check_filter(nfields, slice, level, margin, dstb);
+}
+
+#ifndef HJ_FILTER_CHECKS_ONLY
 template <typename F3> static int dispatch_plant(const hjq_grid* g, int scheme, const hjr_plant* plant, F3&& f) {
     static_assert(HJ_HAM_DUBINS_REL == 0 && HJ_HAM_DOUBLE_INTEGRATOR == 1 && HJ_HAM_DOUBLE_PENDULUM == 2, "plant ids name the kernels");
     return dispatch(g->dtype, scheme, [&](auto t, auto sch) {
@@ -77,8 +113,11 @@ template <typename F3> static int dispatch_plant(const hjq_grid* g, int scheme, 
     });
 }
 
+#endif  // HJ_FILTER_CHECKS_ONLY
+
 }  // namespace hjf
 
+#ifndef HJ_FILTER_CHECKS_ONLY
 using namespace hjf;
 
 extern "C" {
@@ -100,21 +139,9 @@ int hjf_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes,
     rc = hjr::check_rollout(G, total, scheme, data, ntimes, single ? (int64_t)total : field_stride, x0, nstates, sub_samples, dt_small,
                             plant, final_state, length, status, [&]() { return check_plant(plant, G); }, go);
     if (rc) return rc;
-    if (slice_policy != HJF_SLICE_CLOCK && slice_policy != HJF_SLICE_STATIC)
-        return fail(HJ_EINVAL, "slice_policy %d is neither HJF_SLICE_CLOCK nor HJF_SLICE_STATIC", slice_policy);
-    if (slice_policy == HJF_SLICE_CLOCK) slice = 0;               // not read
-    if ((rc = check_filter(single ? 1 : ntimes, slice, level, margin, dstb))) return rc;
-    if (nominal != HJF_NOMINAL_TABLE && nominal != HJF_NOMINAL_VALUE)
-        return fail(HJ_EINVAL, "nominal %d is neither HJF_NOMINAL_TABLE nor HJF_NOMINAL_VALUE", nominal);
-    if (nominal == HJF_NOMINAL_VALUE) {
-        if (nom_ntimes != 1 && nom_ntimes != ntimes)
-            return fail(HJ_EINVAL, "nom_ntimes %lld: the nominal value function has one field or ntimes (%lld)", (long long)nom_ntimes, (long long)ntimes);
-        if (nom_ntimes > 1 && nom_field_stride < total)
-            return fail(HJ_EINVAL, "nom_field_stride %lld is smaller than the grid (%lld)", (long long)nom_field_stride, total);
-        if (nom_u_mode != HJR_MODE_MIN && nom_u_mode != HJR_MODE_MAX) return fail(HJ_EINVAL, "nom_u_mode must be HJR_MODE_MIN or HJR_MODE_MAX");
-    }
-    if ((ntimes - 1) * (long long)sub_samples > 0x7fffffffll)
-        return fail(HJ_EINVAL, "(ntimes - 1) * sub_samples = %lld: a step index is an int32", (long long)((ntimes - 1) * (long long)sub_samples));
+    if ((rc = check_rollout_filter(total, ntimes, sub_samples, single, slice_policy, slice, nominal, nom_ntimes, nom_field_stride, nom_u_mode, level,
+                                   margin, dstb)))
+        return rc;
     if (!go) {
         launched_none();
         return HJ_OK;
@@ -152,10 +179,7 @@ int hjf_decide(const hjq_grid* g, int scheme, const void* data, int64_t nfields,
     rc = hjr::check_rollout(G, total, scheme, data, 2, (int64_t)total, xs, nstates, 1, 0.0, plant, applied, active, value,
                             [&]() { return check_plant(plant, G); }, go);
     if (rc) return rc;
-    if (nfields < 1 || nfields > 0x7fffffffll) return fail(HJ_EINVAL, "nfields %lld: a decision needs a stored set", (long long)nfields);
-    if (nfields > 1 && field_stride < total)
-        return fail(HJ_EINVAL, "field_stride %lld is smaller than the grid (%lld)", (long long)field_stride, total);
-    if ((rc = check_filter(nfields, slice, level, margin, dstb))) return rc;
+    if ((rc = check_decide_filter(total, nfields, field_stride, slice, level, margin, dstb))) return rc;
     if (!go) {
         launched_none();
         return HJ_OK;
@@ -181,3 +205,4 @@ int hjf_decide(const hjq_grid* g, int scheme, const void* data, int64_t nfields,
 HJ_TOOL_LAST_SYMBOLS(hjf)
 
 }  // extern "C"
+#endif  // HJ_FILTER_CHECKS_ONLY

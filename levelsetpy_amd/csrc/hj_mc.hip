@@ -53,9 +53,7 @@ __global__ __launch_bounds__(256) void normals_kernel(unsigned long long seed, u
     }
 }
 
-// ---------------------------------------------------------------------------------------------- host side
-static const char TOO_MANY_REAL[] = "too many realisations for one launch (nstates * nreal * 2^ndim must be below 2^32): split over states";
-
+// ---------------------------------------------------------------------------------------------- host side (the noise's checks: hj_mc_dev.h)
 template <typename T, int SCHEME, int PLANT>
 static int launch(const hjq_grid* g, const QGrid& G, const void* data, int64_t ntimes, int64_t field_stride, const double* x0,
                   long long groups, long long R, int sub_samples, double dt_small, const hjr_plant& P, const Noise& N,
@@ -109,17 +107,9 @@ int hjn_rollout(const hjq_grid* g, int scheme, const void* data, int64_t ntimes,
         return (int)HJ_OK;
     }, go);
     if (rc) return rc;
-    if (nreal < 1) return fail(HJ_EINVAL, "nreal must be at least 1");
-    if (policy != HJN_POLICY_EARLIEST && policy != HJN_POLICY_CLOCK) return fail(HJ_EINVAL, "policy %d is neither HJN_POLICY_EARLIEST nor HJN_POLICY_CLOCK", policy);
-    if (!std::isfinite(sq)) return fail(HJ_EINVAL, "sq must be finite");
-    if (!Gm) return fail(HJ_EINVAL, "null argument: G");
-    for (int k = 0; k < G.ndim * G.ndim; ++k)
-        if (!std::isfinite(Gm[k])) return fail(HJ_EINVAL, "G[%d][%d] is not finite", k / G.ndim, k % G.ndim);
-    if ((ntimes - 1) * (long long)sub_samples > 0x100000000ll)
-        return fail(HJ_EINVAL, "(ntimes - 1) * sub_samples = %lld: the counter holds a step in 32 bits", (long long)((ntimes - 1) * (long long)sub_samples));
+    if ((rc = check_noise(G.ndim, ntimes, sub_samples, nreal, policy, sq, Gm))) return rc;
     if (!go) return HJ_OK;
-    if (!value_end || !value_min) return fail(HJ_EINVAL, "null argument");
-    if (nreal > 0xffffffffll || nstates > 0xffffffffll || nstates * nreal > (0xffffffffll >> G.ndim)) return fail(HJ_EINVAL, "%s", TOO_MANY_REAL);
+    if ((rc = check_realisations(G.ndim, nstates, nreal, value_end, value_min))) return rc;
     Noise N;
     N.normals = normals;
     N.first = first_realisation;

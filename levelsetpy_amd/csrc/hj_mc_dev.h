@@ -154,5 +154,32 @@ template <int ND> struct NoisyHooks {
     }
 };
 
+// ---------------------------------------------------------------------------------------------- host side
+#ifndef HJ_RTC
+// The checks of a noisy rollout's entry point (hjn_rollout; hjp_noisy_rollout / _hi of libhj_plant.so) after check_rollout's, in the
+// order the refusals are documented in: check_noise before the look at `go`, check_realisations after it.
+static const char TOO_MANY_REAL[] = "too many realisations for one launch (nstates * nreal * 2^ndim must be below 2^32): split over states";
+
+static int check_noise(int ndim, int64_t ntimes, int sub_samples, int64_t nreal, int policy, double sq, const double* Gm) {
+    using hj_tool::fail;
+    if (nreal < 1) return fail(HJ_EINVAL, "nreal must be at least 1");
+    if (policy != HJN_POLICY_EARLIEST && policy != HJN_POLICY_CLOCK) return fail(HJ_EINVAL, "policy %d is neither HJN_POLICY_EARLIEST nor HJN_POLICY_CLOCK", policy);
+    if (!std::isfinite(sq)) return fail(HJ_EINVAL, "sq must be finite");
+    if (!Gm) return fail(HJ_EINVAL, "null argument: G");
+    for (int k = 0; k < ndim * ndim; ++k)
+        if (!std::isfinite(Gm[k])) return fail(HJ_EINVAL, "G[%d][%d] is not finite", k / ndim, k % ndim);
+    if ((ntimes - 1) * (long long)sub_samples > 0x100000000ll)
+        return fail(HJ_EINVAL, "(ntimes - 1) * sub_samples = %lld: the counter holds a step in 32 bits", (long long)((ntimes - 1) * (long long)sub_samples));
+    return HJ_OK;
+}
+
+static int check_realisations(int ndim, int64_t nstates, int64_t nreal, const void* value_end, const void* value_min) {
+    using hj_tool::fail;
+    if (!value_end || !value_min) return fail(HJ_EINVAL, "null argument");
+    if (nreal > 0xffffffffll || nstates > 0xffffffffll || nstates * nreal > (0xffffffffll >> ndim)) return fail(HJ_EINVAL, "%s", TOO_MANY_REAL);
+    return HJ_OK;
+}
+#endif  // HJ_RTC
+
 }  // namespace hjn
 #endif

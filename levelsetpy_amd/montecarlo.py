@@ -31,6 +31,12 @@ launch of noisy_rollout_kernel (libhj_mc.so) per split.  Plane5D / DubinsPair6D,
 derivative function without a point kernel take a host loop on dynSys.get_opt_u / get_opt_v / update_state with the same
 generator (hjn_normals_host) and the same output contract, and say so in an info line.
 
+extraArgs.plantKernel=True (a bool, default False) sends two more kinds of system to a kernel, after the built-in rule: a registered plant
+(plant.register_plant; plant_of's identity rule, the registration's dimension, a derivative function with a point kernel) and Plane5D /
+DubinsPair6D, which the package registers itself at their first use (plant_builtin.py).  libhj_plant.so compiles
+user_noisy_rollout_kernel around the plant at run time, under the contract above word for word; whatever is not eligible under the flag
+keeps the host loop and its info line.
+
 reachProbability forms its sums with torch / NumPy on the returned arrays: the kernel uses no float atomics.
 Parity UNPINNED: the reference has no counterpart (its computeOptTraj cannot run).
 """
@@ -39,7 +45,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _nffi, _rffi
+from . import _nffi, _pffi, _rffi, plant_builtin
 from .context import is_tensor, require_gpu
 from .dynamics import native_plant, native_plant_hi
 from .query import interp_states, costate_states, point_scheme, states_2d
@@ -49,7 +55,8 @@ from .stochastic import check_sigma
 from .utilities import Bundle, error, info
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, device_data as _device_data,
                        device_states as _device_states, stream as _stream, ptr as _ptr, fields as _fields,
-                       descriptor as _descriptor, dtype_name as _dtype_name, is_hi as _is_hi)
+                       descriptor as _descriptor, dtype_name as _dtype_name, is_hi as _is_hi, descriptor_hi as _descriptor_hi)
+from .plant import PlantRegistration
 
 __all__ = ["computeStochTrajs", "reachProbability"]
 
@@ -64,8 +71,14 @@ def last_path():
     return _last_path
 
 
-def _why_host(dynSys, derivFunc, g):
+def _why_host(dynSys, derivFunc, g, plantKernel=False):
+    """(plant, None) when a kernel covers this call, else (None, the reason for the host loop).  plant: native_plant's (id, parameters),
+    or under plantKernel (registration, parameters) of a plant libhj_plant.so compiles a kernel around -- the built-in rule comes first."""
     nat = native_plant(dynSys)
+    if plantKernel and nat is None:
+        user, why = plant_builtin.route(dynSys, derivFunc, g)
+        if user is not None or why is not None:
+            return user, why
     if nat is None:
         if native_plant_hi(dynSys) is not None:
             return None, "%s has no noisy rollout kernel (5-D / 6-D systems are out of its scope)" % type(dynSys).__name__
@@ -81,11 +94,16 @@ def _why_host(dynSys, derivFunc, g):
 
 
 def noisy_rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, G, sq, R, first, seed, normals, policy, keep):
-    """hjn_rollout on device tensors: `data` a contiguous (T,) + g.shape stack, `xs` an (M, dim) fp64 tensor, `normals` None or an
+    """hjn_rollout (hjp_noisy_rollout / _hi for a _pffi.Plant) on device tensors: `data` a contiguous (T,) + g.shape stack, `xs` an (M, dim) fp64 tensor, `normals` None or an
     (M, R, (T-1) subSamples, dim) fp64 device tensor, `G` a (dim, dim) float64 NumPy array.
     -> final, length, status, value_end, value_min, traj or None, t_earliest or None."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    if isinstance(plant, _pffi.Plant):
+        hi = _is_hi(g)
+        ffi, call, describe = _pffi, (_pffi.lib().hjp_noisy_rollout_hi if hi else _pffi.lib().hjp_noisy_rollout), (_descriptor_hi if hi else _descriptor)
+    else:
+        ffi, call, describe = _nffi, _nffi.lib().hjn_rollout, _descriptor
+    desc, N = describe(g, _dtype_name(data))
     T, stride = _fields(data, N)
     M, nd = int(xs.shape[0]), g.dim
     dev = data.device
@@ -95,10 +113,10 @@ def noisy_rollout_states(g, data, xs, scheme, subSamples, dtSmall, plant, G, sq,
     traj, te = (f64(M, R, nd, T), i32(M, R, T)) if keep else (None, None)
     Gm = np.ascontiguousarray(G, dtype=np.float64)
     with torch.cuda.device(dev):
-        _nffi.check(_nffi.lib().hjn_rollout(C.byref(desc), int(scheme), _ptr(data), T, stride, _ptr(xs), M, int(R), int(first),
-                                            int(seed), _ptr(normals), Gm.ctypes.data, float(sq), int(policy), int(subSamples),
-                                            float(dtSmall), C.byref(plant), _ptr(final), _ptr(length), _ptr(status), _ptr(vend),
-                                            _ptr(vmin), _ptr(traj), _ptr(te), _stream(torch, dev)))
+        ffi.check(call(C.byref(desc), int(scheme), _ptr(data), T, stride, _ptr(xs), M, int(R), int(first),
+                       int(seed), _ptr(normals), Gm.ctypes.data, float(sq), int(policy), int(subSamples),
+                       float(dtSmall), C.byref(plant), _ptr(final), _ptr(length), _ptr(status), _ptr(vend),
+                       _ptr(vmin), _ptr(traj), _ptr(te), _stream(torch, dev)))
     return final, length, status, vend, vmin, traj, te
 
 
@@ -243,19 +261,26 @@ def computeStochTrajs(g, data, tau, dynSys, x0s, sigma, extraArgs=None):
     dtSmall = (tau[1] - tau[0]) / subSamples                     # exactly as computeOptTraj forms it
     sq = float(np.sqrt(np.float64(dtSmall)))
     pol = _nffi.POLICIES[policy]
-    nat, why = _why_host(dynSys, derivFunc, g) if not _is_hi(g) else (None, "%s has no noisy rollout kernel on a %d-D grid" % (type(dynSys).__name__, g.dim))
+    plantKernel = plant_builtin.flag(extraArgs)
+    if plantKernel or not _is_hi(g):                             # (a built-in plant on a 5-D / 6-D grid is refused by its dimension there)
+        nat, why = _why_host(dynSys, derivFunc, g, plantKernel)
+    else:
+        nat, why = None, "%s has no noisy rollout kernel on a %d-D grid" % (type(dynSys).__name__, g.dim)
     if why is None:
+        user = isinstance(nat[0], PlantRegistration)
+        ffi = _pffi if user else _nffi
         t = _device_data(data)
         xs = _device_states(x0, t.device)
         nz = _device_states(normals, t.device) if normals is not None else None
-        plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
+        plant = (_pffi.plant_descriptor(nat[0].plant_id, _MODES[uMode], _MODES[dMode or 'min'], nat[1]) if user
+                 else _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1]))
         per = max(1, (LAUNCH_THREADS >> g.dim) // R)             # states one launch holds
         parts = []
         for a in range(0, max(M, 1), per):
             b = min(M, a + per)
             parts.append(noisy_rollout_states(g, t, xs[a:b], point_scheme(derivFunc), subSamples, dtSmall, plant, G, sq, R,
                                               (first + a * R) % 2 ** 64, seed, nz[a:b] if nz is not None else None, pol, keep))
-        _last_path = _nffi.last_kernel() if M else ""
+        _last_path = ffi.last_kernel() if M else ""
         torch = require_gpu()
         outs = [parts[0][i] if len(parts) == 1 else (torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None)
                 for i in range(7)]

@@ -117,10 +117,14 @@ class PlantRegistration(object):
                                                    rtc.encode() if rtc else None, C.byref(pid)))
         self.plant_id = int(pid.value)
 
-    def check(self, scheme="WENO5_ASSHIPPED", dtype="float64"):
-        """Compile user_rollout_kernel of (scheme, dtype) now (no GPU needed): raises ValueError with the compiler's message, which points
-        into the body at fault as name:line, if one is wrong."""
-        _pffi.check(_pffi.lib().hjp_plant_compile_check(self.plant_id, _ffi.SCHEME_IDS[scheme], _ffi.F64 if dtype == "float64" else _ffi.F32))
+    def check(self, scheme="WENO5_ASSHIPPED", dtype="float64", kind="rollout"):
+        """Compile the kernel of (scheme, dtype) now (no GPU needed): raises ValueError with the compiler's message, which points into the
+        body at fault as name:line, if one is wrong.  kind: 'rollout' (user_rollout_kernel: computeOptTrajs), 'noisy' (computeStochTrajs),
+        'filtered' (computeSafeTrajs) or 'decide' (safeControls) -- the last three run under extraArgs.plantKernel."""
+        if kind not in _pffi.KINDS:
+            raise ValueError("kind must be 'rollout', 'noisy', 'filtered' or 'decide' (got %r)" % (kind,))
+        _pffi.check(_pffi.lib().hjp_plant_compile_kind(self.plant_id, _pffi.KINDS[kind], _ffi.SCHEME_IDS[scheme],
+                                                       _ffi.F64 if dtype == "float64" else _ffi.F32))
         return self
 
     def source(self):

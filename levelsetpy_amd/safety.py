@@ -39,6 +39,14 @@ ONE launch of filtered_rollout_kernel (libhj_filter.so) per split over states, a
 Plane5D / DubinsPair6D, a registered plant, a foreign dynSys or a derivative function without a point kernel take a host loop on
 dynSys.get_opt_u / get_opt_v / update_state with the same output contract (controls then holds the system's u then d, flattened,
 padded with 0.0 to two), and say so in an info line.
+
+extraArgs.plantKernel=True (a bool, default False) sends two more kinds of system to a kernel, after the built-in rule: a registered plant
+(plant.register_plant; plant_of's identity rule, the registration's dimension, a derivative function with a point kernel) and Plane5D /
+DubinsPair6D, which the package registers itself at their first use (plant_builtin.py).  libhj_plant.so compiles
+user_filtered_rollout_kernel / user_decide_points_kernel around the plant at run time; the contract is the one above with the plant's
+controls u[0 .. NU) in the nominal's place (a table's last axis is NU = the registration's ncontrols), every dst[j] zeroed by disturbance
+'zero', and controls W = max(2, NU + NDST) wide: u then dst, padded with 0.0 -- the host loop's layout.  Whatever is not eligible under the
+flag keeps the host loop and its info line.
 Parity UNPINNED: the reference has no counterpart.
 """
 import copy
@@ -46,7 +54,7 @@ import ctypes as C
 
 import numpy as np
 
-from . import _fffi, _rffi
+from . import _fffi, _pffi, _rffi, plant_builtin
 from .context import is_tensor, require_gpu
 from .dynamics import native_plant, native_plant_hi
 from .query import interp_states, costate_states, point_scheme, states_2d
@@ -55,7 +63,8 @@ from .spatial import upwindFirstWENO5
 from .utilities import Bundle, error, info, isfield
 from ._marshal import (unlazy as _unlazy, wants_tensor as _wants_tensor, device_data as _device_data,
                        device_states as _device_states, stream as _stream, ptr as _ptr, descriptor as _descriptor,
-                       dtype_name as _dtype_name, is_hi as _is_hi)
+                       dtype_name as _dtype_name, is_hi as _is_hi, descriptor_hi as _descriptor_hi)
+from .plant import PlantRegistration
 
 __all__ = ["computeSafeTrajs", "safeControls", "SAFE", "VIOLATED", "LEFT_GRID"]
 
@@ -72,7 +81,13 @@ def last_path():
     return _last_path
 
 
-def _why_host(dynSys, derivFunc, g):
+def _why_host(dynSys, derivFunc, g, plantKernel=False):
+    """(plant, None) when a kernel covers this call, else (None, the reason for the host loop).  plant: native_plant's (id, parameters),
+    or under plantKernel (registration, parameters) of a plant libhj_plant.so compiles a kernel around -- the built-in rule comes first."""
+    if plantKernel and native_plant(dynSys) is None:
+        user, why = plant_builtin.route(dynSys, derivFunc, g)
+        if user is not None or why is not None:
+            return user, why
     if _is_hi(g):
         return None, "%s has no filter kernel on a %d-D grid" % (type(dynSys).__name__, g.dim)
     nat = native_plant(dynSys)
@@ -140,13 +155,22 @@ def _table(u, lead, M, what):
     return u
 
 
+def _entry(plant, g, name):
+    """(binding, entry point, descriptor function) for a built-in plant's descriptor or a registered plant's (_pffi.Plant)."""
+    if isinstance(plant, _pffi.Plant):
+        hi = _is_hi(g)
+        return _pffi, getattr(_pffi.lib(), "hjp_" + name + ("_hi" if hi else "")), (_descriptor_hi if hi else _descriptor)
+    return _fffi, getattr(_fffi.lib(), "hjf_" + ("rollout" if name == "filtered_rollout" else name)), _descriptor
+
+
 def filtered_rollout_states(g, data, T, xs, scheme, subSamples, dtSmall, plant, policy, k, u_nom, nom, nom_mode, level, margin,
-                            dstb, keep, keep_controls):
-    """hjf_rollout on device tensors: `data` a contiguous (T,) + g.shape stack or one g.shape field (stride 0), `xs` an (M, dim)
+                            dstb, keep, keep_controls, width=2):
+    """hjf_rollout (hjp_filtered_rollout / _hi for a _pffi.Plant, `width` its W) on device tensors: `data` a contiguous (T,) + g.shape stack or one g.shape field (stride 0), `xs` an (M, dim)
     fp64 tensor, `u_nom` an (M, T-1, NU) fp64 tensor or None, `nom` None or a stack / field of data's dtype.
     -> final, gap_min, value_end, interventions, first, length, status, traj or None, active or None, applied or None."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    ffi, call, describe = _entry(plant, g, "filtered_rollout")
+    desc, N = describe(g, _dtype_name(data))
     total = int(np.prod(N))
     stride = 0 if tuple(data.shape) == tuple(N) else total
     M, nd = int(xs.shape[0]), g.dim
@@ -157,10 +181,10 @@ def filtered_rollout_states(g, data, T, xs, scheme, subSamples, dtSmall, plant, 
     final, gmin, vend, count, first, length, status = f64(M, nd), f64(M), f64(M), i32(M), i32(M), i32(M), i32(M)
     traj = f64(M, nd, T) if keep else None
     active = torch.empty((M, nsteps), dtype=torch.uint8, device=dev) if keep_controls else None
-    applied = f64(M, nsteps, 2) if keep_controls else None
+    applied = f64(M, nsteps, width) if keep_controls else None
     nom_T = 0 if nom is None else (1 if tuple(nom.shape) == tuple(N) else int(nom.shape[0]))
     with torch.cuda.device(dev):
-        _fffi.check(_fffi.lib().hjf_rollout(
+        ffi.check(call(
             C.byref(desc), int(scheme), _ptr(data), T, stride, _ptr(xs), M, int(subSamples), float(dtSmall), C.byref(plant), int(policy),
             int(k), _fffi.NOMINAL_TABLE if nom is None else _fffi.NOMINAL_VALUE, _ptr(u_nom), _ptr(nom), nom_T, total, int(nom_mode),
             float(level), float(margin), int(dstb), _ptr(final), _ptr(gmin), _ptr(vend), _ptr(count), _ptr(first), _ptr(length),
@@ -168,20 +192,22 @@ def filtered_rollout_states(g, data, T, xs, scheme, subSamples, dtSmall, plant, 
     return final, gmin, vend, count, first, length, status, traj, active, applied
 
 
-def decide_states(g, data, k, xs, scheme, plant, u_nom, level, margin, dstb):
-    """hjf_decide on device tensors -> applied (M, 2), active (M,) uint8, value, gap (M,), costate (M, dim)."""
+def decide_states(g, data, k, xs, scheme, plant, u_nom, level, margin, dstb, width=2):
+    """hjf_decide (hjp_decide / _hi for a _pffi.Plant, `width` its W) on device tensors -> applied (M, width), active (M,) uint8, value,
+    gap (M,), costate (M, dim)."""
     torch = require_gpu()
-    desc, N = _descriptor(g, _dtype_name(data))
+    ffi, call, describe = _entry(plant, g, "decide")
+    desc, N = describe(g, _dtype_name(data))
     total = int(np.prod(N))
     F = 1 if tuple(data.shape) == tuple(N) else int(data.shape[0])
     M, dev = int(xs.shape[0]), data.device
     f64 = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)        # noqa: E731
-    applied, value, gap, costate = f64(M, 2), f64(M), f64(M), f64(M, g.dim)
+    applied, value, gap, costate = f64(M, width), f64(M), f64(M), f64(M, g.dim)
     active = torch.empty((M,), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        _fffi.check(_fffi.lib().hjf_decide(C.byref(desc), int(scheme), _ptr(data), F, total, int(k), _ptr(xs), M, C.byref(plant),
-                                           _ptr(u_nom), float(level), float(margin), int(dstb), _ptr(applied), _ptr(active),
-                                           _ptr(value), _ptr(gap), _ptr(costate), _stream(torch, dev)))
+        ffi.check(call(C.byref(desc), int(scheme), _ptr(data), F, total, int(k), _ptr(xs), M, C.byref(plant),
+                       _ptr(u_nom), float(level), float(margin), int(dstb), _ptr(applied), _ptr(active),
+                       _ptr(value), _ptr(gap), _ptr(costate), _stream(torch, dev)))
     return applied, active, value, gap, costate
 
 
@@ -302,6 +328,15 @@ def _host_loop(g, data, tau, dynSys, x0, u_nom, nom, nomMode, uMode, dMode, subS
 
 
 # ---------------------------------------------------------------------------------------------- the front ends
+def _kernel_plant(nat, uMode, dMode):
+    """-> (plant descriptor, NU, W, the binding whose last_kernel names the launch) of _why_host's plant."""
+    if isinstance(nat[0], PlantRegistration):
+        reg = nat[0]
+        return (_pffi.plant_descriptor(reg.plant_id, _MODES[uMode], _MODES[dMode or 'min'], nat[1]), reg.ncontrols,
+                max(2, reg.ncontrols + reg.ndisturbances), _pffi)
+    return _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1]), _fffi.PLANT_NU[nat[0]], 2, _fffi
+
+
 def _out_device(torch, data, xs):
     d = _unlazy(data)
     return d.device if is_tensor(d) and d.is_cuda else (xs.device if is_tensor(xs) and xs.is_cuda else "cuda")
@@ -348,16 +383,16 @@ def computeSafeTrajs(g, data, tau, dynSys, x0s, nominal, extraArgs=None):
                   % (tuple(g.shape), (T,) + tuple(g.shape), tuple(nom.shape)))
     else:
         u_nom = _table(nominal, (T - 1,), M, 'nominal')
-    nat, why = _why_host(dynSys, derivFunc, g)
-    if why is None and u_nom is not None and int(u_nom.shape[-1]) != _fffi.PLANT_NU[nat[0]]:
-        error('nominal holds %d controls per column, %s has %d' % (int(u_nom.shape[-1]), type(dynSys).__name__, _fffi.PLANT_NU[nat[0]]))
+    nat, why = _why_host(dynSys, derivFunc, g, plant_builtin.flag(extraArgs))
     if why is None:
+        plant, NU, W, ffi = _kernel_plant(nat, uMode, dMode)
+        if u_nom is not None and int(u_nom.shape[-1]) != NU:
+            error('nominal holds %d controls per column, %s has %d' % (int(u_nom.shape[-1]), type(dynSys).__name__, NU))
         torch = require_gpu()
         t = _device_data(data)
         xs = _device_states(x0, t.device)
         un = _device_states(u_nom, t.device) if u_nom is not None else None
         nt = _device_data(nom).to(device=t.device, dtype=t.dtype).contiguous() if nom is not None else None
-        plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
         dtSmall = (tau[1] - tau[0]) / subSamples                     # exactly as computeOptTraj forms it
         per = max(1, LAUNCH_THREADS >> g.dim)                        # states one launch holds
         parts = []
@@ -365,8 +400,8 @@ def computeSafeTrajs(g, data, tau, dynSys, x0s, nominal, extraArgs=None):
             b = min(M, a + per)
             parts.append(filtered_rollout_states(g, t, T, xs[a:b], point_scheme(derivFunc), subSamples, dtSmall, plant,
                                                  _fffi.POLICIES[policy], k, un[a:b] if un is not None else None, nt, _MODES[nomMode],
-                                                 level, margin, _fffi.DISTURBANCES[dstb], keep, keep_controls))
-        _last_path = _fffi.last_kernel() if M else ""
+                                                 level, margin, _fffi.DISTURBANCES[dstb], keep, keep_controls, W))
+        _last_path = ffi.last_kernel() if M else ""
         outs = [parts[0][i] if len(parts) == 1 else (torch.cat([p[i] for p in parts]) if parts[0][i] is not None else None)
                 for i in range(10)]
         if outs[8] is not None:
@@ -400,15 +435,15 @@ def safeControls(g, data, dynSys, xs, uNom, extraArgs=None):
     x = states_2d(g, xs)
     M = int(x.shape[0])
     u_nom = _table(uNom, (), M, 'uNom')
-    nat, why = _why_host(dynSys, derivFunc, g)
-    if why is None and int(u_nom.shape[-1]) != _fffi.PLANT_NU[nat[0]]:
-        error('uNom holds %d controls per state, %s has %d' % (int(u_nom.shape[-1]), type(dynSys).__name__, _fffi.PLANT_NU[nat[0]]))
+    nat, why = _why_host(dynSys, derivFunc, g, plant_builtin.flag(extraArgs))
     if why is None:
+        plant, NU, W, ffi = _kernel_plant(nat, uMode, dMode)
+        if int(u_nom.shape[-1]) != NU:
+            error('uNom holds %d controls per state, %s has %d' % (int(u_nom.shape[-1]), type(dynSys).__name__, NU))
         t = _device_data(data)
-        plant = _rffi.plant_descriptor(nat[0], _MODES[uMode], _MODES[dMode or 'min'], nat[1])
         outs = list(decide_states(g, t, k, _device_states(x, t.device), point_scheme(derivFunc), plant, _device_states(u_nom, t.device),
-                                  level, margin, _fffi.DISTURBANCES[dstb]))
-        _last_path = _fffi.last_kernel() if M else ""
+                                  level, margin, _fffi.DISTURBANCES[dstb], W))
+        _last_path = ffi.last_kernel() if M else ""
         outs[1] = outs[1].bool()
         if not tensors:
             outs = [o.cpu().numpy() for o in outs]
